@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the rustradio hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already
 resident in HBM.  Default workload = BASELINE.json configs[1]:
     FftFilter, 401 taps (low_pass_complex(10e6, 1e6, 60e3) => reference fft_size 1024,
     nsamples 623), 10 Msps synthetic Complex<f32>, 10 s = 100,000,000 samples per step.
-Other workloads (--workload; every one also runs short in the default run): bench_workloads.py lists them; the drop-in
+Other workloads (--workload; with --full every one also runs short): bench_workloads.py lists them; the drop-in
 path (rr_block_work on reference-sized HOST windows, PCIe-inclusive, never `value`) is bench_dropin.py.
 
 Multi-GPU (`--gpus N`, one process per GPU, weak scaling): when WORLD_SIZE is not set, this process — before it
@@ -17,11 +17,15 @@ by channel: default N > 1 workload = configs[3] (fm_multi: rank r owns channels 
 bank).  The only collective is the fan-out of the shared IQ source: rank 0 produces tile t+1 and RCCL-broadcasts it on a
 communication stream while every rank runs tile t (double buffer, events) — INSIDE the timed region.
 
-Prints ONE JSON line (rank 0), strict JSON under 4 KB: the contract keys, `config`, `roofline` (dominant kernel: mean launch
+A plain run sets up, settles and warms up, times exactly K steps and prints ONE JSON line (rank 0), strict JSON: the
+contract keys (`value`, `ms_per_step` = wall time of the K timed steps / K, ...) and `config`.  --dump-outputs DIR writes
+what the last timed step computed (dump_outputs); the synthetic inputs are seeded, the same in every run.
+
+--full adds everything else, and its line (still under 4 KB) gains `roofline` (dominant kernel: mean launch
 duration from HIP events on its launch stream, algorithmic bytes and executed flops per launch, both fractions, `bound` = the
 larger), `cpu_baseline`, and compact companions (`metric_chain`, `north_star_target`, `parity`, `verified`, `others_brief`).
 Everything else — every workload's full record, the drop-in path, the CPU modes, the multi-GPU prediction, the prose — goes
-to gpurun_out/bench_detail.json (--detail-out) and to stderr BEFORE the line.  After each workload's timed passes one more
+to the detail file (--detail-out) and to stderr BEFORE the line.  After each workload's timed passes one more
 step on fresh handles is checked against a float64 evaluation of the reference's chain (bench_verify.py); a failed check
 makes the exit code 3.  `value` counts input samples entering the first block (x channels for the multi-channel block),
 summed over ranks, per second of max-over-ranks wall time.
@@ -55,10 +59,12 @@ from bench_workloads import HBM_PEAK_GBS, FP32_PEAK_TFLOPS, METRIC, WORKLOADS, m
 
 
 # ---- measurement ------------------------------------------------------------------------------
-def run_timed(w, steps, warmup, dist, stream, fan=None, src_ptr=None, settle_ms=0.0):
+def run_timed(w, steps, warmup, dist, stream, fan=None, src_ptr=None, settle_ms=0.0, extra_passes=True, after_timed=None):
     """W untimed warm-up steps, then EXACTLY `steps` timed steps bracketed by barrier + synchronize on both sides.
     With `fan` (multi.TileFanout) every step's input is the tile rank 0 produced and broadcast during the previous
-    step.  -> units, wall seconds, dominant-kernel ms, launches, dominant units, per-step times (ms, HIP events)
+    step.  `after_timed()` runs right after the timed steps, while the output buffers still hold the last one's result.
+    -> units, wall seconds, dominant-kernel ms, launches, dominant units, per-step times (ms, HIP events); without
+    `extra_passes` the two passes after the timed region are not run (0.0, 0 and [] in their place)
 
     The timed region carries NO instrumentation at all (round 2 kept the dominant block's two
     HIP-event brackets per launch inside it, ~8 us of stream time per step — 10 % of the 0.07 ms fm_chain step, charged
@@ -109,6 +115,14 @@ def run_timed(w, steps, warmup, dist, stream, fan=None, src_ptr=None, settle_ms=
     if settle_ms > 0:
         for _ in range(2):                       # (the very first launch of a kernel pays its one-time set-up)
             one(t); t += 1
+        # The rest runs on w.settle_blocks when there is one (a twin of the chain: fresh handles of the same constructors).  The
+        # number of settle steps follows the clock, and a block carries the part of a window it could not use yet into the next
+        # call: on the timed handles it would make the last timed step's output differ from run to run.
+        timed_blocks = w.blocks
+        w.blocks = getattr(w, "settle_blocks", None) or timed_blocks
+        n_twin = 0 if w.blocks is timed_blocks else 1
+        for _ in range(n_twin):                  # (the twin's own first call)
+            one(t); t += 1
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
         for _ in range(4):
@@ -123,7 +137,8 @@ def run_timed(w, steps, warmup, dist, stream, fan=None, src_ptr=None, settle_ms=
             n_settle = int(ns.item())
         for _ in range(n_settle):
             one(t); t += 1
-        n_settle += 6
+        w.blocks = timed_blocks
+        n_settle += 6 + n_twin
     w.settle_steps = n_settle
     for _ in range(warmup):
         one(t); t += 1
@@ -142,6 +157,10 @@ def run_timed(w, steps, warmup, dist, stream, fan=None, src_ptr=None, settle_ms=
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if after_timed is not None:
+        after_timed()
+    if not extra_passes:
+        return units, dt, 0.0, 0, w.dom_units, []
     # second pass: the dominant kernel alone (the library's HIP-event brackets on the launch stream)
     w.blocks[w.dominant].set_profiling(True)
     w.dom_units = 0
@@ -161,6 +180,55 @@ def run_timed(w, steps, warmup, dist, stream, fan=None, src_ptr=None, settle_ms=
     step_ms = [a.elapsed_time(b) for a, b in evs]
     w.dom_units = dom_units
     return units, dt, kms, launches, dom_units, step_ms
+
+
+DUMP_LIMIT = 64_000_000        # bytes: every file --dump-outputs writes, together
+DUMP_SEED = 0xD0_5EED
+
+
+def dump_positions(p, k, seed=DUMP_SEED):
+    """k sorted positions in [0, p): all of them when k >= p, else one per stride of p // k at a seeded offset within it
+    (the same positions for the same p in every run)"""
+    if k >= p:
+        return np.arange(p, dtype=np.int64)
+    stride = p // k
+    rng = np.random.default_rng(seed)
+    return np.arange(k, dtype=np.int64) * stride + rng.integers(0, stride, k)
+
+
+def dump_outputs(w, out_dir, prefix="", limit=DUMP_LIMIT):
+    """--dump-outputs: what the workload's last step handed its caller — the last block's output windows (w.bufs[-1], one of
+    w.caps[-1] elements per channel, w.last_p of them produced) — as .npy files in out_dir:
+        output.npy            float32 [windows, k] (real output) or [windows, k, 2] (complex: re, im)
+        output_index.npy      float64 [k]: the positions of output.npy's k samples in every window
+        output_produced.npy   float64 [windows]: the elements produced per window
+    When the whole windows do not fit in `limit` bytes, a fixed seeded sample of positions (dump_positions) stands in for them.
+    -> the paths written"""
+    out_dt = np.dtype(w.blocks[-1].out_dtype)
+    if out_dt == np.complex64:
+        comp = 2
+    elif out_dt == np.float32:
+        comp = 1
+    else:
+        raise ValueError(f"--dump-outputs: no float32 form for output dtype {out_dt}")
+    p, cap, nwin = int(w.last_p), int(w.caps[-1]), int(w.n_windows)
+    k = min(p, (limit - 4096) // (nwin * comp * 4 + 8))
+    pos = dump_positions(p, k)
+    out = w.bufs[-1]
+    if out.is_cuda:
+        torch.cuda.synchronize(out.device)
+    idx = torch.from_numpy(pos).to(out.device)
+    vals = torch.stack([out[comp * c * cap:comp * (c * cap + p)].view(p, comp).index_select(0, idx) for c in range(nwin)])
+    vals = vals.float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    files = {"output": vals if comp == 2 else vals[..., 0], "output_index": pos.astype(np.float64),
+             "output_produced": np.full(nwin, p, dtype=np.float64)}
+    paths = []
+    for name, a in files.items():
+        path = os.path.join(out_dir, f"{prefix}{name}.npy")
+        np.save(path, a)
+        paths.append(path)
+    return paths
 
 
 # ---- CPU baseline (the oracle; test infrastructure used here as the reported baseline only) ----------------------
@@ -508,6 +576,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: fftfilter (configs[1]) on one GPU, fm_multi (configs[3]) on N > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the from-idle run, the roofline and per-step passes, the f64 "
+                         "check, the other workloads, the drop-in path, the CPU baseline, the N > 1 anchor and resident-source "
+                         "runs, and the detail file.  Without it a run prints the contract keys and `config` only; the --no-* "
+                         "options below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (float32, at most 64 MB: a fixed "
+                         "seeded sample of a larger output; see dump_outputs)")
     ap.add_argument("--no-others", action="store_true", help="skip the short runs of the other workloads")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-dropin", action="store_true", help="skip the host-window (drop-in path) measurements")
@@ -584,6 +660,8 @@ def main():
     stage("build workload")
     with rr.build_options(**opts):
         w = make_workload(wname, dev, rank, world, shared_src)
+        if args.settle_ms > 0:
+            w.settle_blocks = w.make_blocks()    # (run_timed: the settle phase leaves the timed handles' state alone)
     abi_check = {}
 
     def make_fan(wl):
@@ -679,7 +757,7 @@ def main():
     # different workload, configs[1]: value(N) / value(1) across those two lines would compare FftFilter samples with
     # channel-samples.)
     anchor = None
-    if world > 1:
+    if world > 1 and args.full:
         stage("N = 1 anchor on rank 0 (the other ranks wait at the barrier)")
         if rank == 0:
             ua, ta, _, _, _, sma = run_timed(w, args.steps, args.warmup, None, stream, None, None, settle_ms=args.settle_ms)
@@ -690,13 +768,32 @@ def main():
         dist.barrier()
     stage("fan-out set-up")
     fan = make_fan(w)
-    w.report_cold = True
+    w.report_cold = args.full
+    dump = None
+    if args.dump_outputs:
+        def dump():
+            dump_outputs(w, args.dump_outputs, prefix="" if world == 1 else f"rank{rank}_")
     stage("timed run (fan-out + compute)")
-    units, dt, kms, launches, dom_units, step_ms = run_timed(w, args.steps, args.warmup, dist, stream, fan, settle_ms=args.settle_ms)
+    units, dt, kms, launches, dom_units, step_ms = run_timed(w, args.steps, args.warmup, dist, stream, fan, settle_ms=args.settle_ms,
+                                                             extra_passes=args.full, after_timed=dump)
     settle_main = getattr(w, "settle_steps", 0)
 
     # max over ranks of the wall time, sum over ranks of the units
     units_all, dt = multi.aggregate(dist, units, dt, dev)
+    value = units_all / dt / 1e6
+    par = "1 GPU" if world == 1 else f"{world} ranks, channel-sharded; shared IQ source fanned out per tile inside the timed region"
+    head = {"metric": METRIC, "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": w.dtype, "data": "synthetic",
+            "config": {"workload": w.name[:118], "workload_key": wname, "samples_per_step_per_gpu": w.n, "parallelism": par[:118],
+                       "settle_steps": settle_main}}
+    if not args.full:
+        if rank == 0:
+            print(compact_line(_clean(head)), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     main_sum = summarize(w, units_all, dt, args.steps, kms, launches, dom_units, step_ms)
 
     # N > 1: the same step on every rank at once with the tile ALREADY on the rank (no fan-out) — what channel sharding
@@ -754,9 +851,7 @@ def main():
 
     rc = 0
     if rank == 0:
-        value = units_all / dt / 1e6
         roof, tnote = roofline_object(w, main_sum, wname)
-        par = "1 GPU" if world == 1 else f"{world} ranks, channel-sharded; shared IQ source fanned out per tile inside the timed region"
         cold = getattr(w, "cold_ms_per_step", None)
         parity_full = parity_report()
         checks = {k: v for k, v in verified.items() if v is not None}
@@ -846,15 +941,8 @@ def main():
         print("bench.py detail: " + dtext, file=sys.stderr, flush=True)
 
         # ---- the line: contract keys + config + roofline + cpu_baseline + compact companions, < 4 KB, strict JSON ----
-        line = {
-            "metric": METRIC, "value": detail["value"], "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": detail["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": w.dtype, "data": "synthetic",
-            "config": {"workload": w.name[:118], "workload_key": wname, "samples_per_step_per_gpu": w.n, "parallelism": par[:118],
-                       "settle_steps": settle_main},
-            "roofline": _clean(roof),
-            "ms_per_step_median": detail["ms_per_step_median"], "value_from_idle": detail["value_from_idle"],
-        }
+        line = dict(head, roofline=_clean(roof), ms_per_step_median=detail["ms_per_step_median"],
+                    value_from_idle=detail["value_from_idle"])
         if "cpu_baseline" in detail:
             cb = detail["cpu_baseline"]
             allc = cb["modes"].get("one_chain_per_core_all_cores", {})

@@ -58,7 +58,7 @@ CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 
 def test_single_gpu_line():
-    d, det = _run("--steps", "3", "--warmup", "1", "--no-cpu", "--no-others")
+    d, det = _run("--full", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-others")
     for k in CONTRACT:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
@@ -106,7 +106,7 @@ def test_default_line_carries_the_metric_chain_and_the_north_star_target():
     first-class objects of the driver's line (compact) and of the detail file (full), each with its GPU rate, its roofline
     fractions and its own single-thread CPU leg (the oracle chain on this host).  Every workload of the run is checked against
     f64 and none has a null roofline fraction."""
-    d, det = _run("--steps", "3", "--warmup", "1", "--cpu-seconds", "4", "--no-dropin")
+    d, det = _run("--full", "--steps", "3", "--warmup", "1", "--cpu-seconds", "4", "--no-dropin")
     for k in CONTRACT + ("cpu_baseline", "metric_chain", "north_star_target", "verified", "others_brief"):
         assert k in d, k
     cb = d["cpu_baseline"]
@@ -146,7 +146,7 @@ def test_default_line_carries_the_metric_chain_and_the_north_star_target():
 
 
 def test_two_rank_line():
-    d, det = _run("--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu")
+    d, det = _run("--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu")
     for k in CONTRACT:
         assert k in d, k
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and "configs[3]" in d["config"]["workload"]
@@ -183,3 +183,43 @@ def test_two_rank_line():
     assert pr["assumptions"]["xgmi_link_gbs"] == 153.0
     # the library's own fan-out (rr_fanout_*) is the measured one whenever every rank has a GPU
     assert c["fanout"] == ("abi" if c["backend"] == "rccl" else "torch")
+
+
+def _plain(*args):
+    """a run without --full, as it is timed for every change -> the ONE stdout line, parsed"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=600,
+                         cwd=ROOT, env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = out.stdout.strip().split("\n")
+    assert len([l for l in lines if l.startswith("{")]) == 1 and lines[-1].startswith("{"), out.stdout[-2000:]
+    return _strict(lines[-1])
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line holds the contract's figures and nothing that needs a run of its own; --dump-outputs writes
+    what the last timed step computed (a seeded sample of the 1e8-sample output, float32, at most 64 MB), the same in two
+    runs with the same arguments."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = _plain("--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path / f"run{i}"))
+        for k in CONTRACT:
+            if k != "roofline":
+                assert k in d, k
+        for k in ("roofline", "cpu_baseline", "verified", "others_brief", "detail", "value_from_idle", "ms_per_step_median"):
+            assert k not in d, k
+        assert d["steps"] == 4 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+        # value = input samples per second of the timed steps, ms_per_step = their wall time / steps
+        assert abs(d["value"] * 1e6 * d["ms_per_step"] * 1e-3 - 100_000_000) < 0.01 * 100_000_000
+        files = sorted(os.listdir(tmp_path / f"run{i}"))
+        assert files == ["output.npy", "output_index.npy", "output_produced.npy"], files
+        assert sum(os.path.getsize(tmp_path / f"run{i}" / f) for f in files) <= 64_000_000
+        dumps.append({f: np.load(tmp_path / f"run{i}" / f) for f in files})
+    a, b = dumps
+    y, pos, produced = a["output.npy"], a["output_index.npy"], a["output_produced.npy"]
+    assert y.dtype == np.float32 and pos.dtype == np.float64 and produced.dtype == np.float64
+    assert y.ndim == 3 and y.shape[0] == 1 and y.shape[1] == len(pos) > 1_000_000 and y.shape[2] == 2     # complex: re, im
+    assert produced[0] > 99_000_000 and np.all(np.diff(pos) > 0) and pos[-1] < produced[0]
+    assert np.all(np.isfinite(y)) and np.abs(y).max() > 0
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f

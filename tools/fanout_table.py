@@ -2,7 +2,7 @@
 """DESIGN.md §7's fan-out prediction table, regenerated from a bench.py line (its `multi_gpu_prediction` object, which
 bench.py computes from that run's MEASURED configs[3] step through multi.predict_fanout).
 
-    python bench.py > line.json ; python tools/fanout_table.py line.json        (or a BENCH_rNN.json of the driver)"""
+    python bench.py --full > line.json ; python tools/fanout_table.py line.json        (or a BENCH_rNN.json of the driver)"""
 import json
 import sys
 

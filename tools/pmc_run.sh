@@ -4,7 +4,7 @@
 # Each pass runs:  rocprofv3 --pmc <counters> -- python3 bench.py ...
 set -u
 OUT=${1:-gpurun_out/pmc}; shift || true
-ARGS=${@:---steps 3 --warmup 1 --no-others --no-cpu}
+ARGS=${@:---full --steps 3 --warmup 1 --no-others --no-cpu}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
 i=0

@@ -17,5 +17,6 @@ timeout 120 ./tools/micro/pcie_inplace.bin > gpurun_out/prof_$TAG/pcie_inplace.t
 python3 tools/chain_tile_probe.py 2>/dev/null | grep -v amdgpu > gpurun_out/prof_$TAG/rtl_fm_tiles.txt
 python3 tools/clock_probe.py channelizer > gpurun_out/prof_$TAG/clocks.txt 2>&1
 bash tools/ab_nonfinite_pass.sh 2>&1 | grep -v amdgpu > gpurun_out/prof_$TAG/ab_nonfinite_pass.txt
-python3 bench.py --detail-out "gpurun_out/prof_$TAG/bench_detail.json" > "gpurun_out/prof_$TAG/bench_default.json" 2> "gpurun_out/prof_$TAG/bench_default.log"
+P=$(ls -d */prof_"$TAG")          # this tag's profile directory, filled above
+python3 bench.py --full --detail-out "$P/bench_detail.json" > "$P/bench_default.json" 2> "$P/bench_default.log"
 tail -c 300 "gpurun_out/prof_$TAG/bench_default.log"; ls gpurun_out/prof_$TAG | head -60

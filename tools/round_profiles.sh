@@ -16,15 +16,15 @@ for pair in $PAIRS; do
   T=$OUT/traffic_$w; mkdir -p $T; i=0
   for c in FETCH_SIZE WRITE_SIZE; do
     i=$((i+1))
-    timeout 300 rocprofv3 --pmc $c --output-format csv -d "$T/pass$i" -o p -- python3 bench.py --workload $w --steps 3 --warmup 1 --no-others --no-cpu --no-dropin --no-verify > "$T/pass$i.log" 2>&1
+    timeout 300 rocprofv3 --pmc $c --output-format csv -d "$T/pass$i" -o p -- python3 bench.py --full --workload $w --steps 3 --warmup 1 --no-others --no-cpu --no-dropin --no-verify > "$T/pass$i.log" 2>&1
   done
   python3 tools/pmc_summary.py "$T" rr:: > "$OUT/${w}_traffic_pmc.txt"
   python3 tools/pmc_traffic.py "$OUT/${w}_traffic_pmc.txt" $w "$k"
   rm -rf $T
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$w" -o p -- python3 bench.py --workload $w --steps $K --warmup 3 --no-others --no-cpu --no-dropin --no-verify > "$OUT/bench_$w.json" 2> "$OUT/$w.log"
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$w" -o p -- python3 bench.py --full --workload $w --steps $K --warmup 3 --no-others --no-cpu --no-dropin --no-verify > "$OUT/bench_$w.json" 2> "$OUT/$w.log"
   f=$(ls $OUT/$w/*kernel_stats.csv 2>/dev/null | head -1); t=$(ls $OUT/$w/*kernel_trace.csv 2>/dev/null | head -1)
   alg=$(python3 -c "import json,sys; print(json.loads(open('$OUT/bench_$w.json').read().strip().splitlines()[-1])['roofline']['alg_bytes_per_launch'])" 2>/dev/null)
-  { echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py --workload $w --steps $K --warmup 3 --no-others --no-cpu --no-dropin --no-verify"; python3 tools/prof_summary.py "$f" 8; echo; python3 tools/prof_launches.py "$t" "$k" $K $alg; echo; echo "# bench line of the same run:"; tail -1 "$OUT/bench_$w.json"; } > "$OUT/${w}_kernel_stats.txt"
+  { echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --workload $w --steps $K --warmup 3 --no-others --no-cpu --no-dropin --no-verify"; python3 tools/prof_summary.py "$f" 8; echo; python3 tools/prof_launches.py "$t" "$k" $K $alg; echo; echo "# bench line of the same run:"; tail -1 "$OUT/bench_$w.json"; } > "$OUT/${w}_kernel_stats.txt"
   rm -rf "$OUT/$w"
   head -3 "$OUT/${w}_kernel_stats.txt" | tail -1
 done
