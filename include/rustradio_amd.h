@@ -97,9 +97,11 @@ typedef struct {
     int fft_log2f;          /* FftFilter: overlap-save tile of 2^n points, n = 10..14 */
     int fft_no_split;       /* tiles of 8192 / 16384 points as ONE workgroup instead of 2 / 4 sub-transforms */
     int fftfloat_complex;   /* FftFilterFloat: the reference's f32 -> Complex -> FftFilter -> .re inner path */
-    int fm_full;            /* fused FM chains: full-size inverse transforms for 1:even ratios too */
-    int fm_poly;            /* fused FM chains: decimate-first (polyphase) tiles, > 0 wherever supported, < 0 never;
-                               8 / 12: also fixes the multi-channel kernel's waves per workgroup (0 / 1: by predicted cost) */
+    int fm_full;            /* fused FM chains and rr_channelizer*_create: full-size inverse transforms for 1:even ratios too
+                               (and never the decimate-first tiles) */
+    int fm_poly;            /* fused FM chains and rr_channelizer*_create: decimate-first (polyphase) tiles, > 0 wherever
+                               supported, < 0 never; 8 / 12: also fixes the multi-channel kernel's waves per workgroup
+                               (0 / 1: by predicted cost) */
     int dstream_no_vmm;     /* rr_dstream_create: the copying fallback ring instead of the double mapping */
     int fir_poly;           /* decimating FirFilter<Complex>: decimate-first (polyphase) tiles, > 0 wherever supported, < 0 never */
     int fft_nonfinite_tiles;/* FftFilter / FftFilterFloat: 1 = leave a NaN / Inf input sample's damage on the GPU's tile instead of
@@ -254,7 +256,30 @@ rr_block *rr_fm_multi_create(const rr_c32 *taps, size_t nchan, size_t ntaps, siz
  * rr_fm_chain_u8_create (input windows, `consumed` and the WAIT_SRC `need` count BYTES). */
 rr_block *rr_fm_multi_u8_create(const rr_c32 *taps, size_t nchan, size_t ntaps, size_t interp, size_t deci,
                                 float gain, int atan2_mode);
-/* number of output windows of a block (1 except rr_fm_multi[_u8]_create) */
+/* Channelizer: `nchan` FftFilter -> RationalResampler pairs fed by ONE Complex input stream, with Complex (baseband)
+ * outputs — the reference's Tee fan-out (src/tee.rs:10-24) plus nchan x {FftFilter::new(_, taps_c)
+ * (src/fft_filter.rs:289-355), RationalResampler::new(_, interp, deci) (src/rational_resampler.rs:154-213)}, the front end
+ * of examples/rtl_downsampled.rs:37-52, rtl_data_stream.rs:188-205, burst_saver.rs:97-107 and ax25-9600-rx.rs:147-151.
+ * taps = [nchan][ntaps].  Whole-stream output of channel c equals the two blocks in sequence, including FftFilter's
+ * zero history at the start of the stream and the gcd reduction of interp:deci.  nchan 1 is the fused
+ * FftFilter -> RationalResampler block (one output window; rr_block_work_streams takes it).
+ * Output windows as rr_fm_multi_create: nchan consecutive windows of out_cap Complex elements, identical counts.
+ * Every tile's forward transform is shared by all channels (the kernels of rr_fm_multi_create with the samples stored
+ * instead of demodulated).
+ * work(): after filtered samples y, N2(y) = ceil(y interp / deci) resampled ones exist.  WAIT_DST(n) when the next filter
+ * block's n resampled samples do not fit, else consumes like FftFilter (whole pending blocks) and returns
+ * WAIT_SRC(nsamples - pending).  The output window must hold one filter block's worth, ceil(nsamples * interp / deci)
+ * (with the reference's 4,096,000-byte streams any ratio up to interp/deci ~ 30 at 16384-point blocks); a smaller one
+ * returns WAIT_DST(n) forever.  No tap-count or ratio limit: shapes beyond the fused kernels (more than 4094 taps off the
+ * decimate-first tiles, a decimation beyond a tile) run as one FftFilter -> RationalResampler pair of GPU blocks per
+ * channel behind the same handle.  NULL + rr_last_error for interp or deci 0 ("RationalResampler created using deci 0"),
+ * nchan 0 or above 4096, ntaps 0.  Tags: RR_TAGS_DROP (the resampler drops them, rational_resampler.rs:156).
+ * A NaN input sample makes exactly the reference's outputs NaN (the resampled samples of its poisoned FftFilter blocks). */
+rr_block *rr_channelizer_create(const rr_c32 *taps, size_t nchan, size_t ntaps, size_t interp, size_t deci);
+/* The same fed by the RTL-SDR byte stream: RtlSdrDecode (src/rtlsdr_decode.rs:9-47) fused in front of the Tee, as in
+ * rr_fm_multi_u8_create (input windows, `consumed` and the WAIT_SRC `need` count BYTES). */
+rr_block *rr_channelizer_u8_create(const rr_c32 *taps, size_t nchan, size_t ntaps, size_t interp, size_t deci);
+/* number of output windows of a block (1 except rr_fm_multi[_u8]_create and rr_channelizer[_u8]_create) */
 size_t rr_block_out_windows(const rr_block *b);
 
 void rr_block_destroy(rr_block *b);

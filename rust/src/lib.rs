@@ -63,6 +63,8 @@ unsafe extern "C" {
                              deci: usize, translate: c_int, samp_rate: f32, freq: f32) -> *mut RrBlock;
     fn rr_fm_multi_create(taps: *const Complex, nchan: usize, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_multi_u8_create(taps: *const Complex, nchan: usize, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
+    fn rr_channelizer_create(taps: *const Complex, nchan: usize, ntaps: usize, interp: usize, deci: usize) -> *mut RrBlock;
+    fn rr_channelizer_u8_create(taps: *const Complex, nchan: usize, ntaps: usize, interp: usize, deci: usize) -> *mut RrBlock;
     fn rr_fanout_unique_id(id128: *mut c_void) -> c_int;
     fn rr_fanout_create(id128: *const c_void, rank: c_int, world: c_int, src_rank: c_int, tile_bytes: usize, flags: c_int) -> *mut RrFanout;
     fn rr_fanout_destroy(f: *mut RrFanout);
@@ -654,6 +656,57 @@ impl Block for GpuFmMulti {
         for d in &self.dsts { outs.push(d.write_buf()?); }
         let cap = outs.iter_mut().map(|o| o.slice().len()).min().unwrap_or(0);
         self.scratch.resize(self.nchan * cap.max(1), 0.0);
+        let (mut c, mut p, mut need) = (0usize, 0usize, 0usize);
+        // SAFETY: scratch holds nchan windows of `cap` elements; input is a live window.
+        let st = unsafe {
+            rr_block_work(self.h.0, input.slice().as_ptr().cast(), input.slice().len(), self.scratch.as_mut_ptr().cast(), cap,
+                          &mut c, &mut p, &mut need)
+        };
+        if st == RR_ERR { return Err(last_error()); }
+        for (ch, mut o) in outs.into_iter().enumerate() {
+            o.slice()[..p].copy_from_slice(&self.scratch[ch * cap..ch * cap + p]);
+            o.produce(p, &[]);
+        }
+        input.consume(c);
+        Ok(if st == RR_WAIT_DST { BlockRet::WaitForStream(&self.dsts[0], need) } else { BlockRet::WaitForStream(&self.src, need) })
+    }
+}
+
+/// `Tee` + N x (FftFilter -> RationalResampler) on ONE input with Complex (baseband) outputs (rr_channelizer_create): what
+/// examples/rtl_downsampled.rs:37-52 wires per channel, every tile's forward transform shared by the channels.  N output
+/// streams, staged through `scratch` like GpuFmMulti (8 B per output sample).  The resampler drops tags
+/// (src/rational_resampler.rs:156), so none are forwarded.
+pub struct GpuChannelizer {
+    h: Handle,
+    nchan: usize,
+    src: ReadStream<Complex>,
+    dsts: Vec<WriteStream<Complex>>,
+    scratch: Vec<Complex>,
+}
+impl GpuChannelizer {
+    /// `taps[c]` = channel c's filter (all of one length).
+    pub fn new(src: ReadStream<Complex>, taps: &[Vec<Complex>], interp: usize, deci: usize)
+        -> Result<(Self, Vec<ReadStream<Complex>>)> {
+        let nchan = taps.len();
+        let ntaps = taps.first().map_or(0, Vec::len);
+        if taps.iter().any(|t| t.len() != ntaps) { return Err(Error::msg("GpuChannelizer: all channels need the same number of taps")); }
+        let flat: Vec<Complex> = taps.iter().flatten().copied().collect();
+        // SAFETY: flat is a live [nchan][ntaps] array.
+        let h = Handle::new(unsafe { rr_channelizer_create(flat.as_ptr(), nchan, ntaps, interp, deci) })?;
+        debug_assert_eq!(unsafe { rr_block_out_windows(h.0) }, nchan);
+        let (dsts, drs): (Vec<_>, Vec<_>) = (0..nchan).map(|_| new_stream()).unzip();
+        Ok((Self { h, nchan, src, dsts, scratch: Vec::new() }, drs))
+    }
+}
+impl BlockName for GpuChannelizer { fn block_name(&self) -> &str { "GpuChannelizer" } }
+impl BlockEOF for GpuChannelizer { fn eof(&mut self) -> bool { self.src.eof() } }
+impl Block for GpuChannelizer {
+    fn work(&mut self) -> Result<BlockRet<'_>> {
+        let (input, _tags) = self.src.read_buf()?;
+        let mut outs = Vec::with_capacity(self.nchan);
+        for d in &self.dsts { outs.push(d.write_buf()?); }
+        let cap = outs.iter_mut().map(|o| o.slice().len()).min().unwrap_or(0);
+        self.scratch.resize(self.nchan * cap.max(1), Complex::default());
         let (mut c, mut p, mut need) = (0usize, 0usize, 0usize);
         // SAFETY: scratch holds nchan windows of `cap` elements; input is a live window.
         let st = unsafe {

@@ -578,5 +578,26 @@ def FmMultiU8(taps_per_channel, interp: int, deci: int, gain: float = 1.0, mode:
     return Block(h, np.uint8, np.float32)
 
 
+def Channelizer(taps_per_channel, interp: int, deci: int) -> Block:
+    """Tee + N x (FftFilter(taps_c) -> RationalResampler(interp, deci)) fused, Complex (baseband) outputs;
+    taps_per_channel = [N][ntaps].  work() returns out with shape (N, produced); work_dev() takes N windows of
+    out_cap elements.  One channel is the fused FftFilter -> RationalResampler block."""
+    t = np.ascontiguousarray(taps_per_channel, np.complex64)
+    if t.ndim != 2:
+        raise ValueError("taps_per_channel must be [nchan][ntaps]")
+    h = lib().rr_channelizer_create(_ptr(t), t.shape[0], t.shape[1], interp, deci)
+    return Block(h, np.complex64, np.complex64)
+
+
+def ChannelizerU8(taps_per_channel, interp: int, deci: int) -> Block:
+    """RtlSdrDecode -> Channelizer fused: RTL-SDR bytes in, N Complex windows out (windows, consumed and the
+    WAIT_SRC need count bytes)."""
+    t = np.ascontiguousarray(taps_per_channel, np.complex64)
+    if t.ndim != 2:
+        raise ValueError("taps_per_channel must be [nchan][ntaps]")
+    h = lib().rr_channelizer_u8_create(_ptr(t), t.shape[0], t.shape[1], interp, deci)
+    return Block(h, np.uint8, np.complex64)
+
+
 def Hilbert(ntaps: int, wtype: int = WIN_HAMMING, parm: float = 0.0) -> Block:
     return Block(lib().rr_hilbert_create(ntaps, wtype, parm), np.float32, np.complex64)

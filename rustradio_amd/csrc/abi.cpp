@@ -221,6 +221,12 @@ rr_block* rr_fm_multi_u8_create(const rr_c32* taps, size_t nchan, size_t ntaps, 
                                 int atan2_mode) {
     return make_block([&] { return rr::make_fm_multi(taps, nchan, ntaps, interp, deci, gain, atan2_mode, true); });
 }
+rr_block* rr_channelizer_create(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci) {
+    return make_block([&] { return rr::make_channelizer(taps, nchan, ntaps, interp, deci, false); });
+}
+rr_block* rr_channelizer_u8_create(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci) {
+    return make_block([&] { return rr::make_channelizer(taps, nchan, ntaps, interp, deci, true); });
+}
 size_t rr_block_out_windows(const rr_block* b) { return b ? b->b->out_windows() : 0; }
 void rr_block_destroy(rr_block* b) { try { delete b; } catch (...) {} }
 

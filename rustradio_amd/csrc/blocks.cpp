@@ -1588,9 +1588,10 @@ int AudioChain::work_blocks(const void* in, size_t in_len, float* out, size_t, s
 }
 
 // ---- N FM chains on one shared source ---------------------------------------------------------------------
-FmMulti::FmMulti(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci, float g, int m, bool u8)
-    : Block(u8 ? "RtlSdrDecode>Tee>N x (FftFilter>RationalResampler>QuadratureDemod)" : "Tee>N x (FftFilter>RationalResampler>QuadratureDemod)",
-            u8 ? 1 : 8, 4), C(nchan), iq8(u8) {
+FmMulti::FmMulti(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci, float g, int m, bool u8, bool cx)
+    : Block(cx ? (u8 ? "RtlSdrDecode>Tee>N x (FftFilter>RationalResampler)" : "Tee>N x (FftFilter>RationalResampler)")
+            : u8 ? "RtlSdrDecode>Tee>N x (FftFilter>RationalResampler>QuadratureDemod)" : "Tee>N x (FftFilter>RationalResampler>QuadratureDemod)",
+            u8 ? 1 : 8, cx ? 8 : 4), C(nchan), cplx(cx), iq8(u8) {
     if (nchan == 0 || nchan > 4096) throw Error("FmMulti: channel count must be 1..4096");
     zero_copy_in = false;                            // (its kernels read a tile once per run of channel rounds: upload it)
     if (deci == 0) throw Error("RationalResampler created using deci 0");
@@ -1602,12 +1603,15 @@ FmMulti::FmMulti(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, 
     const int64_t gg0 = gcd64((int64_t)std::min<size_t>(deci, (size_t)1 << 31), (int64_t)std::min<size_t>(interp, (size_t)1 << 31));
     const bool want_poly = build_opts().fm_poly >= 0 && !build_opts().fm_full && interp <= ((size_t)1 << 31) && deci <= ((size_t)1 << 31) &&
                            (int64_t)interp / gg0 == 1 && ntaps <= 16383 &&
-                           fm_poly_supported(1, (long)((int64_t)deci / gg0), (int)ntaps, true);
+                           fm_poly_supported(1, (long)((int64_t)deci / gg0), (int)ntaps, true) &&
+                           // (the channelizer: decimations up to 8 at up to 768 taps per phase — one phase per wave)
+                           (!cx || ((int64_t)deci / gg0 <= 8 && (ntaps + (size_t)((int64_t)deci / gg0) - 1) / (size_t)((int64_t)deci / gg0) <= 768));
     // Everything else is the shared-forward kernels on tiles of at most 4096 points, which yield 4097 - ntaps filtered samples
     // each: towards 4094 taps a tile is all overlap (tools/multi_taps_probe.py, 32 channels 1:6 without decimate-first
     // tiles, ms per 2.4e6 samples: 3000 taps 0.55, 3800 taps 1.80) while one fused chain per channel on 8192-point split tiles
     // (compose.cpp Parallel) costs 0.83 ms at 5000 taps and less below.  The crossover is where a tile still yields ~768 samples.
-    if (!want_poly && ntaps > 4097 - 768)
+    // (the channelizer's alternative is the UNFUSED pair per channel: its shared-forward tiles go to 4094 taps)
+    if (!want_poly && ntaps > 4097 - 768 && !cx)
         throw NotFusedShape("FmMulti: beyond 3329 taps one fused chain per channel on larger tiles is cheaper");
     chain.reset(new FmChain(taps, ntaps, interp, deci, g, m, false, want_poly ? 14 : 12));   // bookkeeping, carry state; tile-agnostic
     if (want_poly) {
@@ -1664,12 +1668,13 @@ int FmMulti::work_blocks(const void* in, size_t in_len, float* out, size_t out_s
     const uint64_t S = f->nsamples;
     const int64_t I = ch.I, D = ch.D;
     auto N2 = [&](uint64_t y) { return (uint64_t)(((__int128)y * I + D - 1) / D); };
-    auto N3 = [&](uint64_t y) { const uint64_t r = N2(y); return r ? r - 1 : 0; };
+    const uint64_t lag = cplx ? 0 : 1;             // the demodulator's one-sample lag (none for the channelizer's Complex outputs)
+    auto N3 = [&](uint64_t y) { const uint64_t r = N2(y); return r > lag ? r - lag : 0; };
     const uint64_t n1 = ch.n1, o_old = N3(n1);
     const uint64_t need_next = N3(n1 + S) - o_old;
     if (need_next > out_cap) { *need = need_next; return RR_WAIT_DST; }
     const uint64_t total = f->pend_len + in_len, k_in = total / S;
-    const __int128 X = (__int128)(o_old + out_cap + 1) * D / I;
+    const __int128 X = (__int128)(o_old + out_cap + lag) * D / I;
     uint64_t k_out = X >= (__int128)n1 ? (uint64_t)((X - n1) / S) : 0;
     while (k_out > 0 && N3(n1 + k_out * S) - o_old > out_cap) k_out--;
     k_out = std::min(k_out, max_blocks);
@@ -1692,7 +1697,17 @@ int FmMulti::work_blocks(const void* in, size_t in_len, float* out, size_t out_s
         if (*consumed) a.carry = CarryOut{f->prefix[f->cur ^ 1].p, (long)n_y, (long)(f->hist + new_pend)};
         a.multi_waves = poly_waves;
         prof_begin(s);
-        if (poly && packed)
+        cf* oc = reinterpret_cast<cf*>(out);
+        if (cplx) {
+            if (poly && packed) launch_chan_poly_iq8(src8, oc, (long)out_stride, (int)f->L, poly->d_tw.p, poly->d_h.p, (int)C, a, s);
+            else if (poly) launch_chan_poly(src, oc, (long)out_stride, (int)f->L, poly->d_tw.p, poly->d_h.p, (int)C, a, s);
+            else if (half_ok && packed)
+                launch_chan_multi_half_iq8(f->log2f, src8, oc, (long)out_stride, (int)f->L, f->d_tw.p, d_tw_half.p, d_hpos_all.p, (int)C, a, s);
+            else if (packed) launch_chan_multi_iq8(f->log2f, src8, oc, (long)out_stride, (int)f->L, f->d_tw.p, d_hpos_all.p, (int)C, a, s);
+            else if (half_ok)
+                launch_chan_multi_half(f->log2f, src, oc, (long)out_stride, (int)f->L, f->d_tw.p, d_tw_half.p, d_hpos_all.p, (int)C, a, s);
+            else launch_chan_multi(f->log2f, src, oc, (long)out_stride, (int)f->L, f->d_tw.p, d_hpos_all.p, (int)C, a, s);
+        } else if (poly && packed)
             launch_fm_multi_poly_iq8(src8, out, (long)out_stride, (int)f->L, poly->d_tw.p, poly->d_h.p, (int)C, a,
                                      last_r[cur_lr].p, last_r[cur_lr ^ 1].p, s);
         else if (poly)
@@ -1715,8 +1730,12 @@ int FmMulti::work_blocks(const void* in, size_t in_len, float* out, size_t out_s
             const uint64_t Lsd = (f->L + (uint64_t)D - 1) / (uint64_t)D;
             const long P_os = (long)((size_t)1 << f->log2f) - (long)f->L + 1;
             const long P = poly ? (long)(1024 - Lsd) : chain_probe_stride(P_os, I, D);
-            launch_chain_blocks_nonfinite(src, out, (long)out_stride, (int)C, a, (long)S, (long)f->hist, P, (int)f->L, 0, nf.rev_c.p,
-                                          (long)f->L, last_r[cur_lr].p, last_r[cur_lr ^ 1].p, nf.slots.p, nf.seq, 0, s);
+            if (cplx)
+                launch_chan_blocks_nonfinite(src, oc, (long)out_stride, (int)C, a, (long)S, (long)f->hist, P, (int)f->L, nf.rev_c.p,
+                                             (long)f->L, nf.slots.p, nf.seq, s);
+            else
+                launch_chain_blocks_nonfinite(src, out, (long)out_stride, (int)C, a, (long)S, (long)f->hist, P, (int)f->L, 0, nf.rev_c.p,
+                                              (long)f->L, last_r[cur_lr].p, last_r[cur_lr ^ 1].p, nf.slots.p, nf.seq, 0, s);
             nf.seq++;
         }
         if (a.r_hi > a.r_lo) cur_lr ^= 1;

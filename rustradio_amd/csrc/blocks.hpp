@@ -400,8 +400,12 @@ struct AudioChain : Block {
 
 // N fused FM chains (FmChain) on ONE shared input: the reference's Tee fan-out + N x three blocks.
 // The forward FFT of every tile is computed once for all channels.  Output = N windows.
+// cplx (the channelizer, rr_channelizer_create): N x {FftFilter, RationalResampler} with Complex outputs — the same kernels
+// storing the resampled samples instead of demodulating them, FmChain's bookkeeping without the demodulator's one-sample
+// lag, and no tail: a window too small for the next block's outputs gets WAIT_DST(that count).
 struct FmMulti : Block {
     size_t C;
+    bool cplx = false;
     std::unique_ptr<FmChain> chain;   // channel 0's chain object: shared bookkeeping + input carry state
     DevBuf<cf> d_hpos_all;            // [C][F]
     DevBuf<cf> d_tw_half;             // w_(F/2)^k: half-size inverse transforms (interp 1, even deci; k_fm_multi_half)
@@ -415,11 +419,13 @@ struct FmMulti : Block {
     DevBuf<cf> decoded;               // odd-addressed byte windows are decoded out of line
     OutTail tail;                     // [C] windows of one block's outputs
     ChainNf nf;                       // (its own: every channel's taps; `chain->nf` stays off)
-    FmMulti(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci, float gain, int mode, bool iq8 = false);
+    FmMulti(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci, float gain, int mode, bool iq8 = false,
+            bool cplx = false);
     size_t out_windows() const override { return C; }
     size_t next_block_outputs() const { return chain->next_block_outputs(); }
     int work_blocks(const void*, size_t, float*, size_t, size_t, size_t*, size_t*, size_t*, hipStream_t, uint64_t max_blocks);
     int work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* c, size_t* p, size_t* need, hipStream_t s) override {
+        if (cplx) return work_blocks(in, in_len, static_cast<float*>(out), out_cap, out_cap, c, p, need, s, ~(uint64_t)0);
         return trickle_work(*this, tail, C, in, in_len, out, out_cap, c, p, need, s);
     }
     bool eof(bool src_eof) override { return src_eof && !tail.pending(); }
@@ -517,6 +523,8 @@ Block* make_fm_chain(const rr_c32* taps, size_t ntaps, size_t interp, size_t dec
                      const rr_c32* fir_taps, size_t fir_ntaps);
 Block* make_fm_multi(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci, float gain, int mode, bool u8);
 Block* make_audio_chain(const float* taps, size_t ntaps, size_t interp, size_t deci, float scale);
+// rr_channelizer*_create: FmMulti(cplx) where its kernels reach, else N x Series(FftFilter, RationalResampler) in a Parallel
+Block* make_channelizer(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci, bool u8);
 
 struct Hilbert : Block {
     FirPlan pl;

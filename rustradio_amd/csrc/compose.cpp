@@ -226,6 +226,32 @@ Block* make_fm_multi(const rr_c32* taps, size_t nchan, size_t ntaps, size_t inte
     return new Parallel(u8 ? "RtlSdrDecode>Tee>N x chain (per channel)" : "Tee>N x chain (per channel)", std::move(ch));
 }
 
+Block* make_channelizer(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci, bool u8) {
+    if (deci == 0) throw Error("RationalResampler created using deci 0");
+    if (interp == 0) throw Error("RationalResampler created using interp 0");
+    if (nchan == 0 || nchan > 4096) throw Error("Channelizer: channel count must be 1..4096");
+    if (ntaps == 0) throw Error("Channelizer: empty taps");
+    try {
+        return new FmMulti(taps, nchan, ntaps, interp, deci, 1.0f, RR_ATAN2_EXACT, u8, true);
+    } catch (const NotFusedShape&) {
+    }
+    // beyond the shared-forward-transform kernels (more than 4094 taps off the decimate-first tiles, a decimation beyond a
+    // tile, ...): the two GPU blocks per channel on the shared window
+    std::vector<std::unique_ptr<Block>> ch;
+    for (size_t c = 0; c < nchan; c++) {
+        std::vector<std::unique_ptr<Block>> v;
+        if (u8) v.emplace_back(new RtlSdrDecode());
+        auto* f = new FftFilter(taps + c * ntaps, ntaps);
+        v.emplace_back(f);
+        f->ref_blocks_on(taps + c * ntaps);
+        v.emplace_back(new Resampler(interp, deci, sizeof(cf)));
+        ch.emplace_back(new Series(u8 ? "RtlSdrDecode>FftFilter>RationalResampler (unfused)" : "FftFilter>RationalResampler (unfused)",
+                                   std::move(v)));
+    }
+    return new Parallel(u8 ? "RtlSdrDecode>Tee>N x (FftFilter>RationalResampler) (per channel)"
+                           : "Tee>N x (FftFilter>RationalResampler) (per channel)", std::move(ch));
+}
+
 Block* make_audio_chain(const float* taps, size_t ntaps, size_t interp, size_t deci, float scale) {
     try {
         return new AudioChain(taps, ntaps, interp, deci, scale);

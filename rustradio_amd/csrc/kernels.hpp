@@ -147,6 +147,22 @@ void launch_fm_multi_poly(VSrc<cf> src, float* out, long out_stride, int L, cons
 void launch_fm_multi_poly_iq8(VSrcIQ8 src, float* out, long out_stride, int L, const cf* tw, const cf* hreg, int nchan,
                               const FmChainArgs& a, const cf* last_in, cf* last_out, hipStream_t s);
 
+// ---- the channelizer (rr_channelizer_create): the multi-channel kernels above with the resampled samples STORED ----------
+// Complex out: channel c writes out[c out_stride + u - r_lo] = r[u] for u in [r_lo, r_hi) (a.o_base = a.r_lo); no
+// demodulator, no carried r.  Tables and shapes as launch_fm_multi / launch_fm_multi_half / launch_fm_multi_poly.
+void launch_chan_multi(int log2f, VSrc<cf> src, cf* out, long out_stride, int L, const cf* tw, const cf* hpos_all, int nchan,
+                       const FmChainArgs& a, hipStream_t s);
+void launch_chan_multi_iq8(int log2f, VSrcIQ8 src, cf* out, long out_stride, int L, const cf* tw, const cf* hpos_all, int nchan,
+                           const FmChainArgs& a, hipStream_t s);
+void launch_chan_multi_half(int log2f, VSrc<cf> src, cf* out, long out_stride, int L, const cf* tw, const cf* tw_half,
+                            const cf* hpos_all, int nchan, const FmChainArgs& a, hipStream_t s);
+void launch_chan_multi_half_iq8(int log2f, VSrcIQ8 src, cf* out, long out_stride, int L, const cf* tw, const cf* tw_half,
+                                const cf* hpos_all, int nchan, const FmChainArgs& a, hipStream_t s);
+void launch_chan_poly(VSrc<cf> src, cf* out, long out_stride, int L, const cf* tw, const cf* hreg, int nchan, const FmChainArgs& a,
+                      hipStream_t s);
+void launch_chan_poly_iq8(VSrcIQ8 src, cf* out, long out_stride, int L, const cf* tw, const cf* hreg, int nchan, const FmChainArgs& a,
+                          hipStream_t s);
+
 // ---- kernels_fir.hip ---------------------------------------------------------------
 struct FirPlan {             // host-prepared polyphase tap table
     int L = 0, d = 1;
@@ -207,6 +223,9 @@ void launch_chain_blocks_nonfinite(VSrc<cf> src, float* out, long out_stride, in
                                    hipStream_t s);
 void launch_chain_blocks_nonfinite(VSrc<float> src, float* out, const AudioChainArgs& a, long S, long hist, long P, int L,
                                    const float* rev, int* slots, int seq, hipStream_t s);
+// ... and the channelizer's Complex outputs (out[u - r_lo] = r[u] per channel)
+void launch_chan_blocks_nonfinite(VSrc<cf> src, cf* out, long out_stride, int nchan, const FmChainArgs& a, long S, long hist, long P,
+                                  int L, const cf* rev, long rev_stride, int* slots, int seq, hipStream_t s);
 // a CarryOut as its own launch (calls without a main kernel; launchers with nothing to launch)
 void launch_carry(VSrc<cf> src, const CarryOut& c, hipStream_t s);
 void launch_carry(VSrcIQ8 src, const CarryOut& c, hipStream_t s);

@@ -1456,11 +1456,12 @@ void k_fm_chain(SRC src, float* __restrict__ out, int L, long ntiles, const cf* 
 // FFT of a tile is computed once, parked in LDS, and each channel only pays H_c * X, the inverse
 // FFT and the resample/demod epilogue.  On-GPU fan-out is free: the input tile is read from HBM
 // once per workgroup, not once per channel.
-template <int LOG2F, class SRC>
-__global__ __launch_bounds__((1 << (LOG2F - 4)), 2)
-void k_fm_multi(SRC src, float* __restrict__ out, long out_stride, int L, long ntiles,
-                const cf* __restrict__ tw, const cf* __restrict__ hpos_all, int nchan, FmArgs a,
-                const cf* __restrict__ last_r_in, cf* __restrict__ last_r_out) {
+// CX (the channelizer, rr_channelizer_create): the resampled samples are stored, Complex, oc[u - r_lo] = r[u] — no
+// demodulator, no carried r; the FM kernel is the CX = false instance (k_fm_multi below).
+template <int LOG2F, class SRC, bool CX>
+__device__ __forceinline__ void multi_body(SRC src, float* __restrict__ out, long out_stride, int L, long ntiles,
+                                           const cf* __restrict__ tw, const cf* __restrict__ hpos_all, int nchan, FmArgs a,
+                                           const cf* __restrict__ last_r_in, cf* __restrict__ last_r_out) {
     carry_store<cf>(src, a.carry);
     constexpr int F = 1 << LOG2F;
     constexpr int T = F / 16;
@@ -1506,6 +1507,14 @@ void k_fm_multi(SRC src, float* __restrict__ out, long out_stride, int L, long n
             X.inverse(w, lds);
             lds_store<LOG2F, 0>(w, t, lds);
             tile_sync<T>();
+            if constexpr (CX) {
+                cf* oc = reinterpret_cast<cf*>(out) + (long)c * out_stride;
+                SrcWalk wu = wu0;
+                for (long u = u_lo + t; u < u_hi; u += T, wu.step(qs, rs, a.I))
+                    oc[u - a.r_lo] = from_reg(lds[lds_pad((int)(wu.q - a.A - ys) + first)]);
+                tile_sync<T>();
+                continue;
+            }
             float* oc = out + (long)c * out_stride;
             SrcWalk wu = wu0, wl = wl0;
             for (long u = u_lo + t; u < u_hi; u += T, wu.step(qs, rs, a.I), wl.step(qs, rs, a.I)) {
@@ -1527,6 +1536,19 @@ void k_fm_multi(SRC src, float* __restrict__ out, long out_stride, int L, long n
         }
     }
 }
+template <int LOG2F, class SRC>
+__global__ __launch_bounds__((1 << (LOG2F - 4)), 2)
+void k_fm_multi(SRC src, float* __restrict__ out, long out_stride, int L, long ntiles,
+                const cf* __restrict__ tw, const cf* __restrict__ hpos_all, int nchan, FmArgs a,
+                const cf* __restrict__ last_r_in, cf* __restrict__ last_r_out) {
+    multi_body<LOG2F, SRC, false>(src, out, out_stride, L, ntiles, tw, hpos_all, nchan, a, last_r_in, last_r_out);
+}
+template <int LOG2F, class SRC>
+__global__ __launch_bounds__((1 << (LOG2F - 4)), 2)
+void k_chan_multi(SRC src, cf* __restrict__ out, long out_stride, int L, long ntiles,
+                  const cf* __restrict__ tw, const cf* __restrict__ hpos_all, int nchan, FmArgs a) {
+    multi_body<LOG2F, SRC, true>(src, reinterpret_cast<float*>(out), out_stride, L, ntiles, tw, hpos_all, nchan, a, nullptr, nullptr);
+}
 
 // ---- the same for an even integer decimation (interp 1): half-size inverse transforms ------------------------
 // The resampler then keeps only samples y[u D] (rational_resampler.rs:183-198 with interp 1), all of one parity, so
@@ -1537,11 +1559,11 @@ void k_fm_multi(SRC src, float* __restrict__ out, long out_stride, int L, long n
 // inverse is an F/2-point transform.  For F = 2048 that is a 1024-point tile of ONE wave: each of the two waves of
 // the workgroup takes every other channel and runs product, fold, inverse and the resample / demod epilogue without
 // a single barrier (the full-size version needs four per channel), on half the arithmetic.
-template <int LOG2F, class SRC>
-__global__ __launch_bounds__((1 << (LOG2F - 4)), 2)
-void k_fm_multi_half(SRC src, float* __restrict__ out, long out_stride, int L, long ntiles, long Sp,
-                     const cf* __restrict__ tw, const cf* __restrict__ tw_half, const cf* __restrict__ hpos_all,
-                     int nchan, FmArgs a, const cf* __restrict__ last_r_in, cf* __restrict__ last_r_out) {
+// (CX: the channelizer's Complex store, as multi_body)
+template <int LOG2F, class SRC, bool CX>
+__device__ __forceinline__ void multi_half_body(SRC src, float* __restrict__ out, long out_stride, int L, long ntiles, long Sp,
+                                                const cf* __restrict__ tw, const cf* __restrict__ tw_half, const cf* __restrict__ hpos_all,
+                                                int nchan, FmArgs a, const cf* __restrict__ last_r_in, cf* __restrict__ last_r_out) {
     carry_store<cf>(src, a.carry);
     constexpr int F = 1 << LOG2F, T = F / 16, LH = LOG2F - 1, FH = F / 2, TH = T / 2;
     constexpr int NP = Plan<LOG2F>::NP;
@@ -1637,6 +1659,13 @@ void k_fm_multi_half(SRC src, float* __restrict__ out, long out_stride, int L, l
             }
             lds_store<LH, 0>(w, th, ldsH);               // natural order: ldsH[pad(n')] = y[2 n'] of the tile
             asm volatile("" ::: "memory");
+            if constexpr (CX) {
+                cf* oc = reinterpret_cast<cf*>(out) + (long)c * out_stride;
+                for (long u = u_lo + th; u < u_hi; u += TH)
+                    oc[u - a.r_lo] = from_reg(ldsH[lds_pad((int)((u * a.D - a.A - ys + first) >> 1))]);
+                asm volatile("" ::: "memory");
+                continue;
+            }
             float* oc = out + (long)c * out_stride;
             for (long u = u_lo + th; u < u_hi; u += TH) {
                 const int p2 = (int)((u * a.D - a.A - ys + first) >> 1);      // half the (even) tile position
@@ -1657,6 +1686,20 @@ void k_fm_multi_half(SRC src, float* __restrict__ out, long out_stride, int L, l
         }
         tile_sync<T>();                                  // both waves done before the next forward reuses the areas
     }
+}
+template <int LOG2F, class SRC>
+__global__ __launch_bounds__((1 << (LOG2F - 4)), 2)
+void k_fm_multi_half(SRC src, float* __restrict__ out, long out_stride, int L, long ntiles, long Sp,
+                     const cf* __restrict__ tw, const cf* __restrict__ tw_half, const cf* __restrict__ hpos_all,
+                     int nchan, FmArgs a, const cf* __restrict__ last_r_in, cf* __restrict__ last_r_out) {
+    multi_half_body<LOG2F, SRC, false>(src, out, out_stride, L, ntiles, Sp, tw, tw_half, hpos_all, nchan, a, last_r_in, last_r_out);
+}
+template <int LOG2F, class SRC>
+__global__ __launch_bounds__((1 << (LOG2F - 4)), 2)
+void k_chan_multi_half(SRC src, cf* __restrict__ out, long out_stride, int L, long ntiles, long Sp,
+                       const cf* __restrict__ tw, const cf* __restrict__ tw_half, const cf* __restrict__ hpos_all, int nchan, FmArgs a) {
+    multi_half_body<LOG2F, SRC, true>(src, reinterpret_cast<float*>(out), out_stride, L, ntiles, Sp, tw, tw_half, hpos_all, nchan, a,
+                                      nullptr, nullptr);
 }
 
 // ---- the single fused chain with the half-size inverse (interp 1, even decimation, 2048-point tiles) ----------
@@ -2321,7 +2364,7 @@ void launch_fm_chain_split_iq8(int nsub, VSrcIQ8 src, float* out, int L, const c
     else launch_fm_split_one<4>(src, out, L, tw4096, hs, wk, h, last_in, last_out, s);
 }
 
-template <int LOG2F, class SRC>
+template <int LOG2F, class SRC, bool CX = false>
 static void launch_fm_multi_one(SRC src, float* out, long out_stride, int L, const cf* tw, const cf* hpos_all,
                                 int nchan, const FmChainArgs& h, const cf* last_in, cf* last_out, hipStream_t s) {
     constexpr int F = 1 << LOG2F;
@@ -2334,9 +2377,15 @@ static void launch_fm_multi_one(SRC src, float* out, long out_stride, int L, con
     const long ntiles = (h.n_y + Sp - 1) / Sp;
     if (ntiles <= 0) { launch_carry(src, h.carry, s); return; }
     const size_t smem = 2 * sizeof(cf) * lds_elems(F);
-    const long grid = grid_for_tiles(k_fm_multi<LOG2F, SRC>, T, smem, ntiles);
-    hipLaunchKernelGGL((k_fm_multi<LOG2F, SRC>), dim3((unsigned)grid), dim3(T), smem, s, src, out, out_stride, L, ntiles,
-                       tw, hpos_all, nchan, a, last_in, last_out);
+    if constexpr (CX) {
+        const long grid = grid_for_tiles(k_chan_multi<LOG2F, SRC>, T, smem, ntiles);
+        hipLaunchKernelGGL((k_chan_multi<LOG2F, SRC>), dim3((unsigned)grid), dim3(T), smem, s, src, reinterpret_cast<cf*>(out), out_stride,
+                           L, ntiles, tw, hpos_all, nchan, a);
+    } else {
+        const long grid = grid_for_tiles(k_fm_multi<LOG2F, SRC>, T, smem, ntiles);
+        hipLaunchKernelGGL((k_fm_multi<LOG2F, SRC>), dim3((unsigned)grid), dim3(T), smem, s, src, out, out_stride, L, ntiles,
+                           tw, hpos_all, nchan, a, last_in, last_out);
+    }
     RR_HIP(hipGetLastError());
 }
 
@@ -2344,7 +2393,7 @@ bool fm_multi_half_supported(int log2f, long I, long D, int L) {
     if (log2f != 11 || I != 1 || D < 2 || (D & 1)) return false;
     return (((1L << log2f) - L + 1) - D - 1) / 2 > 0;
 }
-template <class SRC>
+template <class SRC, bool CX = false>
 static void launch_fm_multi_half_t(int log2f, SRC src, float* out, long out_stride, int L, const cf* tw, const cf* tw_half,
                                    const cf* hpos_all, int nchan, const FmChainArgs& h, const cf* last_in, cf* last_out, hipStream_t s) {
     constexpr int LOG2F = 11, F = 1 << LOG2F, T = F / 16;
@@ -2357,9 +2406,15 @@ static void launch_fm_multi_half_t(int log2f, SRC src, float* out, long out_stri
     const long ntiles = (h.n_y + Sp - 1) / Sp;
     if (ntiles <= 0) { launch_carry(src, h.carry, s); return; }
     const size_t smem = sizeof(cf) * (2 * lds_elems(F) + 64);
-    const long grid = grid_for_tiles(k_fm_multi_half<LOG2F, SRC>, T, smem, ntiles);
-    hipLaunchKernelGGL((k_fm_multi_half<LOG2F, SRC>), dim3((unsigned)grid), dim3(T), smem, s, src, out, out_stride, L, ntiles, Sp,
-                       tw, tw_half, hpos_all, nchan, a, last_in, last_out);
+    if constexpr (CX) {
+        const long grid = grid_for_tiles(k_chan_multi_half<LOG2F, SRC>, T, smem, ntiles);
+        hipLaunchKernelGGL((k_chan_multi_half<LOG2F, SRC>), dim3((unsigned)grid), dim3(T), smem, s, src, reinterpret_cast<cf*>(out),
+                           out_stride, L, ntiles, Sp, tw, tw_half, hpos_all, nchan, a);
+    } else {
+        const long grid = grid_for_tiles(k_fm_multi_half<LOG2F, SRC>, T, smem, ntiles);
+        hipLaunchKernelGGL((k_fm_multi_half<LOG2F, SRC>), dim3((unsigned)grid), dim3(T), smem, s, src, out, out_stride, L, ntiles, Sp,
+                           tw, tw_half, hpos_all, nchan, a, last_in, last_out);
+    }
     RR_HIP(hipGetLastError());
 }
 void launch_fm_multi_half(int log2f, VSrc<cf> src, float* out, long out_stride, int L, const cf* tw, const cf* tw_half,
@@ -2416,13 +2471,13 @@ void launch_fftfilt_half(VSrc<cf> src, cf* out, long n_out, int L, int d, const 
 
 bool fm_multi_supported(int log2f) { return log2f >= 10 && log2f <= 12; }
 
-template <class SRC>
+template <class SRC, bool CX = false>
 static void launch_fm_multi_t(int log2f, SRC src, float* out, long out_stride, int L, const cf* tw, const cf* hpos_all,
                               int nchan, const FmChainArgs& h, const cf* last_in, cf* last_out, hipStream_t s) {
     switch (log2f) {
-    case 10: launch_fm_multi_one<10>(src, out, out_stride, L, tw, hpos_all, nchan, h, last_in, last_out, s); break;
-    case 11: launch_fm_multi_one<11>(src, out, out_stride, L, tw, hpos_all, nchan, h, last_in, last_out, s); break;
-    case 12: launch_fm_multi_one<12>(src, out, out_stride, L, tw, hpos_all, nchan, h, last_in, last_out, s); break;
+    case 10: launch_fm_multi_one<10, SRC, CX>(src, out, out_stride, L, tw, hpos_all, nchan, h, last_in, last_out, s); break;
+    case 11: launch_fm_multi_one<11, SRC, CX>(src, out, out_stride, L, tw, hpos_all, nchan, h, last_in, last_out, s); break;
+    case 12: launch_fm_multi_one<12, SRC, CX>(src, out, out_stride, L, tw, hpos_all, nchan, h, last_in, last_out, s); break;
     default: throw Error("fm_multi: unsupported tile size");
     }
 }
@@ -2433,6 +2488,26 @@ void launch_fm_multi(int log2f, VSrc<cf> src, float* out, long out_stride, int L
 void launch_fm_multi_iq8(int log2f, VSrcIQ8 src, float* out, long out_stride, int L, const cf* tw, const cf* hpos_all,
                          int nchan, const FmChainArgs& h, const cf* last_in, cf* last_out, hipStream_t s) {
     launch_fm_multi_t(log2f, src, out, out_stride, L, tw, hpos_all, nchan, h, last_in, last_out, s);
+}
+
+// the channelizer (Complex store, a.o_base = a.r_lo)
+void launch_chan_multi(int log2f, VSrc<cf> src, cf* out, long out_stride, int L, const cf* tw, const cf* hpos_all, int nchan,
+                       const FmChainArgs& h, hipStream_t s) {
+    launch_fm_multi_t<VSrc<cf>, true>(log2f, src, reinterpret_cast<float*>(out), out_stride, L, tw, hpos_all, nchan, h, nullptr, nullptr, s);
+}
+void launch_chan_multi_iq8(int log2f, VSrcIQ8 src, cf* out, long out_stride, int L, const cf* tw, const cf* hpos_all, int nchan,
+                           const FmChainArgs& h, hipStream_t s) {
+    launch_fm_multi_t<VSrcIQ8, true>(log2f, src, reinterpret_cast<float*>(out), out_stride, L, tw, hpos_all, nchan, h, nullptr, nullptr, s);
+}
+void launch_chan_multi_half(int log2f, VSrc<cf> src, cf* out, long out_stride, int L, const cf* tw, const cf* tw_half,
+                            const cf* hpos_all, int nchan, const FmChainArgs& h, hipStream_t s) {
+    launch_fm_multi_half_t<VSrc<cf>, true>(log2f, src, reinterpret_cast<float*>(out), out_stride, L, tw, tw_half, hpos_all, nchan, h,
+                                           nullptr, nullptr, s);
+}
+void launch_chan_multi_half_iq8(int log2f, VSrcIQ8 src, cf* out, long out_stride, int L, const cf* tw, const cf* tw_half,
+                                const cf* hpos_all, int nchan, const FmChainArgs& h, hipStream_t s) {
+    launch_fm_multi_half_t<VSrcIQ8, true>(log2f, src, reinterpret_cast<float*>(out), out_stride, L, tw, tw_half, hpos_all, nchan, h,
+                                          nullptr, nullptr, s);
 }
 
 }  // namespace rr

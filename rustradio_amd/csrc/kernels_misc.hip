@@ -358,11 +358,13 @@ struct ChainBlocksCtx {
     int sparse;                                                      // ceil(D / I) > S: at most one output per reference block
 };
 __device__ __forceinline__ long chain_n2(long y, long I, long D) { return (long)(((__int128)y * I + D - 1) / D); }   // first r index whose source is >= y
-template <class T, bool DEMOD, bool WIDE>
-__global__ __launch_bounds__(256) void k_chain_blocks_nonfinite(ChainBlocksCtx c) {
+// O: the output type — float (FM / audio chains) or cf (the channelizer, rr_channelizer_create: T = cf, no demodulator; an
+// output is NaN iff the filtered sample it IS lies in a poisoned stretch, a smeared one is refolded with nf_fold_cc)
+template <class T, bool DEMOD, bool WIDE, class O>
+__device__ __forceinline__ void chain_blocks_body(const ChainBlocksCtx& c) {
     const VSrc<T> src{static_cast<const T*>(c.prefix), c.plen, static_cast<const T*>(c.in), c.in_len};
     const int ch = (int)blockIdx.y;
-    float* out = c.out + (long)ch * c.out_stride;
+    O* out = reinterpret_cast<O*>(c.out) + (long)ch * c.out_stride;
     const long b0 = (long)blockIdx.x * c.bpw, b1 = b0 + c.bpw < c.nb ? b0 + c.bpw : c.nb;
     if (b0 >= b1) return;
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, nw = (int)(blockDim.x >> 6);
@@ -495,6 +497,12 @@ __global__ __launch_bounds__(256) void k_chain_blocks_nonfinite(ChainBlocksCtx c
                 const float re = sub_rn(mul_rn(a.x, bq.x), mul_rn(na, bq.y));
                 const float im = add_rn(mul_rn(a.x, bq.y), mul_rn(na, bq.x));
                 out[o] = mul_rn(c.gain, c.mode == 0 ? atan2f(im, re) : fm_atan2(im, re));
+            } else if constexpr (std::is_same<O, cf>::value) {
+                const bool p = poisoned_any(yb);
+                if (lane != 0) continue;
+                if (p) { out[o] = mkcf(nanv, nanv); continue; }
+                if (!nf_bad(out[o])) continue;
+                out[o] = nf_fold_cc(src, static_cast<const cf*>(c.rev) + (long)ch * c.rev_stride, c.L, yb);
             } else {
                 const bool p = poisoned_any(yb);
                 if (lane != 0) continue;
@@ -517,6 +525,10 @@ __global__ __launch_bounds__(256) void k_chain_blocks_nonfinite(ChainBlocksCtx c
                 const float re = sub_rn(mul_rn(a.x, bq.x), mul_rn(na, bq.y));
                 const float im = add_rn(mul_rn(a.x, bq.y), mul_rn(na, bq.x));
                 out[o] = mul_rn(c.gain, c.mode == 0 ? atan2f(im, re) : fm_atan2(im, re));
+            } else if constexpr (std::is_same<O, cf>::value) {
+                if (poisoned(yb)) { out[o] = mkcf(nanv, nanv); continue; }
+                if (!nf_bad(out[o])) continue;
+                out[o] = nf_fold_cc(src, static_cast<const cf*>(c.rev) + (long)ch * c.rev_stride, c.L, yb);
             } else {
                 if (poisoned(yb)) { out[o] = nanv; continue; }
                 if (!nf_bad(out[o])) continue;
@@ -544,7 +556,11 @@ __global__ __launch_bounds__(256) void k_chain_blocks_nonfinite(ChainBlocksCtx c
         }
     }
 }
-template <class T, bool DEMOD>
+template <class T, bool DEMOD, bool WIDE>
+__global__ __launch_bounds__(256) void k_chain_blocks_nonfinite(ChainBlocksCtx c) { chain_blocks_body<T, DEMOD, WIDE, float>(c); }
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_chan_blocks_nonfinite(ChainBlocksCtx c) { chain_blocks_body<cf, false, WIDE, cf>(c); }
+template <class T, bool DEMOD, bool CX = false>
 static void launch_chain_blocks(ChainBlocksCtx c, hipStream_t s) {
     if (c.n_y <= 0 || c.nchan <= 0) return;
     c.nb = c.n_y / c.S;
@@ -559,7 +575,10 @@ static void launch_chain_blocks(ChainBlocksCtx c, hipStream_t s) {
     const long gx = (c.nb + c.bpw - 1) / c.bpw;
     const __int128 lim = (__int128)1 << 62;
     const bool wide = (__int128)(c.A + c.n_y + 1) * c.I >= lim || (__int128)(c.r_hi + 1) * c.D >= lim;
-    if (wide) hipLaunchKernelGGL((k_chain_blocks_nonfinite<T, DEMOD, true>), dim3((unsigned)gx, (unsigned)c.nchan), dim3(256), 0, s, c);
+    if constexpr (CX) {
+        if (wide) hipLaunchKernelGGL((k_chan_blocks_nonfinite<true>), dim3((unsigned)gx, (unsigned)c.nchan), dim3(256), 0, s, c);
+        else hipLaunchKernelGGL((k_chan_blocks_nonfinite<false>), dim3((unsigned)gx, (unsigned)c.nchan), dim3(256), 0, s, c);
+    } else if (wide) hipLaunchKernelGGL((k_chain_blocks_nonfinite<T, DEMOD, true>), dim3((unsigned)gx, (unsigned)c.nchan), dim3(256), 0, s, c);
     else hipLaunchKernelGGL((k_chain_blocks_nonfinite<T, DEMOD, false>), dim3((unsigned)gx, (unsigned)c.nchan), dim3(256), 0, s, c);
     RR_HIP(hipGetLastError());
 }
@@ -569,6 +588,12 @@ void launch_chain_blocks_nonfinite(VSrc<cf> src, float* out, long out_stride, in
     ChainBlocksCtx c{src.prefix, src.plen, src.in, src.in_len, out, out_stride, nchan, a.A, a.n_y, a.r_lo, a.r_hi, a.o_base, a.I, a.D,
                      S, hist, P, L, front, rev, rev_stride, a.gain, a.mode, last_in, last_out, slots, seq, 0, 0, force, 0};
     launch_chain_blocks<cf, true>(c, s);
+}
+void launch_chan_blocks_nonfinite(VSrc<cf> src, cf* out, long out_stride, int nchan, const FmChainArgs& a, long S, long hist, long P,
+                                  int L, const cf* rev, long rev_stride, int* slots, int seq, hipStream_t s) {
+    ChainBlocksCtx c{src.prefix, src.plen, src.in, src.in_len, reinterpret_cast<float*>(out), out_stride, nchan, a.A, a.n_y, a.r_lo, a.r_hi,
+                     a.r_lo, a.I, a.D, S, hist, P, L, 0, rev, rev_stride, 1.0f, 0, nullptr, nullptr, slots, seq, 0, 0, 0, 0};
+    launch_chain_blocks<cf, false, true>(c, s);
 }
 void launch_chain_blocks_nonfinite(VSrc<float> src, float* out, const AudioChainArgs& a, long S, long hist, long P, int L,
                                    const float* rev, int* slots, int seq, hipStream_t s) {

@@ -504,6 +504,26 @@ __device__ __forceinline__ void poly_store_tile(const creg* ldsR, int lane0, int
     for (int i = lane0; i < nv; i += stride, pu += stride, o += stride) *o = *pu;
 }
 
+// The channelizer (rr_channelizer_create, launch_chan_poly): the tile's samples r[u0 + i] to out[u0 - o_base + i] as 16-byte
+// stores of two samples (global_store_dwordx4; the LDS reads are 8-byte, any start is conflict-free: nat_store); a window
+// position that is not 16-byte aligned has its first sample stored alone, an odd remainder its last.
+__device__ __forceinline__ void poly_store_pairs(const creg* ldsR, int lane, long u0, int Sa, const PolyArgs& a, cf* __restrict__ out) {
+    const long left = a.r_hi - u0;
+    const int nv = left < Sa ? (int)left : Sa;
+    if (nv <= 0) return;
+    cf* o = out + (u0 - a.o_base);
+    const creg* r = ldsR + a.Ls;
+    const int h = (int)(((uintptr_t)o >> 3) & 1);
+    if (h && lane == 0) o[0] = from_reg(r[0]);
+    const int np = (nv - h) >> 1;
+    creg2* o2 = reinterpret_cast<creg2*>(o + h);
+    for (int j = lane; j < np; j += PT) {
+        const creg x0 = r[h + 2 * j], x1 = r[h + 2 * j + 1];
+        o2[j] = creg2{x0.x, x0.y, x1.x, x1.y};
+    }
+    if (((nv - h) & 1) && lane == 0) o[nv - 1] = from_reg(r[nv - 1]);
+}
+
 // mode 2 (decimating FirFilter): the reference's locality for non-finite samples (nan_fix.hpp; the context is the kernels'
 // first argument, built by launch_chain_poly_d)
 
@@ -725,7 +745,8 @@ void k_fm_chain_polyw(NanFixCtx nfx, SRC src, float* __restrict__ out, long ntil
 }
 
 // ---- N channels on one input -------------------------------------------------------------------------------------
-template <int D, class SRC>
+// (CX: the channelizer — the channel's samples stored, poly_store_pairs, instead of demodulated; out is then cf*)
+template <int D, class SRC, bool CX = false>
 __global__ __launch_bounds__(512, 1)
 void k_fm_multi_poly(SRC src, float* __restrict__ out, long out_stride, long ntiles, const cf* __restrict__ tw,
                      const cf* __restrict__ hreg, int nchan, PolyArgs a, const cf* __restrict__ last_r_in,
@@ -837,6 +858,11 @@ void k_fm_multi_poly(SRC src, float* __restrict__ out, long out_stride, long nti
             nat_store(z, t, ex);                         // natural order in the wave's own area
             wave_fence();
             if (c == 8 * r0 + w) PSTAMP(4);
+            if constexpr (CX) {
+                poly_store_pairs(ex, t, u0, Sa, a, reinterpret_cast<cf*>(out) + (long)c * out_stride);
+                wave_fence();
+                continue;
+            }
             float* oc = out + (long)c * out_stride;
             if (a.mode == 0) {
                 if (tile_tame(z)) poly_demod_tile<0, true>(ex, t, PT, u0, Sa, a, oc, last_r_in + c, last_r_out + c);
@@ -856,7 +882,7 @@ void k_fm_multi_poly(SRC src, float* __restrict__ out, long out_stride, long nti
 // of 30 VGPRs, the responses and the parked spectra in HALF-phase buffers (8 registers each, the next half in flight), so
 // that the kernel fits 168 VGPRs; LDS: 12 exchange areas + D parked spectra + the tables = 161.8 KB at D = 6.
 constexpr int MW = 12;
-template <int D, class SRC>
+template <int D, class SRC, bool CX = false>
 __global__ __launch_bounds__(64 * MW, 1)
 void k_fm_multi_poly12(SRC src, float* __restrict__ out, long out_stride, long ntiles, const cf* __restrict__ tw,
                        const cf* __restrict__ hreg, int nchan, PolyArgs a, const cf* __restrict__ last_r_in,
@@ -935,6 +961,11 @@ void k_fm_multi_poly12(SRC src, float* __restrict__ out, long out_stride, long n
             nat_store(z, t, ex);
             wave_fence();
             RR_MARK("demod");
+            if constexpr (CX) {
+                poly_store_pairs(ex, t, u0, Sa, a, reinterpret_cast<cf*>(out) + (long)c * out_stride);
+                wave_fence();
+                continue;
+            }
             float* oc = out + (long)c * out_stride;
             if (a.mode == 0) {
                 if (tile_tame(z)) poly_demod_tile<0, true>(ex, t, PT, u0, Sa, a, oc, last_r_in + c, last_r_out + c);
@@ -1105,7 +1136,7 @@ static PolyPart poly_partition(long ntiles, int R, int G, int wC, int wF) {
     return cache.emplace(key, p).first->second;
 }
 
-template <int D, class SRC>
+template <int D, class SRC, bool CX>
 static void launch_multi_poly_d(SRC src, float* out, long out_stride, int L, const cf* tw, const cf* hreg, int nchan,
                                 const FmChainArgs& h, const cf* last_in, cf* last_out, hipStream_t s) {
     const PolyArgs a = poly_args(h, L);
@@ -1134,23 +1165,35 @@ static void launch_multi_poly_d(SRC src, float* out, long out_stride, int L, con
         const bool use12 = h.multi_waves == 12 || (h.multi_waves == 0 && nchan > 8 && part12.cost < part.cost);
         if (use12) {
             const size_t smem12 = sizeof(cf) * (MW * PLE + D * PF + 64 + 15 * PT);
-            (void)grid_for_tiles(k_fm_multi_poly12<D, SRC>, 64 * MW, smem12, G12);               // (sets the shared-memory attribute once)
-            hipLaunchKernelGGL((k_fm_multi_poly12<D, SRC>), dim3((unsigned)G12), dim3(64 * MW), smem12, s, src, out, out_stride, ntiles, tw,
-                               hreg, nchan, a, last_in, last_out, part12);
+            if constexpr (CX) {
+                (void)grid_for_tiles(k_fm_multi_poly12<D, SRC, true>, 64 * MW, smem12, G12);
+                hipLaunchKernelGGL((k_fm_multi_poly12<D, SRC, true>), dim3((unsigned)G12), dim3(64 * MW), smem12, s, src, out, out_stride, ntiles,
+                                   tw, hreg, nchan, a, nullptr, nullptr, part12);
+            } else {
+                (void)grid_for_tiles(k_fm_multi_poly12<D, SRC>, 64 * MW, smem12, G12);               // (sets the shared-memory attribute once)
+                hipLaunchKernelGGL((k_fm_multi_poly12<D, SRC>), dim3((unsigned)G12), dim3(64 * MW), smem12, s, src, out, out_stride, ntiles, tw,
+                                   hreg, nchan, a, last_in, last_out, part12);
+            }
             RR_HIP(hipGetLastError());
             return;
         }
     }
-    (void)grid_for_tiles(k_fm_multi_poly<D, SRC>, 512, smem, G);                     // (sets the shared-memory attribute once)
-    hipLaunchKernelGGL((k_fm_multi_poly<D, SRC>), dim3((unsigned)G), dim3(512), smem, s, src, out, out_stride, ntiles, tw, hreg,
-                       nchan, a, last_in, last_out, fft_stamp_buffer(), part);
+    if constexpr (CX) {
+        (void)grid_for_tiles(k_fm_multi_poly<D, SRC, true>, 512, smem, G);
+        hipLaunchKernelGGL((k_fm_multi_poly<D, SRC, true>), dim3((unsigned)G), dim3(512), smem, s, src, out, out_stride, ntiles, tw, hreg,
+                           nchan, a, nullptr, nullptr, nullptr, part);
+    } else {
+        (void)grid_for_tiles(k_fm_multi_poly<D, SRC>, 512, smem, G);                     // (sets the shared-memory attribute once)
+        hipLaunchKernelGGL((k_fm_multi_poly<D, SRC>), dim3((unsigned)G), dim3(512), smem, s, src, out, out_stride, ntiles, tw, hreg,
+                           nchan, a, last_in, last_out, fft_stamp_buffer(), part);
+    }
     RR_HIP(hipGetLastError());
 }
-template <class SRC>
+template <class SRC, bool CX = false>
 static void launch_multi_poly_t(SRC src, float* out, long out_stride, int L, const cf* tw, const cf* hreg, int nchan,
                                 const FmChainArgs& h, const cf* last_in, cf* last_out, hipStream_t s) {
     switch (h.D) {
-#define RR_POLY_CASE(DV) case DV: launch_multi_poly_d<DV>(src, out, out_stride, L, tw, hreg, nchan, h, last_in, last_out, s); break
+#define RR_POLY_CASE(DV) case DV: launch_multi_poly_d<DV, SRC, CX>(src, out, out_stride, L, tw, hreg, nchan, h, last_in, last_out, s); break
     RR_POLY_CASE(2); RR_POLY_CASE(3); RR_POLY_CASE(4); RR_POLY_CASE(5); RR_POLY_CASE(6); RR_POLY_CASE(7); RR_POLY_CASE(8);
     RR_POLY_CASE(9); RR_POLY_CASE(10); RR_POLY_CASE(11);
 #undef RR_POLY_CASE
@@ -1164,6 +1207,14 @@ void launch_fm_multi_poly(VSrc<cf> src, float* out, long out_stride, int L, cons
 void launch_fm_multi_poly_iq8(VSrcIQ8 src, float* out, long out_stride, int L, const cf* tw, const cf* hreg, int nchan,
                               const FmChainArgs& a, const cf* last_in, cf* last_out, hipStream_t s) {
     launch_multi_poly_t(src, out, out_stride, L, tw, hreg, nchan, a, last_in, last_out, s);
+}
+void launch_chan_poly(VSrc<cf> src, cf* out, long out_stride, int L, const cf* tw, const cf* hreg, int nchan, const FmChainArgs& a,
+                      hipStream_t s) {
+    launch_multi_poly_t<VSrc<cf>, true>(src, reinterpret_cast<float*>(out), out_stride, L, tw, hreg, nchan, a, nullptr, nullptr, s);
+}
+void launch_chan_poly_iq8(VSrcIQ8 src, cf* out, long out_stride, int L, const cf* tw, const cf* hreg, int nchan, const FmChainArgs& a,
+                          hipStream_t s) {
+    launch_multi_poly_t<VSrcIQ8, true>(src, reinterpret_cast<float*>(out), out_stride, L, tw, hreg, nchan, a, nullptr, nullptr, s);
 }
 
 }  // namespace rr

@@ -831,6 +831,10 @@ inline const rr_c32* c32(const std::vector<Complex>& v) { return reinterpret_cas
 inline auto FmChain(ReadStream<Complex> src, const std::vector<Complex>& taps, size_t interp, size_t deci, Float gain, bool exact_atan2 = true) {
     return Fused<Complex, Float>::make(std::move(src), [&] { return rr_fm_chain_create(c32(taps), taps.size(), interp, deci, gain, exact_atan2 ? RR_ATAN2_EXACT : RR_ATAN2_FAST); });
 }
+// FftFilter -> RationalResampler fused, Complex out (rr_channelizer_create with one channel; examples/rtl_downsampled.rs:37-52)
+inline auto FftFilterResampler(ReadStream<Complex> src, const std::vector<Complex>& taps, size_t interp, size_t deci) {
+    return Fused<Complex, Complex>::make(std::move(src), [&] { return rr_channelizer_create(c32(taps), 1, taps.size(), interp, deci); });
+}
 // FirFilter -> FftFilter as one convolution (the north star's pair)
 inline auto FirFftFilter(ReadStream<Complex> src, const std::vector<Complex>& fir_taps, const std::vector<Complex>& fft_taps) {
     return Fused<Complex, Complex>::make(std::move(src), [&] { return rr_fir_fftfilter_create(c32(fir_taps), fir_taps.size(), c32(fft_taps), fft_taps.size()); });
