@@ -216,6 +216,56 @@ static void graph_fm_chain() {
     CHECK(worst < 1e-4);
 }
 
+// FftFilterResampler (rr_channelizer_create with one channel) under the mirror's Graph against the definition in double:
+// y[n] = sum_k taps[k] x[n - k] with x[< 0] = 0, out[r] = y[(r deci) / interp] with the ratio as given; the sink holds the
+// resampled samples of the whole filter blocks the stream fills (fft_filter.rs:289-355, rational_resampler.rs:154-213).
+static void fft_filter_resampler_against_the_definition() {
+    const size_t n = 200000;
+    std::vector<Complex> x(n);
+    uint64_t st = 777;
+    auto rnd = [&] { st = st * 6364136223846793005ULL + 1442695040888963407ULL; return (float)((st >> 40) / 8388608.0 - 1.0); };
+    for (size_t i = 0; i < n; i++) {
+        const double w = 2.0 * M_PI * 0.013 * (double)i;
+        x[i] = Complex((float)(0.7 * std::cos(w)) + 0.2f * rnd(), (float)(0.7 * std::sin(w)) + 0.2f * rnd());
+    }
+    auto base = fir::low_pass_complex(2.4e6f, 100e3f, 50e3f, WindowType::Hamming());
+    CHECK(base.size() > 64 && base.size() < 256);
+    std::vector<Complex> taps(base.size());
+    for (size_t k = 0; k < base.size(); k++)              // Complex taps, centred on the tone
+        taps[k] = base[k] * Complex((float)std::cos(2.0 * M_PI * 0.013 * (double)k), (float)std::sin(2.0 * M_PI * 0.013 * (double)k));
+    size_t fft_size = 1;
+    while (fft_size < taps.size()) fft_size <<= 1;
+    const size_t nsamples = 2 * fft_size - taps.size();   // fft_filter.rs:36-42, 261-262
+    const size_t ratios[3][2] = {{1, 6}, {2, 3}, {3, 18}};
+    for (const auto& r : ratios) {
+        const size_t interp = r[0], deci = r[1];
+        auto [src, s0] = VectorSource<Complex>::new_(x);
+        auto [b, s1] = FftFilterResampler(std::move(s0), taps, interp, deci);
+        auto sink = std::make_unique<VectorSink<Complex>>(std::move(s1));
+        auto hook = sink->hook();
+        Graph g;
+        g.add(std::move(src)); g.add(std::move(b)); g.add(std::move(sink));
+        g.run();
+        const size_t n1 = (n / nsamples) * nsamples, n2 = (n1 * interp + deci - 1) / deci;
+        CHECK(hook->size() == n2);
+        std::vector<std::complex<double>> want(std::min(n2, hook->size()));
+        double big = 0;
+        for (size_t u = 0; u < want.size(); u++) {
+            const size_t m = u * deci / interp;
+            std::complex<double> acc(0, 0);
+            for (size_t k = 0; k < taps.size() && k <= m; k++)
+                acc += std::complex<double>(taps[k].real(), taps[k].imag()) * std::complex<double>(x[m - k].real(), x[m - k].imag());
+            want[u] = acc;
+            big = std::max(big, std::abs(acc));
+        }
+        double worst = 0;
+        for (size_t u = 0; u < want.size(); u++)
+            worst = std::max(worst, std::abs(std::complex<double>((*hook)[u].real(), (*hook)[u].imag()) - want[u]));
+        CHECK(big > 0.1);
+        CHECK(worst <= 1e-5 * big);
+    }
+}
+
 // Graph-level fusions against the blocks they replace, both through Graph on the GPU: FirFilter -> FftFilter as one
 // convolution, the metric's four-block chain as one kernel, the rtl_fm audio stage as one kernel.
 template <class T> static double max_rel(const std::vector<T>& a, const std::vector<T>& b, double floor_ = 0.0) {
@@ -634,6 +684,7 @@ static void tee_and_memcopy_between_device_rings() {
 int main() {
     test_complex(); test_identity(); moving_avg(); translate_matches_mixed_input(); test_filter_generator();
     fft_tag_propagation(); resampler_examples(); quad_known(); rtlsdr_decode_tests(); hilbert_rejects_even(); graph_fm_chain();
+    fft_filter_resampler_against_the_definition();
     device_resident_graph(); fused_blocks_equal_their_chains(); fanout_from_c_abi(); fft_message_block(); tee_and_signal_source(); tee_and_memcopy_between_device_rings(); sync_blocks(); fftstream_adds_frame_tags(); file_source_tests(); handles_on_concurrent_threads();
     printf(g_fail ? "FAILED (%d)\n" : "OK\n", g_fail);
     return g_fail ? 1 : 0;

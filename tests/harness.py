@@ -38,6 +38,27 @@ def max_norm_err(got, ref, scale=None) -> float:
     return float(np.max(np.abs(got.astype(np.complex128) - ref.astype(np.complex128)))) / den
 
 
+def resampled_filter_truth(taps, x, interp, deci, n_out):
+    """The float64 statement of FftFilter(taps) -> RationalResampler(interp, deci) on a stream that starts at x[0]:
+        y[n] = sum_k taps[k] x[n - k] in complex128, x[< 0] = 0;    out[r] = y[(r deci) // interp]
+    with interp and deci as given (not reduced), over the n_out samples the chain under test produced.  No block, ring or
+    tile appears in it.  (Long filters are convolved through a complex128 FFT as long as the whole stream: its rounding, some
+    1e-15 of the largest sample, is eight orders below the f32 chains it judges.)"""
+    t = np.asarray(taps).astype(np.complex128).reshape(-1)
+    xx = np.asarray(x).astype(np.complex128).reshape(-1)
+    n, L = len(xx), len(t)
+    idx = (np.arange(n_out, dtype=np.int64) * int(deci)) // int(interp)
+    assert n_out == 0 or idx[-1] < n, (n_out, int(idx[-1]) if n_out else 0, n)
+    if L <= 16:
+        y = np.zeros(n, np.complex128)
+        for k in range(min(L, n)):
+            y[k:] += t[k] * xx[:n - k]
+    else:
+        m = 1 << int(np.ceil(np.log2(n + L)))
+        y = np.fft.ifft(np.fft.fft(xx, m) * np.fft.fft(t, m))[:n]
+    return y[idx]
+
+
 def angle_parity(yg, yo, ro, tol=1e-5, skip=0):
     """Chain-level check of a demodulated stream against the oracle's (say how much of the allowance is
     used).  atan2 amplifies a 1e-5 error of the resampled stream `ro` by 1 / |r|, so the bound per sample is the stage

@@ -581,6 +581,70 @@ def test_fuzz_zero_copy_windows(rr, seed):
         assert np.array_equal(ya.view(np.uint8), yb.view(np.uint8)), (blk.name, seed)
 
 
+# ---- the channelizer ---------------------------------------------------------------------------------------------------
+CHAN_TAPS = [1, 2, 3, 64, 463, 767, 768, 769, 1024, 1025, 1536, 1537, 2467, 3329, 3330, 4000, 4094, 4095, 5000, 6144, 6145]
+CHAN_NCHAN = [1, 2, 3, 5, 8, 9, 17, 33]
+CHAN_KNOBS = [{}, {"fm_poly": -1}, {"fm_poly": 8}, {"fm_poly": 12}, {"fm_full": 1},
+              {"fm_poly": -1, "fft_log2f": 11}]         # (2048-point tiles wherever the filter fits: the half-size inverse's)
+CHAN_SEEDS = range(42)                                  # every tap count of the list twice
+
+
+def draw_channelizer(seed):
+    """One trial of test_fuzz_channelizer (tests/test_channelizer_cpu.py runs the oracle over the same draws): tap counts on
+    both sides of every limit of FmMulti's path selection (768 taps per phase at 1:2 and 1:8, 3329 / 3330, 4094 / 4095,
+    6144 / 6145, one tap), ratios 1..5 : 1..40 as drawn (pairs that reduce included), either source, an odd or even window
+    address, every kernel knob, odd and even windows of any size from one filter block's worth up."""
+    rng = np.random.default_rng(23000 + seed)
+    L = CHAN_TAPS[seed % len(CHAN_TAPS)]
+    nchan = int(rng.choice(CHAN_NCHAN))
+    if L > 2000:
+        nchan = min(nchan, 9)
+    I, D = int(rng.integers(1, 6)), int(rng.integers(1, 41))
+    kind = int(rng.integers(0, 3))                      # any pair; one that reduces to 1:2 .. 1:8; one that reduces to 1:even
+    if kind == 1:
+        D = I * int(rng.integers(2, 9))
+    elif kind == 2:
+        D = I * 2 * int(rng.integers(1, 40 // (2 * I) + 1))
+    u8, odd_addr = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
+    opts = CHAN_KNOBS[int(rng.integers(0, len(CHAN_KNOBS)))]
+    S = 2 * (1 << int(np.ceil(np.log2(L)))) - L if L > 1 else 1          # FftFilter's block
+    n = int(rng.integers(max(4 * S, 5000), 150_001))
+    nb = -(-S * I // D)
+    # (the floors bound a trial to some 40 calls)
+    cap_in = max(S + int(rng.integers(1, 3 * S + 20_000)), n // 40)
+    cap_out = max(nb + int(rng.integers(0, 3 * nb + 2000)), -(-n * I // (40 * D)))
+    taps = np.stack([_c(rng, L) / max(1, L // 4) for _ in range(nchan)])
+    if u8:
+        src = rng.integers(0, 256, 2 * n + int(rng.integers(0, 2)), dtype=np.uint8)
+        cap_in = 2 * cap_in + int(rng.integers(0, 2))                     # bytes
+    else:
+        src = _c(rng, n)
+    return {"L": L, "nchan": nchan, "I": I, "D": D, "u8": u8, "odd_addr": odd_addr, "opts": opts, "S": S, "n": n,
+            "cap_in": cap_in, "cap_out": cap_out, "taps": taps, "src": src}
+
+
+@pytest.mark.parametrize("seed", CHAN_SEEDS)
+def test_fuzz_channelizer(rr, seed):
+    """Random channelizers: every channel against its oracle chain at 1e-5 and against the float64 statement of the operation
+    within 1e-5 plus the oracle's own distance from it, the protocol log against the model of the path the constructor's
+    rules give (the fused block's n2 model, or the composition's rounds over the oracle's blocks).  The constructor takes
+    every shape, by composition if need be: nothing is skipped."""
+    import test_gpu_channelizer as tc
+    d = draw_channelizer(seed)
+    L, I, D, taps, src = d["L"], d["I"], d["D"], d["taps"], d["src"]
+    assert d["S"] == tc.nsamples(L)
+    family = tc.expected_kernel(L, I, D, d["opts"])
+    with rr.build_options(**d["opts"]):
+        blk = (rr.ChannelizerU8 if d["u8"] else rr.Channelizer)(taps, I, D)
+    assert ("per channel" in blk.name) == (family == "per channel"), (blk.name, family)
+    assert rr.lib().rr_block_out_windows(blk._h) == d["nchan"]
+    calls = []
+    yg, log = tc.drive(blk, src, d["nchan"], d["cap_in"], d["cap_out"], offset=int(d["odd_addr"]), calls=calls)
+    assert log == tc.expected_log(family, taps[0], I, D, src, calls), (seed, family)
+    x = run_chain([orc.RtlSdrDecode()], src) if d["u8"] else src
+    tc.check_three_ways(yg, taps, I, D, src, x, f"fuzz-{seed}-{family}-{L}-{I}:{D}-{d['nchan']}ch")
+
+
 @pytest.mark.parametrize("seed", list(range(24)) + [10074])       # (10074: found by round 6's soak — the head fix of the fused
 def test_fuzz_nonfinite_sets(rr, seed):                            #  FirFilter -> FftFilter cut a poisoned tile's run short of the probe stride)
     """Round 5: random filters, stream lengths, ring sizes and NaN / +-Inf positions (isolated, clustered, at the very ends,
