@@ -279,7 +279,39 @@ rr_block *rr_channelizer_create(const rr_c32 *taps, size_t nchan, size_t ntaps, 
 /* The same fed by the RTL-SDR byte stream: RtlSdrDecode (src/rtlsdr_decode.rs:9-47) fused in front of the Tee, as in
  * rr_fm_multi_u8_create (input windows, `consumed` and the WAIT_SRC `need` count BYTES). */
 rr_block *rr_channelizer_u8_create(const rr_c32 *taps, size_t nchan, size_t ntaps, size_t interp, size_t deci);
-/* number of output windows of a block (1 except rr_fm_multi[_u8]_create and rr_channelizer[_u8]_create) */
+/* N-station FM receiver down to audio: the whole of examples/rtl_fm.rs:381-419 on every branch of a Tee (src/tee.rs:10-24)
+ * fed by ONE Complex input stream — per channel c the six blocks
+ *   FftFilter::new(_, rf_taps[c]) (src/fft_filter.rs:289-355) -> RationalResampler::new(_, rf_interp, rf_deci)
+ *   (src/rational_resampler.rs:125-206) -> QuadratureDemod::new(_, gain) (src/quadrature_demod.rs:65-109; FastFM
+ *   :144-165 with RR_DEMOD_FASTFM) -> FftFilterFloat::new(_, audio_taps) (src/fft_filter.rs:365-491) ->
+ *   RationalResampler::new(_, audio_interp, audio_deci) -> MultiplyConst::new(_, scale) (src/multiply_const.rs:6-23)
+ * i.e. rr_fm_multi_create followed by one rr_audio_chain_create per channel, as ONE block of two tile launches per call
+ * whatever nchan is.  rf_taps = [nchan][rf_ntaps]; audio_taps is one set shared by all channels, as in rtl_fm.  Both filters
+ * start from zero history, both ratios are gcd-reduced.  Output: nchan consecutive windows of out_cap f32 elements (channel c
+ * at out + c*out_cap), identical counts; rr_block_out_windows returns nchan.
+ * work(): no output tail.  With S1 / S2 the nsamples of the RF / audio filter, d(y) = max(ceil(y rf_interp / rf_deci) - 1, 0)
+ * the demodulated samples after y filtered ones, and A(k) = ceil(floor(d(k S1) / S2) S2 audio_interp / audio_deci) the audio
+ * samples after k RF blocks (K blocks run so far, `pend` input samples carried): WAIT_DST(A(K+1) - A(K)) consuming nothing when
+ * that does not fit out_cap; else with k_out the largest k for which A(K+k) - A(K) fits and k_in = floor((pend + len) / S1):
+ * k_in > k_out runs k_out blocks, consumes k_out S1 - pend and returns WAIT_DST(A(K+k_out+1) - A(K+k_out)); otherwise runs k_in
+ * blocks, consumes the whole window and returns WAIT_SRC(S1 - new pend).  Counts depend on lengths only and are final on
+ * return.  EOF follows the source; tags: RR_TAGS_DROP.
+ * Shapes beyond the fused kernels (RR_DEMOD_FASTFM, more than 3584 audio taps, RF shapes rr_fm_multi_create runs per channel)
+ * run behind the same handle as rr_fm_multi feeding one rr_audio_chain per channel through device-resident streams of the
+ * reference's capacity: the same whole-stream output, with the window protocol of that composition (progress on any window,
+ * WAIT_DST / WAIT_SRC from the stage that stalls) instead of the one above.
+ * NULL + rr_last_error for an interp or deci of 0 ("RationalResampler created using deci 0"), nchan 0 or above 4096, either
+ * tap count 0.  A NaN input sample makes exactly the reference's audio samples NaN: those of the audio blocks that hold a
+ * demodulated sample of its poisoned RF block. */
+rr_block *rr_fm_receiver_create(const rr_c32 *rf_taps, size_t nchan, size_t rf_ntaps, size_t rf_interp, size_t rf_deci,
+                                float gain, int atan2_mode, const float *audio_taps, size_t audio_ntaps,
+                                size_t audio_interp, size_t audio_deci, float scale);
+/* The same fed by the RTL-SDR byte stream: RtlSdrDecode (src/rtlsdr_decode.rs:9-47) fused in front of the Tee — the whole
+ * of examples/rtl_fm.rs:328-419 — as rr_fm_multi_u8_create (input windows, `consumed` and the WAIT_SRC `need` count BYTES). */
+rr_block *rr_fm_receiver_u8_create(const rr_c32 *rf_taps, size_t nchan, size_t rf_ntaps, size_t rf_interp, size_t rf_deci,
+                                   float gain, int atan2_mode, const float *audio_taps, size_t audio_ntaps,
+                                   size_t audio_interp, size_t audio_deci, float scale);
+/* number of output windows of a block (1 except rr_fm_multi[_u8]_create, rr_channelizer[_u8]_create and rr_fm_receiver[_u8]_create) */
 size_t rr_block_out_windows(const rr_block *b);
 
 void rr_block_destroy(rr_block *b);

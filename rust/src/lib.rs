@@ -65,6 +65,8 @@ unsafe extern "C" {
     fn rr_fm_multi_u8_create(taps: *const Complex, nchan: usize, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_channelizer_create(taps: *const Complex, nchan: usize, ntaps: usize, interp: usize, deci: usize) -> *mut RrBlock;
     fn rr_channelizer_u8_create(taps: *const Complex, nchan: usize, ntaps: usize, interp: usize, deci: usize) -> *mut RrBlock;
+    fn rr_fm_receiver_create(rf_taps: *const Complex, nchan: usize, rf_ntaps: usize, rf_interp: usize, rf_deci: usize, gain: f32, atan2_mode: c_int, audio_taps: *const f32, audio_ntaps: usize, audio_interp: usize, audio_deci: usize, scale: f32) -> *mut RrBlock;
+    fn rr_fm_receiver_u8_create(rf_taps: *const Complex, nchan: usize, rf_ntaps: usize, rf_interp: usize, rf_deci: usize, gain: f32, atan2_mode: c_int, audio_taps: *const f32, audio_ntaps: usize, audio_interp: usize, audio_deci: usize, scale: f32) -> *mut RrBlock;
     fn rr_fanout_unique_id(id128: *mut c_void) -> c_int;
     fn rr_fanout_create(id128: *const c_void, rank: c_int, world: c_int, src_rank: c_int, tile_bytes: usize, flags: c_int) -> *mut RrFanout;
     fn rr_fanout_destroy(f: *mut RrFanout);
@@ -707,6 +709,62 @@ impl Block for GpuChannelizer {
         for d in &self.dsts { outs.push(d.write_buf()?); }
         let cap = outs.iter_mut().map(|o| o.slice().len()).min().unwrap_or(0);
         self.scratch.resize(self.nchan * cap.max(1), Complex::default());
+        let (mut c, mut p, mut need) = (0usize, 0usize, 0usize);
+        // SAFETY: scratch holds nchan windows of `cap` elements; input is a live window.
+        let st = unsafe {
+            rr_block_work(self.h.0, input.slice().as_ptr().cast(), input.slice().len(), self.scratch.as_mut_ptr().cast(), cap,
+                          &mut c, &mut p, &mut need)
+        };
+        if st == RR_ERR { return Err(last_error()); }
+        for (ch, mut o) in outs.into_iter().enumerate() {
+            o.slice()[..p].copy_from_slice(&self.scratch[ch * cap..ch * cap + p]);
+            o.produce(p, &[]);
+        }
+        input.consume(c);
+        Ok(if st == RR_WAIT_DST { BlockRet::WaitForStream(&self.dsts[0], need) } else { BlockRet::WaitForStream(&self.src, need) })
+    }
+}
+
+/// The N-station FM receiver down to audio (rr_fm_receiver_create): `Tee` (src/tee.rs:10-24) + N x the six blocks of
+/// examples/rtl_fm.rs:381-419 — FftFilter, RationalResampler, QuadratureDemod, FftFilterFloat, RationalResampler,
+/// MultiplyConst — on ONE input, two tile launches per call whatever N is.  N audio streams, staged through `scratch` like
+/// GpuFmMulti (4 B per output sample).  The resamplers drop tags (src/rational_resampler.rs:156), so none are forwarded.
+pub struct GpuFmReceiver {
+    h: Handle,
+    nchan: usize,
+    src: ReadStream<Complex>,
+    dsts: Vec<WriteStream<Float>>,
+    scratch: Vec<Float>,
+}
+impl GpuFmReceiver {
+    /// `rf_taps[c]` = channel c's RF filter (all of one length); `audio_taps` is shared by the channels, as in rtl_fm.
+    #[allow(clippy::too_many_arguments)]
+    pub fn new(src: ReadStream<Complex>, rf_taps: &[Vec<Complex>], rf_interp: usize, rf_deci: usize, gain: Float, fast_math: bool,
+               audio_taps: &[Float], audio_interp: usize, audio_deci: usize, scale: Float)
+        -> Result<(Self, Vec<ReadStream<Float>>)> {
+        let nchan = rf_taps.len();
+        let ntaps = rf_taps.first().map_or(0, Vec::len);
+        if rf_taps.iter().any(|t| t.len() != ntaps) { return Err(Error::msg("GpuFmReceiver: all channels need the same number of taps")); }
+        let flat: Vec<Complex> = rf_taps.iter().flatten().copied().collect();
+        // SAFETY: flat is a live [nchan][ntaps] array, audio_taps a live slice.
+        let h = Handle::new(unsafe {
+            rr_fm_receiver_create(flat.as_ptr(), nchan, ntaps, rf_interp, rf_deci, gain, fast_math as c_int,
+                                  audio_taps.as_ptr(), audio_taps.len(), audio_interp, audio_deci, scale)
+        })?;
+        debug_assert_eq!(unsafe { rr_block_out_windows(h.0) }, nchan);
+        let (dsts, drs): (Vec<_>, Vec<_>) = (0..nchan).map(|_| new_stream()).unzip();
+        Ok((Self { h, nchan, src, dsts, scratch: Vec::new() }, drs))
+    }
+}
+impl BlockName for GpuFmReceiver { fn block_name(&self) -> &str { "GpuFmReceiver" } }
+impl BlockEOF for GpuFmReceiver { fn eof(&mut self) -> bool { self.src.eof() } }
+impl Block for GpuFmReceiver {
+    fn work(&mut self) -> Result<BlockRet<'_>> {
+        let (input, _tags) = self.src.read_buf()?;
+        let mut outs = Vec::with_capacity(self.nchan);
+        for d in &self.dsts { outs.push(d.write_buf()?); }
+        let cap = outs.iter_mut().map(|o| o.slice().len()).min().unwrap_or(0);
+        self.scratch.resize(self.nchan * cap.max(1), 0.0);
         let (mut c, mut p, mut need) = (0usize, 0usize, 0usize);
         // SAFETY: scratch holds nchan windows of `cap` elements; input is a live window.
         let st = unsafe {

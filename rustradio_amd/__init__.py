@@ -599,5 +599,34 @@ def ChannelizerU8(taps_per_channel, interp: int, deci: int) -> Block:
     return Block(h, np.uint8, np.complex64)
 
 
+def _fm_receiver(create, in_dtype, taps_per_channel, rf_interp, rf_deci, audio_taps, audio_interp, audio_deci, gain, mode, scale):
+    t = np.ascontiguousarray(taps_per_channel, np.complex64)
+    if t.ndim != 2:
+        raise ValueError("taps_per_channel must be [nchan][ntaps]")
+    a = np.ascontiguousarray(audio_taps, np.float32)
+    if a.ndim != 1:
+        raise ValueError("audio_taps must be one set of taps, shared by the channels")
+    h = create(_ptr(t), t.shape[0], t.shape[1], rf_interp, rf_deci, gain, mode, _ptr(a), len(a), audio_interp, audio_deci, scale)
+    return Block(h, in_dtype, np.float32)
+
+
+def FmReceiver(taps_per_channel, rf_interp: int, rf_deci: int, audio_taps, audio_interp: int, audio_deci: int,
+               gain: float = 1.0, mode: int = ATAN2_EXACT, scale: float = 1.0) -> Block:
+    """The N-station FM receiver down to audio (rr_fm_receiver_create): Tee + N x (FftFilter(taps_c) -> RationalResampler ->
+    QuadratureDemod -> FftFilterFloat(audio_taps) -> RationalResampler -> MultiplyConst), examples/rtl_fm.rs:381-419 per
+    channel, two tile launches per call.  taps_per_channel = [N][ntaps]; audio_taps is shared.  work() returns out with
+    shape (N, produced); work_dev() takes N windows of out_cap f32 elements."""
+    return _fm_receiver(lib().rr_fm_receiver_create, np.complex64, taps_per_channel, rf_interp, rf_deci, audio_taps,
+                        audio_interp, audio_deci, gain, mode, scale)
+
+
+def FmReceiverU8(taps_per_channel, rf_interp: int, rf_deci: int, audio_taps, audio_interp: int, audio_deci: int,
+                 gain: float = 1.0, mode: int = ATAN2_EXACT, scale: float = 1.0) -> Block:
+    """RtlSdrDecode -> FmReceiver fused: RTL-SDR bytes in, N f32 audio windows out (windows, consumed and the WAIT_SRC need
+    count bytes)."""
+    return _fm_receiver(lib().rr_fm_receiver_u8_create, np.uint8, taps_per_channel, rf_interp, rf_deci, audio_taps,
+                        audio_interp, audio_deci, gain, mode, scale)
+
+
 def Hilbert(ntaps: int, wtype: int = WIN_HAMMING, parm: float = 0.0) -> Block:
     return Block(lib().rr_hilbert_create(ntaps, wtype, parm), np.float32, np.complex64)

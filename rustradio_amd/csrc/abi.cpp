@@ -227,6 +227,22 @@ rr_block* rr_channelizer_create(const rr_c32* taps, size_t nchan, size_t ntaps, 
 rr_block* rr_channelizer_u8_create(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci) {
     return make_block([&] { return rr::make_channelizer(taps, nchan, ntaps, interp, deci, true); });
 }
+rr_block* rr_fm_receiver_create(const rr_c32* rf_taps, size_t nchan, size_t rf_ntaps, size_t rf_interp, size_t rf_deci, float gain,
+                                int atan2_mode, const float* audio_taps, size_t audio_ntaps, size_t audio_interp, size_t audio_deci,
+                                float scale) {
+    return make_block([&] {
+        return rr::make_fm_receiver(rf_taps, nchan, rf_ntaps, rf_interp, rf_deci, gain, atan2_mode, audio_taps, audio_ntaps,
+                                    audio_interp, audio_deci, scale, false);
+    });
+}
+rr_block* rr_fm_receiver_u8_create(const rr_c32* rf_taps, size_t nchan, size_t rf_ntaps, size_t rf_interp, size_t rf_deci, float gain,
+                                   int atan2_mode, const float* audio_taps, size_t audio_ntaps, size_t audio_interp, size_t audio_deci,
+                                   float scale) {
+    return make_block([&] {
+        return rr::make_fm_receiver(rf_taps, nchan, rf_ntaps, rf_interp, rf_deci, gain, atan2_mode, audio_taps, audio_ntaps,
+                                    audio_interp, audio_deci, scale, true);
+    });
+}
 size_t rr_block_out_windows(const rr_block* b) { return b ? b->b->out_windows() : 0; }
 void rr_block_destroy(rr_block* b) { try { delete b; } catch (...) {} }
 

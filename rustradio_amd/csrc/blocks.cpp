@@ -1756,6 +1756,131 @@ int FmMulti::work_blocks(const void* in, size_t in_len, float* out, size_t out_s
     return st;
 }
 
+// ---- N-station FM receiver: FmMulti -> C audio chains in one kernel (examples/rtl_fm.rs:381-419 behind a Tee) ------------
+FmReceiver::FmReceiver(const rr_c32* rf_taps, size_t nchan, size_t rf_ntaps, size_t rf_interp, size_t rf_deci, float gain, int mode,
+                       const float* audio_taps, size_t audio_ntaps, size_t audio_interp, size_t audio_deci, float sc, bool u8)
+    : Block(u8 ? "RtlSdrDecode>Tee>N x (FftFilter>RationalResampler>QuadratureDemod>FftFilterFloat>RationalResampler>MultiplyConst)"
+               : "Tee>N x (FftFilter>RationalResampler>QuadratureDemod>FftFilterFloat>RationalResampler>MultiplyConst)",
+            u8 ? 1 : 8, 4), C(nchan), iq8(u8), scale(sc) {
+    zero_copy_in = false;                            // (as FmMulti: its kernels read a tile once per run of channel rounds)
+    if (audio_ntaps == 0) throw Error("FftFilterFloat: empty taps");
+    if (audio_deci == 0) throw Error("RationalResampler created using deci 0");
+    if (audio_interp == 0) throw Error("RationalResampler created using interp 0");
+    if (audio_interp > (size_t)1 << 31 || audio_deci > (size_t)1 << 31) throw NotFusedShape("FmReceiver: interp and deci must be <= 2^31");
+    if (audio_ntaps > 3584) throw NotFusedShape("FmReceiver: at most 3584 audio taps (real-stream tiles of up to 4096 points)");
+    rf.reset(new FmMulti(rf_taps, nchan, rf_ntaps, rf_interp, rf_deci, gain, mode, u8));      // (may throw NotFusedShape)
+    const int64_t gg = gcd64((int64_t)audio_deci, (int64_t)audio_interp);
+    D2 = (int64_t)audio_deci / gg; I2 = (int64_t)audio_interp / gg;
+    std::vector<rr_c32> ct(audio_ntaps);
+    for (size_t i = 0; i < audio_ntaps; i++) ct[i] = rr_c32{audio_taps[i], 0.0f};              // fft_filter.rs:398
+    af.reset(new FftFilter(ct.data(), audio_ntaps, false, 12, true));
+    if (!audio_multi_supported(af->log2f)) throw NotFusedShape("FmReceiver: audio tile beyond the fused kernel");
+    // The tile above minimises the cost per sample of a full chip.  A call whose work items — tiles x channels, all channels
+    // together — number fewer than the CUs leaves CUs idle whatever the tile costs: such calls run on the next smaller tile
+    // (twice the items, each about half as long), where it still yields at least half its points.
+    if (build_opts().fft_log2f == 0 && af->log2f > 10 && ((size_t)1 << (af->log2f - 1)) >= 2 * audio_ntaps) {
+        BuildOpts o = build_opts();
+        o.fft_log2f = af->log2f - 1;
+        set_build_opts(&o);
+        try {
+            af_small.reset(new FftFilter(ct.data(), audio_ntaps, false, 12, true));
+        } catch (...) {
+            o.fft_log2f = 0; set_build_opts(&o);
+            throw;
+        }
+        o.fft_log2f = 0; set_build_opts(&o);
+    }
+    pstride = af->hist + af->nsamples;               // [L - 1 history][pending < nsamples]; zero history at stream start
+    for (auto& p : pre) {
+        p.reserve(C * pstride);
+        RR_HIP(hipMemsetAsync(p.p, 0, C * pstride * sizeof(float), stream));
+    }
+    if (chain_nf_wanted(u8, I2, D2, af->nsamples)) {
+        std::vector<float> r(audio_ntaps);
+        for (size_t j = 0; j < audio_ntaps; j++) r[j] = audio_taps[audio_ntaps - 1 - j];
+        rev_f.upload(r.data(), r.size(), stream);
+        std::vector<int> none(6 * C, -1);
+        slots.upload(none.data(), none.size(), stream);
+        nf_on = true;
+    }
+    RR_HIP(hipStreamSynchronize(stream));
+}
+
+// A(k) = ceil(floor(d(k S1) / S2) S2 I2 / D2), d(y) = max(ceil(y I1 / D1) - 1, 0): the demodulator lags the resampler by one sample
+uint64_t FmReceiver::audio_after(uint64_t k) const {
+    const FmChain& ch = *rf->chain;
+    const uint64_t r = (uint64_t)(((__int128)(k * ch.f->nsamples) * ch.I + ch.D - 1) / ch.D);
+    const uint64_t d = r ? r - 1 : 0, S2 = af->nsamples;
+    return (uint64_t)(((__int128)(d / S2 * S2) * I2 + D2 - 1) / D2);
+}
+
+// AudioChain::work_blocks' protocol with N2 replaced by A: WAIT_DST(A(K + 1) - A(K)) when the audio the next RF block completes
+// does not fit; else as many RF blocks as the window offers and the output window takes, all of whose demodulated samples the
+// audio stage takes in (whole audio blocks filtered, the rest carried).  Counts depend on lengths only.
+int FmReceiver::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed, size_t* produced, size_t* need,
+                         hipStream_t s) {
+    *consumed = *produced = *need = 0;
+    FmChain& ch = *rf->chain;
+    const uint64_t S1 = ch.f->nsamples, S2 = af->nsamples;
+    const uint64_t K = ch.n1 / S1, a0 = audio_after(K);
+    if (audio_after(K + 1) - a0 > out_cap) { *need = audio_after(K + 1) - a0; return RR_WAIT_DST; }
+    const uint64_t k_in = (ch.f->pend_len + (iq8 ? in_len / 2 : in_len)) / S1;
+    uint64_t lo = 1, hi = std::max<uint64_t>(k_in, 1);             // largest k in [1, max(k_in, 1)] whose audio fits (A is monotone)
+    while (lo < hi) {
+        const uint64_t m = lo + (hi - lo + 1) / 2;
+        if (audio_after(K + m) - a0 <= out_cap) lo = m; else hi = m - 1;
+    }
+    const uint64_t k_fit = lo, kk = std::min(k_in, k_fit);
+    auto demod_after = [&](uint64_t k) {
+        const uint64_t r = (uint64_t)(((__int128)(k * S1) * ch.I + ch.D - 1) / ch.D);
+        return r ? r - 1 : 0;
+    };
+    // stage 1 into the internal buffer: room for the blocks it will run (at least one: FmMulti asks for that before it looks)
+    const size_t m_need = (size_t)(demod_after(K + std::max<uint64_t>(kk, 1)) - demod_after(K)) + 1;
+    if (mid_cap < m_need) {
+        mid_cap = m_need + m_need / 2 + 64;
+        mid.reserve(C * mid_cap);
+    }
+    size_t c1 = 0, p1 = 0, need1 = 0;
+    const int st1 = rf->work_blocks(in, in_len, mid.p, mid_cap, mid_cap, &c1, &p1, &need1, s, k_fit);
+    if (st1 == RR_ERR) return st1;
+    *consumed = c1;
+    // stage 2: the p1 new demodulated samples of every channel behind its carried ones
+    if (p1) {
+        const uint64_t total = pend_len + p1, k2 = total / S2, n_y = k2 * S2, new_pend = total - n_y;
+        auto N2 = [&](uint64_t y) { return (uint64_t)(((__int128)y * I2 + D2 - 1) / D2); };
+        const AudioMultiSrc src{pre[cur].p, (long)(af->hist + pend_len), (long)pstride, mid.p, (long)p1, (long)mid_cap};
+        AudioChainArgs a{(long)n1, (long)n_y, (long)N2(n1), (long)N2(n1 + n_y), I2, D2, scale, {}};
+        a.carry = CarryOut{pre[cur ^ 1].p, (long)n_y, (long)(af->hist + new_pend)};
+        const FftFilter* f = af.get();
+        if (af_small && k2) {
+            const uint64_t per = 2 * (((uint64_t)1 << af->log2f) - af->L + 1);
+            if (C * ((n_y + per - 1) / per) < (uint64_t)std::max(1, device_cu_count())) f = af_small.get();
+        }
+        if ((size_t)(a.r_hi - a.r_lo) > out_cap) throw Error("FmReceiver: bookkeeping out of step");
+        prof_begin(s);
+        launch_audio_multi(f->log2f, src, (int)C, static_cast<float*>(out), (long)out_cap, (int)f->L, f->d_tw.p, f->d_hpos.p, a, s);
+        prof_end(s);
+        if (nf_on && k2) {
+            const long P_y = (long)((size_t)1 << f->log2f) - (long)f->L + 1;       // one real segment of a tile
+            launch_audio_multi_blocks_nonfinite(src, (int)C, static_cast<float*>(out), (long)out_cap, a, (long)S2, (long)af->hist,
+                                                chain_probe_stride(P_y, I2, D2), (int)af->L, rev_f.p, slots.p, nf_seq, s);
+            nf_seq++;
+        }
+        cur ^= 1;
+        pend_len = new_pend;
+        *produced = a.r_hi - a.r_lo;
+        n1 += n_y;
+    }
+    if (st1 == RR_WAIT_DST) {
+        const uint64_t Kn = ch.n1 / S1;
+        *need = audio_after(Kn + 1) - audio_after(Kn);
+        return RR_WAIT_DST;
+    }
+    *need = need1;
+    return st1;
+}
+
 // ---- FftFilterFloat (fft_filter.rs:365-491) ---------------------------------------------------------
 FftFilterFloat::FftFilterFloat(const float* taps, size_t ntaps) : Block("FftFilterFloat", 4, 4) {
     if (ntaps == 0) throw Error("FftFilterFloat: empty taps");

@@ -431,6 +431,52 @@ struct FmMulti : Block {
     bool eof(bool src_eof) override { return src_eof && !tail.pending(); }
 };
 
+// The whole N-station FM receiver of examples/rtl_fm.rs:381-419 behind a Tee (tee.rs:10-24): FmMulti (stage 1, f32 outputs)
+// into an internal [C][mid_cap] buffer, then the C audio chains FftFilterFloat -> RationalResampler -> MultiplyConst as ONE
+// kernel (k_audio_multi) on that buffer: two tile launches per call whatever C is.  One set of audio taps for all channels.
+// Every channel moves the same counts, so the audio bookkeeping (n1, pend_len, cur) is shared and only the carry prefixes and
+// the non-finite verdict slots are per channel.  No output tail (as the channelizer): a call runs as many RF blocks as the
+// audio they complete fits the window, see work_dev.
+struct FmReceiver : Block {
+    size_t C;
+    bool iq8 = false;
+    std::unique_ptr<FmMulti> rf;          // stage 1: carries its own input state; driven through work_blocks(..., max_blocks)
+    std::unique_ptr<FftFilter> af;        // the audio filter (real stream): tables, tile, the reference's nsamples
+    std::unique_ptr<FftFilter> af_small;  // the same on the next smaller tile, for calls of too few work items to fill the chip
+    int64_t I2 = 1, D2 = 1;
+    float scale;
+    uint64_t n1 = 0;                      // filtered audio-stage samples emitted so far (per channel)
+    size_t pend_len = 0, pstride = 0;     // demodulated samples carried (< nsamples); prefix row length
+    DevBuf<float> pre[2];                 // [C][hist + pend]
+    int cur = 0;
+    DevBuf<float> mid;                    // [C][mid_cap] demodulated samples of the current call (grows on demand)
+    size_t mid_cap = 0;
+    DevBuf<float> rev_f;                  // the audio taps reversed (non-finite pass)
+    DevBuf<int> slots;                    // [C][6]
+    bool nf_on = false;
+    int nf_seq = 1;
+    FmReceiver(const rr_c32* rf_taps, size_t nchan, size_t rf_ntaps, size_t rf_interp, size_t rf_deci, float gain, int mode,
+               const float* audio_taps, size_t audio_ntaps, size_t audio_interp, size_t audio_deci, float scale, bool iq8);
+    size_t out_windows() const override { return C; }
+    uint64_t audio_after(uint64_t rf_blocks) const;     // A(k): audio samples per channel after k RF filter blocks
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+};
+// ... and what the fused kernels do not cover (FastFM, more than 3584 audio taps, RF shapes beyond FmMulti): make_fm_multi(...)
+// feeding one make_audio_chain(...) per channel through C device-resident links of the reference's stream capacity — a
+// Series whose links are C wide.  Same whole-stream output; the window protocol is the composition's own.
+struct FmReceiverUnfused : Block {
+    size_t C;
+    std::unique_ptr<Block> rf;
+    std::vector<std::unique_ptr<Block>> audio;
+    DevBuf<float> link[2], scratch;       // [C][cap]
+    int cur = 0;
+    size_t cap = 0, len = 0;
+    FmReceiverUnfused(std::unique_ptr<Block> rf, std::vector<std::unique_ptr<Block>> audio, bool iq8);
+    size_t out_windows() const override { return C; }
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+    bool eof(bool src_eof) override;
+};
+
 struct FftFilterFloat : Block {
     std::unique_ptr<FftFilter> inner;
     size_t cap = 0;
@@ -525,6 +571,9 @@ Block* make_fm_multi(const rr_c32* taps, size_t nchan, size_t ntaps, size_t inte
 Block* make_audio_chain(const float* taps, size_t ntaps, size_t interp, size_t deci, float scale);
 // rr_channelizer*_create: FmMulti(cplx) where its kernels reach, else N x Series(FftFilter, RationalResampler) in a Parallel
 Block* make_channelizer(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci, bool u8);
+// rr_fm_receiver*_create: FmReceiver where its kernels reach, else FmReceiverUnfused
+Block* make_fm_receiver(const rr_c32* rf_taps, size_t nchan, size_t rf_ntaps, size_t rf_interp, size_t rf_deci, float gain, int mode,
+                        const float* audio_taps, size_t audio_ntaps, size_t audio_interp, size_t audio_deci, float scale, bool u8);
 
 struct Hilbert : Block {
     FirPlan pl;

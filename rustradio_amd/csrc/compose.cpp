@@ -252,6 +252,95 @@ Block* make_channelizer(const rr_c32* taps, size_t nchan, size_t ntaps, size_t i
                            : "Tee>N x (FftFilter>RationalResampler) (per channel)", std::move(ch));
 }
 
+// ---- the N-station receiver beyond its fused kernels: a Series of two stages whose link is C windows wide ----------------
+FmReceiverUnfused::FmReceiverUnfused(std::unique_ptr<Block> r, std::vector<std::unique_ptr<Block>> a, bool u8)
+    : Block(u8 ? "RtlSdrDecode>Tee>N x (chain>audio chain) (unfused)" : "Tee>N x (chain>audio chain) (unfused)", u8 ? 1 : 8, 4),
+      C(a.size()), rf(std::move(r)), audio(std::move(a)) {
+    if (rf->out_windows() != C || rf->out_es != sizeof(float)) throw Error("FmReceiver: stages do not fit");
+    zero_copy_in = false;
+    cap = 4096000 / sizeof(float);                                    // stream.rs:105,336-339
+    for (auto& b : link) b.reserve(C * cap);
+    scratch.reserve(C * cap);
+}
+
+int FmReceiverUnfused::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed, size_t* produced,
+                                size_t* need, hipStream_t s) {
+    *consumed = *produced = *need = 0;
+    int st_rf = RR_AGAIN, st_au = RR_AGAIN;
+    size_t need_rf = 0, need_au = 0;
+    float* o = static_cast<float*>(out);
+    // rounds of one work() per stage until a round moves nothing (Series::work_dev with C-wide windows)
+    for (int round = 0; round < 1 << 20; round++) {
+        bool progress = false;
+        {   // stage 1 writes C windows `room` apart: through the scratch windows, then behind what each link row holds
+            const size_t room = cap - len;
+            size_t c = 0, p = 0;
+            st_rf = rf->work_dev(static_cast<const unsigned char*>(in) + *consumed * in_es, in_len - *consumed, scratch.p, room, &c, &p,
+                                 &need_rf, s);
+            if (st_rf == RR_ERR) return st_rf;
+            if (p) RR_HIP(hipMemcpy2DAsync(link[cur].p + len, cap * sizeof(float), scratch.p, room * sizeof(float), p * sizeof(float), C,
+                                           hipMemcpyDeviceToDevice, s));
+            *consumed += c;
+            len += p;
+            if (c || p) progress = true;
+        }
+        {   // stage 2: the channels are of one shape, so their counts agree
+            const size_t room = out_cap - *produced;
+            size_t c0 = 0, p0 = 0;
+            for (size_t ch = 0; ch < C; ch++) {
+                size_t c = 0, p = 0, nd = 0;
+                const int st = audio[ch]->work_dev(link[cur].p + ch * cap, len, o + ch * out_cap + *produced, room, &c, &p, &nd, s);
+                if (st == RR_ERR) return st;
+                if (ch == 0) { st_au = st; c0 = c; p0 = p; need_au = nd; }
+                else if (st != st_au || c != c0 || p != p0 || nd != need_au) throw Error("FmReceiver: channels of one shape disagree on the window protocol");
+            }
+            if (c0) {
+                const size_t left = len - c0;
+                if (left) RR_HIP(hipMemcpy2DAsync(link[cur ^ 1].p, cap * sizeof(float), link[cur].p + c0, cap * sizeof(float),
+                                                  left * sizeof(float), C, hipMemcpyDeviceToDevice, s));
+                cur ^= 1;
+                len = left;
+            }
+            *produced += p0;
+            if (c0 || p0) progress = true;
+        }
+        if (!progress) break;
+    }
+    if (st_au == RR_WAIT_DST) { *need = need_au; return RR_WAIT_DST; }
+    if (st_rf == RR_WAIT_SRC) { *need = need_rf; return RR_WAIT_SRC; }
+    if (*consumed == 0 && *produced == 0)
+        throw Error("FmReceiver: the inner streams can hold neither what stage 1 must emit at once nor what stage 2 needs");
+    return RR_AGAIN;
+}
+
+bool FmReceiverUnfused::eof(bool src_eof) {
+    const bool e1 = rf->eof(src_eof) && len == 0;
+    bool e = true;
+    for (auto& a : audio) e = a->eof(e1) && e;
+    return e;
+}
+
+Block* make_fm_receiver(const rr_c32* rf_taps, size_t nchan, size_t rf_ntaps, size_t rf_interp, size_t rf_deci, float gain, int mode,
+                        const float* audio_taps, size_t audio_ntaps, size_t audio_interp, size_t audio_deci, float scale, bool u8) {
+    if (rf_deci == 0 || audio_deci == 0) throw Error("RationalResampler created using deci 0");
+    if (rf_interp == 0 || audio_interp == 0) throw Error("RationalResampler created using interp 0");
+    if (nchan == 0 || nchan > 4096) throw Error("FmReceiver: channel count must be 1..4096");
+    if (rf_ntaps == 0) throw Error("FftFilter: empty taps");
+    if (audio_ntaps == 0) throw Error("FftFilterFloat: empty taps");
+    if (!rf_taps || !audio_taps) throw Error("FmReceiver: null taps");
+    if (mode != RR_DEMOD_FASTFM) {
+        try {
+            return new FmReceiver(rf_taps, nchan, rf_ntaps, rf_interp, rf_deci, gain, mode, audio_taps, audio_ntaps, audio_interp,
+                                  audio_deci, scale, u8);
+        } catch (const NotFusedShape&) {
+        }
+    }
+    std::unique_ptr<Block> rf(make_fm_multi(rf_taps, nchan, rf_ntaps, rf_interp, rf_deci, gain, mode, u8));
+    std::vector<std::unique_ptr<Block>> au;
+    for (size_t c = 0; c < nchan; c++) au.emplace_back(make_audio_chain(audio_taps, audio_ntaps, audio_interp, audio_deci, scale));
+    return new FmReceiverUnfused(std::move(rf), std::move(au), u8);
+}
+
 Block* make_audio_chain(const float* taps, size_t ntaps, size_t interp, size_t deci, float scale) {
     try {
         return new AudioChain(taps, ntaps, interp, deci, scale);

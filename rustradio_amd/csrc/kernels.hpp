@@ -40,6 +40,16 @@ struct AudioChainArgs {
 };
 void launch_audio_chain(int log2f, VSrc<float> src, float* out, int L, const cf* tw, const cf* hpos, const AudioChainArgs& a,
                         hipStream_t s);
+// The same for C streams of one shape in ONE launch (k_audio_multi, the audio half of rr_fm_receiver_create): stream c is
+// VSrc<float>{prefix + c * pstride, plen, in + c * in_stride, in_len}, writes out + c * out_stride, and a.carry.dst is the
+// base of C carry prefixes pstride apart.  One filter (tw, hpos) for all streams; the work items are (stream, tile) pairs.
+struct AudioMultiSrc {
+    const float* prefix; long plen, pstride;
+    const float* in; long in_len, in_stride;
+};
+bool audio_multi_supported(int log2f);
+void launch_audio_multi(int log2f, const AudioMultiSrc& src, int C, float* out, long out_stride, int L, const cf* tw, const cf* hpos,
+                        const AudioChainArgs& a, hipStream_t s);
 
 // Decimation by D = F / 256 (4 / 8 / 16 on tiles of 1024 / 2048 / 4096 points) with a pruned inverse transform
 // (k_fftfilt_prune): out[m] = y[m D], m < n_out.  Tables (see the kernel): hpos2 = H in position order with the
@@ -223,6 +233,9 @@ void launch_chain_blocks_nonfinite(VSrc<cf> src, float* out, long out_stride, in
                                    hipStream_t s);
 void launch_chain_blocks_nonfinite(VSrc<float> src, float* out, const AudioChainArgs& a, long S, long hist, long P, int L,
                                    const float* rev, int* slots, int seq, hipStream_t s);
+// ... C audio streams of one shape (launch_audio_multi): the stream in the grid, slots = int[C][6], one set of reversed taps
+void launch_audio_multi_blocks_nonfinite(const AudioMultiSrc& src, int C, float* out, long out_stride, const AudioChainArgs& a, long S,
+                                         long hist, long P, int L, const float* rev, int* slots, int seq, hipStream_t s);
 // ... and the channelizer's Complex outputs (out[u - r_lo] = r[u] per channel)
 void launch_chan_blocks_nonfinite(VSrc<cf> src, cf* out, long out_stride, int nchan, const FmChainArgs& a, long S, long hist, long P,
                                   int L, const cf* rev, long rev_stride, int* slots, int seq, hipStream_t s);

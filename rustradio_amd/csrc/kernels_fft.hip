@@ -1413,6 +1413,117 @@ void launch_audio_chain(int log2f, VSrc<float> src, float* out, int L, const cf*
     }
 }
 
+// ---- C audio chains of one shape in ONE launch (the audio half of rr_fm_receiver_create; examples/rtl_fm.rs:398-418 behind
+// every branch of a Tee) ----
+// k_audio_chain's tile, unchanged — the same TileXform, the same segment pairing, the same un-contracted scale — with the
+// persistent tile walk running over ntiles x C work items, stream-major: item w is tile w % ntiles of stream w / ntiles, so
+// the items of one XCD's share are whole runs of neighbouring tiles of a few streams (the L - 1 samples two tiles share stay
+// in that XCD's L2) and a window of 70 tiles per stream still fills the chip at 32 streams.  Stream c of the launch computes
+// bit for bit what k_audio_chain computes on the same window and tile size.  The twiddle and response tables are shared
+// (X.init once per workgroup).  The carry of every stream is written by this launch: element i of the C x carry.n it
+// moves belongs to stream i / carry.n.
+struct AudioMultiArgs {
+    const float* prefix; long plen, pstride;
+    const float* in; long in_len, in_stride;
+    long out_stride;
+    int C;
+};
+template <int LOG2F>
+__global__ __launch_bounds__((KCfg<LOG2F, 0>::T), (KCfg<LOG2F, 0>::WAVES_PER_SIMD))
+void k_audio_multi(AudioMultiArgs m, float* __restrict__ out_all, int L, long ntiles, const cf* __restrict__ tw,
+                   const cf* __restrict__ hpos, AudioArgs a) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.carry.n * m.C; i += (long)gridDim.x * blockDim.x) {
+        const long c = i / a.carry.n, j = i - c * a.carry.n;
+        const VSrc<float> sc{m.prefix + c * m.pstride, m.plen, m.in + c * m.in_stride, m.in_len};
+        static_cast<float*>(a.carry.dst)[c * m.pstride + j] = sc.load(a.carry.v0 + j);
+    }
+    constexpr int F = 1 << LOG2F;
+    constexpr int T = F / 16;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    creg* lds = reinterpret_cast<creg*>(smem_raw);
+    float* ybuf = reinterpret_cast<float*>(smem_raw);    // 2 S filtered samples in stream order (after the transform)
+    const int t = threadIdx.x;
+    const long S = F - L + 1;
+    const int first = L - 1;
+    const long qs = ((long)T * a.D) / a.I, rs = ((long)T * a.D) % a.I;      // SrcWalk step of T outputs
+    TileXform<LOG2F, 0> X;
+    X.init(t, tw, hpos);
+    for (TileIter it(ntiles * m.C); it.tile < it.end; it.tile += it.step) {
+        const long c = it.tile / ntiles, tile = it.tile - c * ntiles;
+        const VSrc<float> src{m.prefix + c * m.pstride, m.plen, m.in + c * m.in_stride, m.in_len};
+        float* __restrict__ out = out_all + c * m.out_stride;
+        const long va = 2 * tile * S, vb = va + S;          // virtual index of position 0 of the two segments
+        creg v[16];
+        if (va >= src.plen && vb - src.plen + F <= src.in_len) {
+            const float* pa = src.in + (va - src.plen) + t;
+#pragma unroll
+            for (int n = 0; n < 16; n++) v[n] = mk(pa[n * T], pa[S + n * T]);
+        } else {
+            stage_pair_slow<T>(lds, src, va, vb, t);
+            tile_sync<T>();
+            lds_load<LOG2F, 0>(v, t, lds);
+        }
+        RR_PHASE();
+        X.run(v, lds, 0, nullptr);
+        tile_sync<T>();                                      // the last exchange is read everywhere
+#pragma unroll
+        for (int n = 0; n < 16; n++) {
+            const int p = n * T + t - first;                 // y_rel[va + p] (segment a), y_rel[vb + p] (segment b)
+            if (p >= 0) { ybuf[p] = v[n].x; ybuf[S + p] = v[n].y; }
+        }
+        tile_sync<T>();
+        // resampled samples with their source in [va, min(va + 2 S, n_y)) (relative to A)
+        const long y_lo = va, y_hi = min(va + 2 * S, a.n_y);
+        long u_lo = ((a.A + y_lo) * a.I + a.D - 1) / a.D;
+        long u_hi = ((a.A + y_hi) * a.I + a.D - 1) / a.D;
+        if (u_lo < a.r_lo) u_lo = a.r_lo;
+        if (u_hi > a.r_hi) u_hi = a.r_hi;
+        SrcWalk wu;
+        wu.init(u_lo + t, a.I, a.D);
+        for (long u = u_lo + t; u < u_hi; u += T, wu.step(qs, rs, a.I))
+            out[u - a.r_lo] = mul_rn(a.scale, ybuf[wu.q - a.A - va]);
+        tile_sync<T>();                                      // before the next tile's exchanges overwrite ybuf
+    }
+}
+// the carries alone (a call that filters nothing: the windows only join the pending samples)
+__global__ __launch_bounds__(256) void k_audio_multi_carry(AudioMultiArgs m, CarryOut carry) {
+    const long c = blockIdx.y;
+    const VSrc<float> sc{m.prefix + c * m.pstride, m.plen, m.in + c * m.in_stride, m.in_len};
+    for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < carry.n; j += (long)gridDim.x * blockDim.x)
+        static_cast<float*>(carry.dst)[c * m.pstride + j] = sc.load(carry.v0 + j);
+}
+template <int LOG2F>
+static void launch_audio_multi_one(const AudioMultiArgs& m, float* out, int L, const cf* tw, const cf* hpos, const AudioChainArgs& h,
+                                   hipStream_t s) {
+    constexpr int F = 1 << LOG2F, T = F / 16;
+    const long S = F - L + 1;
+    const long ntiles = (h.n_y + 2 * S - 1) / (2 * S);
+    AudioArgs a{h.A, h.n_y, h.r_lo, h.r_hi, h.I, h.D, h.scale, h.carry};
+    const size_t smem = sizeof(cf) * lds_elems(F);
+    const long grid = grid_for_tiles(k_audio_multi<LOG2F>, T, smem, ntiles * m.C);
+    hipLaunchKernelGGL((k_audio_multi<LOG2F>), dim3((unsigned)grid), dim3(T), smem, s, m, out, L, ntiles, tw, hpos, a);
+    RR_HIP(hipGetLastError());
+}
+bool audio_multi_supported(int log2f) { return log2f >= 10 && log2f <= 12; }
+void launch_audio_multi(int log2f, const AudioMultiSrc& src, int C, float* out, long out_stride, int L, const cf* tw, const cf* hpos,
+                        const AudioChainArgs& a, hipStream_t s) {
+    if (C <= 0) return;
+    const AudioMultiArgs m{src.prefix, src.plen, src.pstride, src.in, src.in_len, src.in_stride, out_stride, C};
+    if (a.n_y <= 0) {
+        if (a.carry.n <= 0) return;
+        const unsigned gx = (unsigned)std::min<long>((a.carry.n + 255) / 256, 64);
+        hipLaunchKernelGGL(k_audio_multi_carry, dim3(gx, (unsigned)C), dim3(256), 0, s, m, a.carry);
+        RR_HIP(hipGetLastError());
+        return;
+    }
+    switch (log2f) {
+    case 10: launch_audio_multi_one<10>(m, out, L, tw, hpos, a, s); break;
+    case 11: launch_audio_multi_one<11>(m, out, L, tw, hpos, a, s); break;
+    case 12: launch_audio_multi_one<12>(m, out, L, tw, hpos, a, s); break;
+    default: throw Error("audio_multi: unsupported tile size");
+    }
+}
+
 // Tile j transforms y[A + j*Sp - G .. + S') and owns every demod output o[u-1] whose UPPER
 // sample r[u] has its source in [A + j*Sp, A + (j+1)*Sp), Sp = S' - G; the lower sample r[u-1]
 // then lies in the same tile — or is the last r of the previous call (`last_r`).

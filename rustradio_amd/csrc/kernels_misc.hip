@@ -356,19 +356,23 @@ struct ChainBlocksCtx {
     long nb, bpw;                                                    // blocks of the call, blocks per workgroup
     int force;                                                       // 1: block 0 regardless (head fix), 2: every block (a call without outputs)
     int sparse;                                                      // ceil(D / I) > S: at most one output per reference block
+    long pstride, in_stride;                                         // PERCH (C audio streams): stream c reads prefix + c * pstride, in + c * in_stride
 };
 __device__ __forceinline__ long chain_n2(long y, long I, long D) { return (long)(((__int128)y * I + D - 1) / D); }   // first r index whose source is >= y
 // O: the output type — float (FM / audio chains) or cf (the channelizer, rr_channelizer_create: T = cf, no demodulator; an
 // output is NaN iff the filtered sample it IS lies in a poisoned stretch, a smeared one is refolded with nf_fold_cc)
-template <class T, bool DEMOD, bool WIDE, class O>
+// PERCH: every channel row is a stream of its own (launch_audio_multi_blocks_nonfinite) — its own window, its own six slots
+template <class T, bool DEMOD, bool WIDE, class O, bool PERCH = false>
 __device__ __forceinline__ void chain_blocks_body(const ChainBlocksCtx& c) {
-    const VSrc<T> src{static_cast<const T*>(c.prefix), c.plen, static_cast<const T*>(c.in), c.in_len};
     const int ch = (int)blockIdx.y;
+    const VSrc<T> src{static_cast<const T*>(c.prefix) + (PERCH ? (long)ch * c.pstride : 0), c.plen,
+                      static_cast<const T*>(c.in) + (PERCH ? (long)ch * c.in_stride : 0), c.in_len};
+    int* const slots = c.slots + (PERCH ? 6 * ch : 0);
     O* out = reinterpret_cast<O*>(c.out) + (long)ch * c.out_stride;
     const long b0 = (long)blockIdx.x * c.bpw, b1 = b0 + c.bpw < c.nb ? b0 + c.bpw : c.nb;
     if (b0 >= b1) return;
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, nw = (int)(blockDim.x >> 6);
-    auto slot = [&](int k) { return c.slots[2 * k + ((c.seq - 1) & 1)] == c.seq - 1; };
+    auto slot = [&](int k) { return slots[2 * k + ((c.seq - 1) & 1)] == c.seq - 1; };
     const bool tail1 = slot(0), tail2 = slot(1), lastr = slot(2);
     // outputs: index o <-> u = o + o_base + (DEMOD ? 1 : 0), the newest filtered sample it reads is y[floor(u D / I)]
     // (WIDE: stream positions times the ratio beyond 2^62 — 128-bit products; otherwise plain 64-bit divisions: the 128-bit
@@ -547,12 +551,12 @@ __device__ __forceinline__ void chain_blocks_body(const ChainBlocksCtx& c) {
                 else if (nf_bad(*lo)) *lo = nf_fold_cc(src, static_cast<const cf*>(c.rev) + (long)ch * c.rev_stride, c.L, yl);
             }
         }
-        if (last && ch == 0 && lane == 0) {                          // what the next call needs (every channel would write the same)
-            c.slots[0 + (c.seq & 1)] = bad0 ? c.seq : -1;
-            c.slots[2 + (c.seq & 1)] = bad1 ? c.seq : -1;
+        if (last && (PERCH || ch == 0) && lane == 0) {               // what the next call needs (every channel would write the same)
+            slots[0 + (c.seq & 1)] = bad0 ? c.seq : -1;
+            slots[2 + (c.seq & 1)] = bad1 ? c.seq : -1;
             long ylast = -1;                                         // the filtered sample the carried r[r_hi - 1] is
             if (c.r_hi > c.r_lo) ylast = src_of(c.r_hi - 1) - c.A;
-            c.slots[4 + (c.seq & 1)] = (c.r_hi > c.r_lo ? (sparse ? carried_bad : poisoned(ylast)) : lastr) ? c.seq : -1;
+            slots[4 + (c.seq & 1)] = (c.r_hi > c.r_lo ? (sparse ? carried_bad : poisoned(ylast)) : lastr) ? c.seq : -1;
         }
     }
 }
@@ -560,7 +564,9 @@ template <class T, bool DEMOD, bool WIDE>
 __global__ __launch_bounds__(256) void k_chain_blocks_nonfinite(ChainBlocksCtx c) { chain_blocks_body<T, DEMOD, WIDE, float>(c); }
 template <bool WIDE>
 __global__ __launch_bounds__(256) void k_chan_blocks_nonfinite(ChainBlocksCtx c) { chain_blocks_body<cf, false, WIDE, cf>(c); }
-template <class T, bool DEMOD, bool CX = false>
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_audio_multi_blocks_nonfinite(ChainBlocksCtx c) { chain_blocks_body<float, false, WIDE, float, true>(c); }
+template <class T, bool DEMOD, bool CX = false, bool PERCH = false>
 static void launch_chain_blocks(ChainBlocksCtx c, hipStream_t s) {
     if (c.n_y <= 0 || c.nchan <= 0) return;
     c.nb = c.n_y / c.S;
@@ -575,7 +581,10 @@ static void launch_chain_blocks(ChainBlocksCtx c, hipStream_t s) {
     const long gx = (c.nb + c.bpw - 1) / c.bpw;
     const __int128 lim = (__int128)1 << 62;
     const bool wide = (__int128)(c.A + c.n_y + 1) * c.I >= lim || (__int128)(c.r_hi + 1) * c.D >= lim;
-    if constexpr (CX) {
+    if constexpr (PERCH) {
+        if (wide) hipLaunchKernelGGL((k_audio_multi_blocks_nonfinite<true>), dim3((unsigned)gx, (unsigned)c.nchan), dim3(256), 0, s, c);
+        else hipLaunchKernelGGL((k_audio_multi_blocks_nonfinite<false>), dim3((unsigned)gx, (unsigned)c.nchan), dim3(256), 0, s, c);
+    } else if constexpr (CX) {
         if (wide) hipLaunchKernelGGL((k_chan_blocks_nonfinite<true>), dim3((unsigned)gx, (unsigned)c.nchan), dim3(256), 0, s, c);
         else hipLaunchKernelGGL((k_chan_blocks_nonfinite<false>), dim3((unsigned)gx, (unsigned)c.nchan), dim3(256), 0, s, c);
     } else if (wide) hipLaunchKernelGGL((k_chain_blocks_nonfinite<T, DEMOD, true>), dim3((unsigned)gx, (unsigned)c.nchan), dim3(256), 0, s, c);
@@ -600,6 +609,12 @@ void launch_chain_blocks_nonfinite(VSrc<float> src, float* out, const AudioChain
     ChainBlocksCtx c{src.prefix, src.plen, src.in, src.in_len, out, 0, 1, a.A, a.n_y, a.r_lo, a.r_hi, a.r_lo, a.I, a.D,
                      S, hist, P, L, 0, rev, 0, a.scale, 0, nullptr, nullptr, slots, seq, 0, 0, 0, 0};
     launch_chain_blocks<float, false>(c, s);
+}
+void launch_audio_multi_blocks_nonfinite(const AudioMultiSrc& src, int C, float* out, long out_stride, const AudioChainArgs& a, long S,
+                                         long hist, long P, int L, const float* rev, int* slots, int seq, hipStream_t s) {
+    ChainBlocksCtx c{src.prefix, src.plen, src.in, src.in_len, out, out_stride, C, a.A, a.n_y, a.r_lo, a.r_hi, a.r_lo, a.I, a.D,
+                     S, hist, P, L, 0, rev, 0, a.scale, 0, nullptr, nullptr, slots, seq, 0, 0, 0, 0, src.pstride, src.in_stride};
+    launch_chain_blocks<float, false, false, true>(c, s);
 }
 
 // ---- Hilbert on transform tiles: the reference's locality for non-finite samples (round 5) -------------------

@@ -859,6 +859,62 @@ inline auto AudioChain(ReadStream<Float> src, const std::vector<Float>& taps, si
     return Fused<Float, Float>::make(std::move(src), [&] { return rr_audio_chain_create(taps.data(), taps.size(), interp, deci, scale); });
 }
 
+// The N-station FM receiver down to audio (rr_fm_receiver_create): Tee (src/tee.rs:10-24) + N x the six blocks of
+// examples/rtl_fm.rs:381-419 on ONE input, N audio streams.  The C ABI takes the N output windows as one buffer of N x out_cap
+// elements, so the block stages them in `scratch_` and copies each channel into its own (host) stream; the resamplers drop tags.
+class FmReceiver : public Block {
+    detail::Handle h_;
+    ReadStream<Complex> src_;
+    std::vector<WriteStream<Float>> dsts_;
+    std::vector<Float> scratch_;
+public:
+    FmReceiver(rr_block* h, ReadStream<Complex> src, std::vector<WriteStream<Float>> dsts)
+        : h_(h), src_(std::move(src)), dsts_(std::move(dsts)) {}
+    // rf_taps[c] = channel c's RF filter (all of one length); audio_taps is shared by the channels, as in rtl_fm
+    static std::pair<std::unique_ptr<FmReceiver>, std::vector<ReadStream<Float>>> new_(
+        ReadStream<Complex> src, const std::vector<std::vector<Complex>>& rf_taps, size_t rf_interp, size_t rf_deci, Float gain,
+        const std::vector<Float>& audio_taps, size_t audio_interp, size_t audio_deci, Float scale, bool exact_atan2 = true) {
+        const size_t nchan = rf_taps.size(), ntaps = nchan ? rf_taps[0].size() : 0;
+        std::vector<Complex> flat;
+        for (auto& t : rf_taps) {
+            if (t.size() != ntaps) throw Error("FmReceiver: all channels need the same number of taps");
+            flat.insert(flat.end(), t.begin(), t.end());
+        }
+        rr_block* h = rr_fm_receiver_create(c32(flat), nchan, ntaps, rf_interp, rf_deci, gain, exact_atan2 ? RR_ATAN2_EXACT : RR_ATAN2_FAST,
+                                            audio_taps.data(), audio_taps.size(), audio_interp, audio_deci, scale);
+        std::vector<WriteStream<Float>> ws;
+        std::vector<ReadStream<Float>> rs;
+        for (size_t c = 0; c < nchan; c++) {
+            auto [w, r] = new_stream<Float>();
+            ws.push_back(std::move(w));
+            rs.push_back(std::move(r));
+        }
+        return {std::make_unique<FmReceiver>(h, std::move(src), std::move(ws)), std::move(rs)};
+    }
+    const char* block_name() const override { return rr_block_name(h_.h); }
+    bool eof() override { return rr_block_eof(h_.h, src_.eof()) != 0; }
+    BlockRet work() override {
+        auto [input, tags] = src_.read_buf();
+        (void)tags;
+        std::vector<BufferWriter<Float>> outs;
+        size_t cap = ~(size_t)0;
+        for (auto& d : dsts_) {
+            outs.push_back(d.write_buf());
+            if (outs.back().device() || input.device()) throw Error("FmReceiver: host streams only (N output windows are one buffer in the C ABI)");
+            cap = std::min(cap, outs.back().len());
+        }
+        scratch_.resize(dsts_.size() * std::max<size_t>(cap, 1));
+        auto w = detail::work(h_.h, input.slice(), input.len(), scratch_.data(), cap);
+        for (size_t c = 0; c < outs.size(); c++) {
+            outs[c].fill_from_slice(scratch_.data() + c * cap, w.produced);
+            outs[c].produce(w.produced, {});
+        }
+        input.consume(w.consumed);
+        if (w.st == RR_AGAIN) return BlockRet::again();
+        return w.st == RR_WAIT_DST ? BlockRet::wait(dsts_[0].wait_handle(), w.need) : BlockRet::wait(src_.wait_handle(), w.need);
+    }
+};
+
 // ---- Hilbert (src/hilbert.rs) ----------------------------------------------------------------------------------------------
 class Hilbert : public Block {
     detail::Handle h_;
