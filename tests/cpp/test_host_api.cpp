@@ -681,10 +681,98 @@ static void tee_and_memcopy_between_device_rings() {
     CHECK(!ta->empty() && (*ta)[0].pos() == 0);       // VectorSource::start travels through every copy
 }
 
+// FmReceiver (rr_fm_receiver_create) under the mirror's Graph with N sinks, every channel with an FM station of its own (centres at
+// integer multiples of the channel rate: the shifted taps select without translating, so only those fold to DC).  Stream
+// lengths are the protocol model's, A(K) = ceil(floor(d(K S1) / S2) S2 I2 / D2) with d(y) = ceil(y / D1) - 1; every channel lies
+// within 1e-5 max|ref| of the composition on the same input: rr_fm_multi_create driven through the C ABI in one call (the mirror
+// has no class for it), then the mirror's AudioChain per channel under its own Graph.
+static void fm_receiver_under_graph() {
+    const size_t nchan = 4, deci = 10, n = 400000, ai = 2, ad = 3;
+    const double fs = 1e6, rate = fs / (double)deci;
+    std::vector<Complex> x(n);
+    uint64_t st = 4242;
+    auto rnd = [&] { st = st * 6364136223846793005ULL + 1442695040888963407ULL; return (float)((st >> 40) / 8388608.0 - 1.0); };
+    std::vector<double> ph(nchan, 0.0), centre(nchan);
+    for (size_t c = 0; c < nchan; c++) centre[c] = ((double)c - (double)(nchan / 2)) * rate;
+    for (size_t i = 0; i < n; i++) {
+        std::complex<double> acc(1e-3 * rnd(), 1e-3 * rnd());
+        for (size_t c = 0; c < nchan; c++) {
+            const double dev = (0.17 + 0.01 * (double)c) * rate, tone = (0.004 + 0.0031 * (double)c) * rate;
+            ph[c] += 2.0 * M_PI * (centre[c] + dev * std::sin(2.0 * M_PI * tone * (double)i / fs)) / fs;
+            acc += std::polar(1.0 / (double)nchan, ph[c]);
+        }
+        x[i] = Complex((float)acc.real(), (float)acc.imag());
+    }
+    auto proto = fir::low_pass_complex((float)fs, (float)(0.35 * rate), (float)(0.15 * rate), WindowType::Hamming());
+    std::vector<std::vector<Complex>> rf(nchan, std::vector<Complex>(proto.size()));
+    std::vector<Complex> flat;
+    for (size_t c = 0; c < nchan; c++) {
+        for (size_t k = 0; k < proto.size(); k++) {
+            const double a = 2.0 * M_PI * centre[c] * (double)k / fs;
+            rf[c][k] = Complex((float)(proto[k].real() * std::cos(a)), (float)(proto[k].real() * std::sin(a)));
+        }
+        flat.insert(flat.end(), rf[c].begin(), rf[c].end());
+    }
+    auto ta = fir::low_pass((float)rate, (float)(0.12 * rate), (float)(0.08 * rate), WindowType::Hamming());
+    CHECK(proto.size() > 100 && proto.size() < 256 && ta.size() > 16 && ta.size() < 128);
+    auto block_len = [](size_t ntaps) { size_t f = 1; while (f < ntaps) f <<= 1; return 2 * f - ntaps; };   // fft_filter.rs:36-42, 261-262
+    const size_t S1 = block_len(proto.size()), S2 = block_len(ta.size()), K = n / S1;
+    const size_t d = (K * S1 + deci - 1) / deci - 1, want = ((d / S2 * S2) * ai + ad - 1) / ad;
+    // the receiver under Graph
+    std::vector<std::shared_ptr<std::vector<Float>>> got;
+    {
+        auto [src, s0] = VectorSource<Complex>::new_(x);
+        auto [rx, outs] = FmReceiver::new_(std::move(s0), rf, 1, deci, 1.0f, ta, ai, ad, -1.5f);
+        CHECK(std::string(rx->block_name()).find("unfused") == std::string::npos);
+        Graph g;
+        g.add(std::move(src)); g.add(std::move(rx));
+        for (auto& o : outs) {
+            auto sink = std::make_unique<VectorSink<Float>>(std::move(o));
+            got.push_back(sink->hook());
+            g.add(std::move(sink));
+        }
+        g.run();
+    }
+    CHECK(got.size() == nchan);
+    // the composition: rr_fm_multi_create in one call, then one AudioChain per channel
+    std::vector<Float> dm(nchan * n);
+    size_t p1 = 0;
+    {
+        detail::Handle h(rr_fm_multi_create(c32(flat), nchan, proto.size(), 1, deci, 1.0f, RR_ATAN2_EXACT));
+        auto w = detail::work(h.h, x.data(), n, dm.data(), n);
+        CHECK(w.consumed == n && w.produced == d);        // (all input taken: what is short of an RF block is carried)
+        p1 = w.produced;
+    }
+    std::vector<std::vector<Float>> ref;
+    for (size_t c = 0; c < nchan; c++) {
+        auto [src, s0] = VectorSource<Float>::new_(std::vector<Float>(dm.begin() + c * n, dm.begin() + c * n + p1));
+        auto [b, s1] = AudioChain(std::move(s0), ta, ai, ad, -1.5f);
+        auto sink = std::make_unique<VectorSink<Float>>(std::move(s1));
+        auto hook = sink->hook();
+        Graph g;
+        g.add(std::move(src)); g.add(std::move(b)); g.add(std::move(sink));
+        g.run();
+        ref.push_back(*hook);
+    }
+    for (size_t c = 0; c < nchan; c++) {
+        CHECK(got[c]->size() == want && ref[c].size() == want && want > 20000);
+        CHECK(max_rel(*got[c], ref[c]) <= 1e-5);
+        // ... and the stations differ: behind the start-up, another channel's audio is nowhere near
+        const size_t o = (c + 1) % nchan;
+        double far = 0, big = 0;
+        for (size_t i = want / 10; i < std::min(ref[c].size(), ref[o].size()); i++) {
+            far = std::max(far, (double)std::fabs(ref[c][i] - ref[o][i]));
+            big = std::max(big, (double)std::fabs(ref[c][i]));
+        }
+        CHECK(big > 0.5 && far > 0.5 * big);
+        CHECK(max_rel(*got[c], ref[o]) > 0.1);
+    }
+}
+
 int main() {
     test_complex(); test_identity(); moving_avg(); translate_matches_mixed_input(); test_filter_generator();
     fft_tag_propagation(); resampler_examples(); quad_known(); rtlsdr_decode_tests(); hilbert_rejects_even(); graph_fm_chain();
-    fft_filter_resampler_against_the_definition();
+    fft_filter_resampler_against_the_definition(); fm_receiver_under_graph();
     device_resident_graph(); fused_blocks_equal_their_chains(); fanout_from_c_abi(); fft_message_block(); tee_and_signal_source(); tee_and_memcopy_between_device_rings(); sync_blocks(); fftstream_adds_frame_tags(); file_source_tests(); handles_on_concurrent_threads();
     printf(g_fail ? "FAILED (%d)\n" : "OK\n", g_fail);
     return g_fail ? 1 : 0;

@@ -1,5 +1,5 @@
 """Test-side statements about the N-station FM receiver (rr_fm_receiver_create): the window protocol as a Python model,
-the test signals and the conditions they must meet, the oracle chain of six blocks, the float64 truth of the whole chain and
+the test signals (one station for all channels, or one per channel) and the conditions they must meet, the oracle chain of six blocks, the float64 truth of the whole chain and
 the propagated parity bar.  Nothing here touches the GPU library; tests/test_fm_receiver_cpu.py checks these statements
 against the oracle, tests/test_gpu_fm_receiver.py holds the block to them."""
 from __future__ import annotations
@@ -156,6 +156,170 @@ def shape_small(rf_deci, audio_ntaps, audio, n=None, seed=7, nchan=3, mode=ATAN2
     return Shape(f"small-{rf_interp}:{rf_deci}-{audio_ntaps}-{audio[0]}:{audio[1]}", shifted(proto, fs, centres), (rf_interp, rf_deci),
                  sinc_low_pass(audio_ntaps, 0.2 * min(1.0, audio[0] / audio[1])), audio, -1.5, x,
                  len(proto) * rf_interp // rf_deci + 2, mode=mode)
+
+
+# ---- signals: one FM station OF ITS OWN per channel ---------------------------------------------------------------------
+def fm_stations(fs, n, station_hz, dev_hz, tone_hz, seed, noise=1e-3):
+    """station i at station_hz[i] with its own deviation dev_hz[i] and tone tone_hz[i], amplitudes 1 / len(station_hz), plus
+    complex noise of sigma `noise`"""
+    t = np.arange(n, dtype=np.float64)
+    r = np.random.default_rng(seed)
+    x = noise * (r.standard_normal(n) + 1j * r.standard_normal(n))
+    for f, dev, tone in zip(station_hz, dev_hz, tone_hz):
+        phi = 2 * np.pi * np.cumsum(f + dev * np.sin(2 * np.pi * tone * t / fs)) / fs
+        x += np.exp(1j * phi) / len(station_hz)
+    return x.astype(np.complex64)
+
+
+def shape_distinct(nchan, rf_deci, audio_ntaps=65, audio=(2, 3), fs=1e6, n=None, seed=11, transition=0.15, mode=ATAN2_EXACT, live=None):
+    """nchan channels, each with a station no other channel hears.  Integer decimation, rf_interp = 1: the channel rate is
+    fs / rf_deci.  The shifted taps select a band without translating it, so only centres at integer multiples of the channel
+    rate fold to DC behind the resampler: channel i sits at (i - nchan // 2) x rate (nchan <= rf_deci of them are distinct),
+    and station i sits on centre i with deviation (0.17 + 0.01 (i % 8)) rate and tone (0.004 + 0.0031 (i % 11)) rate — the
+    audio of two channels differs by thousands of bars (test_fm_receiver_cpu.py asserts at least 100 for every pair), so a
+    receiver that hands a channel any other channel's carry, history, row or verdict fails parity.  Smaller deviations
+    (0.10 - 0.22 rate) leave the bar of a channel with a small start-up spike above 10 x plain nearly everywhere.
+    The propagated term of the bar over the plain one is about 5 sum|audio_taps| / (peak angle), and sum|h| of a windowed sinc
+    grows with ntaps x cutoff (128 taps at 0.2: 2.1, 900 at 0.13: 2.8 — every sample above 10 x plain), so long audio filters
+    get the cutoff 8 / ntaps (sum|h| about 1.7) and the tones are slowed until the fastest lies at half the cutoff.
+    The stream holds 60 audio filter lengths per channel at least: the start-up stretch, where |r| is small and the bar wide,
+    stays below 2 % of the samples.  `transition` (of the rate) sets the prototype's tap count.  `live`: every channel's RF
+    taps but that one are zero (the silent-channel tests)."""
+    assert 1 <= nchan <= rf_deci, (nchan, rf_deci)
+    rate = fs / rf_deci
+    proto = orc.low_pass_complex(fs, 0.35 * rate, transition * rate)
+    centres = [(i - nchan // 2) * rate for i in range(nchan)]
+    n = n or int(rf_deci * max(8000, 60 * audio_ntaps))
+    cutoff = min(0.2 * min(1.0, audio[0] / audio[1]), 8.0 / audio_ntaps)
+    slow = min(1.0, cutoff / 0.07)
+    x = fm_stations(fs, n, centres, [(0.17 + 0.01 * (i % 8)) * rate for i in range(nchan)],
+                    [(0.004 + 0.0031 * (i % 11)) * slow * rate for i in range(nchan)], seed)
+    taps = shifted(proto, fs, centres)
+    if live is not None:
+        taps[[c for c in range(nchan) if c != live]] = 0
+    return Shape(f"distinct-{nchan}x1:{rf_deci}-{audio_ntaps}-{audio[0]}:{audio[1]}" + ("" if live is None else f"-live{live}"), taps,
+                 (1, rf_deci), sinc_low_pass(audio_ntaps, cutoff), audio, -1.5, x, len(proto) // rf_deci + 2, mode=mode)
+
+
+# the distinct-station signals of tests/test_gpu_fm_receiver.py by name: (channels, RF decimation, audio taps, audio ratio, keywords).
+# tests/test_fm_receiver_cpu.py holds every one of them to the signal conditions and to the separation of its channels.
+DISTINCT = {
+    "4x10": (4, 10, 65, (2, 3), {}),
+    "9x10": (9, 10, 65, (2, 3), {}),
+    "9x10-u8": (9, 10, 65, (2, 3), {}),
+    "5x5": (5, 5, 128, (7, 4), {}),
+    "32x40": (32, 40, 65, (2, 3), {}),
+    "5x6-2.4M": (5, 6, 241, (3, 25), dict(fs=2.4e6)),                          # 97 RF taps: the decimate-first tiles at 1:6
+    "5x6-2.4M-463": (5, 6, 241, (3, 25), dict(fs=2.4e6, transition=0.03125)),   # 463 RF taps, cfg4's count: every FmMulti family
+    "5x10-400": (5, 10, 400, (2, 3), {}),                                      # audio tile 2048 by cost, 1024 beside it
+    "9x10-400": (9, 10, 400, (2, 3), {}),
+    "9x10-900": (9, 10, 900, (2, 3), {}),                                      # audio tile 4096 by cost, 2048 beside it
+    "5x5-65": (5, 5, 65, (2, 3), {}),
+    "5x5-u8": (5, 5, 128, (7, 4), {}),
+    "9x10-400-u8": (9, 10, 400, (2, 3), {}),
+}
+STREAM_KINDS = ("mixed", "short-in", "tight-out")
+
+
+def distinct(key, **kw):
+    nchan, deci, ant, audio, k = DISTINCT[key]
+    return shape_distinct(nchan, deci, ant, audio, **dict(k, **kw))
+
+
+def fuzz_distinct(seed):
+    """the second fuzz family: a distinct-station shape, a source type and four windows drawn from the seed
+    -> (shape, u8, [(input window, output window)])"""
+    g = np.random.default_rng(7000 + seed)
+    nchan = int(g.choice([2, 3, 5, 9, 17]))
+    deci = int(g.choice([d for d in (2, 3, 5, 6, 8, 10, 25) if d >= nchan]))
+    ant = int(g.choice([1, 2, 17, 64, 65, 200, 511]))
+    audio = [(2, 3), (7, 4), (1, 1), (3, 25), (6, 25), (1, 4), (4, 2)][int(g.integers(0, 7))]
+    u8 = bool(g.integers(0, 2))
+    n = int(g.integers(50_000, 90_000))
+    n = max(n, 6 * nsamples(ant) * deci)                              # six audio blocks at least
+    sh = shape_distinct(nchan, deci, ant, audio, seed=100 + seed, n=n)
+    m = sh.model(u8)
+    S1 = m.S1 * (2 if u8 else 1)
+    step = max(max(m.A(k + 1) - m.A(k) for k in range(n // m.S1 + 1)), 1)
+    caps = [(int(g.integers(S1 // 3 + 1, 6 * S1)), int(g.integers(max(step // 2, 1), 5 * step + 2))) for _ in range(3)] + [(4 * S1 + 1, 3 * step + 1)]
+    return sh, u8, caps
+
+
+def stream_caps(m: ReceiverModel, kind, n):
+    """the windows of the streaming tests, (input, output) per call in turn: input windows shorter than one RF block, output
+    windows below the next step (WAIT_DST consuming nothing) and between steps (WAIT_DST after k_out blocks)"""
+    S1 = m.S1 * (2 if m.u8 else 1)
+    step = max(m.A(k + 1) - m.A(k) for k in range(n // m.S1 + 1))
+    if kind == "mixed":
+        return [(3 * S1 + 7, 2 * step + 3), (S1 // 2 + 1, step - 1), (5 * S1 + 1, step), (S1 + 3, 6 * step + 1)]
+    if kind == "short-in":
+        return [(S1 // 3 + 1, 4 * step + 5), (S1 // 2 + 2, 4 * step + 5), (2 * S1 + 1, 4 * step + 5)]
+    assert kind == "tight-out", kind
+    return [(9 * S1 + 5, step), (9 * S1 + 5, step // 2), (9 * S1 + 5, 2 * step + 1)]
+
+
+class ModelBlock:
+    """the protocol model behind a block's work(): zeros for samples.  Lets a CPU test drive the GPU tests' own loop"""
+
+    def __init__(self, m: ReceiverModel, nchan):
+        self.m, self.nchan = m, nchan
+
+    def work(self, x, out_cap):
+        st, c, p, need = self.m.work(len(x), out_cap)
+        return st, c, p, need, np.zeros((self.nchan, p), np.float32)
+
+
+def drive(blk, x, nch, caps):
+    """Graph::run's loop around the block with per-call window capacities caps[i % len] = (input, output) -> ([nch] streams, log)"""
+    outs, log = [[] for _ in range(nch)], []
+    pos, ring, idle = 0, np.zeros(0, x.dtype), 0
+    for i in range(200_000):
+        cin, cout = caps[i % len(caps)]
+        take = max(0, min(cin - len(ring), len(x) - pos))
+        ring = np.concatenate([ring, x[pos:pos + take]]); pos += take
+        st, c, p, need, out = blk.work(ring[:cin], cout)
+        log.append((len(ring[:cin]), cout, st, c, p, need))
+        ring = ring[c:]
+        out = np.atleast_2d(out)
+        for ch in range(nch):
+            outs[ch].append(out[ch])
+        idle = idle + 1 if (take == 0 and c == 0 and p == 0) else 0
+        if idle >= len(caps):
+            break
+    else:
+        raise AssertionError("no termination")
+    return [np.concatenate(o) for o in outs], log
+
+
+def call_lengths(m: ReceiverModel, log):
+    """what the model says every call of `log` ((input window, output window, ...) per call) took in: -> [(RF blocks, new
+    demodulated samples, filtered audio samples n_y, audio samples produced)] — n_y = 0 with new demodulated samples is the
+    call that only carries (k_audio_multi_carry)"""
+    out = []
+    for cin, cout, *_ in log:
+        K0 = m.K
+        st, c, p, need = m.work(cin, cout)
+        d0, d1 = m.d(K0 * m.S1), m.d(m.K * m.S1)
+        out.append((m.K - K0, d1 - d0, (d1 // m.S2 - d0 // m.S2) * m.S2, p))
+    return out
+
+
+def neighbour_distance(sh: Shape, chans=None, x=None):
+    """|au_c - au_c'| / bar_c over the samples behind the start-up tenth, for every ordered pair of `chans` (all by default)
+    -> {(c, c'): (median, max, share of samples within the bar)}; the oracle alone"""
+    chans = list(range(sh.nchan) if chans is None else chans)
+    au, bar = {}, {}
+    for c in chans:
+        au[c], _dm, r = oracle_channel(sh, c, x)
+        bar[c], _ = audio_bar(sh, r, au[c])
+    out = {}
+    for c in chans:
+        for d in chans:
+            if c != d:
+                lo = len(au[c]) // 10
+                q = np.abs(au[c][lo:].astype(np.float64) - au[d][lo:]) / bar[c][lo:]
+                out[(c, d)] = (float(np.median(q)), float(np.max(q)), float(np.mean(q <= 1.0)))
+    return out
 
 
 # ---- the reference chain, its float64 truth and the parity bar ---------------------------------------------------------
