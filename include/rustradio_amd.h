@@ -180,6 +180,17 @@ rr_block *rr_multiply_const_c32_create(float re, float im);
 rr_block *rr_fastfm_create(void);
 /* Hilbert::new(src, ntaps, &window_type) (src/hilbert.rs:38-61); ntaps odd > 1. */
 rr_block *rr_hilbert_create(size_t ntaps, int window, float window_parm);
+/* Vco::new(src, k) (src/vco.rs:9-37): Float in, Complex out.  Per sample a: phase += k * a in f64, one wrap by 2 pi when the
+ * phase leaves [-2 pi, 2 pi], output Complex::new(phase.sin() as f32, phase.cos() as f32) — re is the SINE and im the cosine,
+ * i.e. the stream is j e^(-j phase) and a quadrature demodulator sees -k * a.  k_bits = the f64 `k` as its IEEE-754 binary64
+ * bit pattern (f64::to_bits), so that a k computed in f64 arrives exactly; any finite or non-finite k is accepted.
+ * #[rustradio(sync)]: work() maps min(input, output space) samples, WaitForStream(src|dst, 1) (rustradio_macros_code/src/lib.rs:
+ * 458-515); tags forwarded position for position.  The running sum is a tiled f64 scan; the phase carried between calls stays
+ * in device memory.  Which multiple of 2 pi the phase holds is not observable, so outputs agree with the reference's within
+ * 2^-25 + n * 2^-48 per component after n samples (|k * a| <= 2 pi), not bit for bit.  From the first NaN / +-Inf input sample
+ * on, both components of EVERY later output are NaN, in that call and all later ones (Inf - 2 pi = Inf, sin(Inf) = NaN); the
+ * outputs before it are untouched. */
+rr_block *rr_vco_create(unsigned long long k_bits);
 
 /* Graph-level fusion of three reference blocks wired as in examples/rtl_fm.rs:381-419:
  *   FftFilter::new(src, taps) -> RationalResampler::new(_, interp, deci) -> QuadratureDemod::new(_, gain)
@@ -232,6 +243,16 @@ rr_block *rr_fm_chain_u8_create(const rr_c32 *taps, size_t ntaps, size_t interp,
  * WAIT_SRC(nsamples - pending).  Up to 3584 taps one kernel per call; longer filters run as the unfused composition of
  * the three GPU blocks behind the same handle (no tap-count limit, as in the reference). */
 rr_block *rr_audio_chain_create(const float *taps, size_t ntaps, size_t interp, size_t deci, float scale);
+
+/* Graph-level fusion of the modulator of examples/fm_tx.rs:84-91:
+ *   RationalResampler::new(src, interp, deci) -> Vco::new(_, k)
+ * (src/rational_resampler.rs:125-206, src/vco.rs:9-37) as ONE block, f32 in, Complex out: the interpolated f32 stream never
+ * reaches HBM, the phase accumulates once per OUTPUT sample.  k_bits as rr_vco_create; re = sin, im = cos.  work() is
+ * rr_resampler_create(interp, deci, _)'s call for call — same status, consumed, produced and need on windows of the same
+ * lengths, the pending sample across a full output window and eof = !pending && src_eof included; the ratio is gcd-reduced;
+ * NULL (reference: Err) when interp or deci is 0.  Tags are dropped (the resampler's rule).  Accuracy and non-finite samples
+ * as rr_vco_create, counted in output samples. */
+rr_block *rr_fm_tx_create(size_t interp, size_t deci, unsigned long long k_bits);
 
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)

@@ -53,6 +53,8 @@ unsafe extern "C" {
     fn rr_rtlsdr_decode_create() -> *mut RrBlock;
     fn rr_multiply_const_f32_create(val: f32) -> *mut RrBlock;
     fn rr_fastfm_create() -> *mut RrBlock;
+    fn rr_vco_create(k_bits: u64) -> *mut RrBlock;
+    fn rr_fm_tx_create(interp: usize, deci: usize, k_bits: u64) -> *mut RrBlock;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;
@@ -346,6 +348,19 @@ impl GpuMap<Complex, Float> {
     /// `FastFM::new(src)` (src/quadrature_demod.rs:144-165)
     pub fn fast_fm(src: ReadStream<Complex>) -> Result<(Self, ReadStream<Float>)> {
         Self::wrap(unsafe { rr_fastfm_create() }, "GpuFastFM", true, src)
+    }
+}
+impl GpuMap<Float, Complex> {
+    /// `Vco::new(src, k)` (src/vco.rs:9-37): re = sin(phase), im = cos(phase).  `k` crosses the C ABI as its bit pattern, so
+    /// the f64 computed from integers in examples/fm_tx.rs:88-90 arrives exactly.
+    pub fn vco(src: ReadStream<Float>, k: f64) -> Result<(Self, ReadStream<Complex>)> {
+        Self::wrap(unsafe { rr_vco_create(k.to_bits()) }, "GpuVco", true, src)
+    }
+    /// `RationalResampler::new(src, interp, deci)` -> `Vco::new(_, k)` as one block (rr_fm_tx_create, the modulator of
+    /// examples/fm_tx.rs:84-91).  A GpuMap rather than a GpuFused like `audio_chain`: its eof() has to ask the library, which
+    /// still holds the resampler's pending sample (rational_resampler.rs:209-213); tags are dropped like the resampler's.
+    pub fn fm_tx(src: ReadStream<Float>, interp: usize, deci: usize, k: f64) -> Result<(Self, ReadStream<Complex>)> {
+        Self::wrap(unsafe { rr_fm_tx_create(interp, deci, k.to_bits()) }, "GpuFmTx", false, src)
     }
 }
 impl GpuMap<u8, Complex> {

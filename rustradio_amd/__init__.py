@@ -24,6 +24,7 @@ import ctypes as C
 import numpy as np
 
 import contextlib
+import struct
 import threading
 
 from ._lib import BuildOpts, lib as _raw_lib, last_error, LIB_PATH  # noqa: F401
@@ -535,6 +536,22 @@ def AudioChain(taps, interp: int, deci: int, scale: float = 1.0) -> Block:
     (rr_audio_chain_create; the audio stage of examples/rtl_fm.rs:398-418); f32 in, f32 out."""
     t = np.ascontiguousarray(taps, np.float32)
     return Block(lib().rr_audio_chain_create(_ptr(t), len(t), interp, deci, scale), np.float32, np.float32)
+
+
+def _f64_bits(k: float) -> int:
+    """f64::to_bits: how a double crosses the C ABI exactly (rr_vco_create)"""
+    return struct.unpack("<Q", struct.pack("<d", k))[0]
+
+
+def Vco(k: float) -> Block:
+    """Vco::new(src, k) (src/vco.rs:9-37): f32 in, Complex(sin phase, cos phase) out, phase += k * a in f64."""
+    return Block(lib().rr_vco_create(_f64_bits(k)), np.float32, np.complex64)
+
+
+def FmTx(interp: int, deci: int, k: float) -> Block:
+    """RationalResampler(interp, deci) -> Vco(k) fused into one block (rr_fm_tx_create; the modulator of
+    examples/fm_tx.rs:84-91); f32 in, Complex out."""
+    return Block(lib().rr_fm_tx_create(interp, deci, _f64_bits(k)), np.float32, np.complex64)
 
 
 def FmChainU8(taps, interp: int, deci: int, gain: float = 1.0, mode: int = ATAN2_EXACT) -> Block:

@@ -182,6 +182,18 @@ rr_block* rr_multiply_const_c32_create(float re, float im) {
 rr_block* rr_fastfm_create(void) {
     return make_block([&] { return new rr::FastFM(); }, RR_TAGS_FORWARD, 1);
 }
+static double f64_from_bits(unsigned long long bits) {
+    double k;
+    static_assert(sizeof k == sizeof bits, "binary64");
+    std::memcpy(&k, &bits, sizeof k);
+    return k;
+}
+rr_block* rr_vco_create(unsigned long long k_bits) {
+    return make_block([&] { return new rr::Vco(f64_from_bits(k_bits)); }, RR_TAGS_FORWARD, 1);
+}
+rr_block* rr_fm_tx_create(size_t interp, size_t deci, unsigned long long k_bits) {
+    return make_block([&] { return new rr::FmTx(interp, deci, f64_from_bits(k_bits)); });
+}
 rr_block* rr_rtlsdr_decode_create(void) {
     return make_block([&] { return new rr::RtlSdrDecode(); });
 }

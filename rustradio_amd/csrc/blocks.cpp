@@ -1955,7 +1955,7 @@ static int64_t gcd64(int64_t a, int64_t b) {
     while (b != 0) { const int64_t t = b; b = a % b; a = t; }
     return a;
 }
-Resampler::Resampler(size_t interp, size_t deci, size_t es) : Block("RationalResampler", es, es) {
+Resampler::Resampler(const char* nm, size_t interp, size_t deci, size_t es, size_t oes) : Block(nm, es, oes) {
     if (deci == 0) throw Error("RationalResampler created using deci 0");      // :130-132
     if (interp == 0) throw Error("RationalResampler created using interp 0");  // :133-135
     if (!(es == 1 || es == 2 || es == 4 || es == 8 || es == 16)) throw Error("RationalResampler: element size must be 1,2,4,8 or 16");
@@ -1967,6 +1967,9 @@ Resampler::Resampler(size_t interp, size_t deci, size_t es) : Block("RationalRes
     d_pending.reserve(16);
 }
 bool Resampler::eof(bool src_eof) { return !has_pending && src_eof; }        // :209-213
+void Resampler::emit(const void* in, void* out, int64_t r, int64_t n_gather, int64_t c0, hipStream_t s) {
+    launch_resample(in, out, in_es, r, d_pending.p, n_gather, I, D, c0, s);
+}
 
 int Resampler::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed,
                         size_t* produced, size_t* need, hipStream_t s) {
@@ -1977,14 +1980,14 @@ int Resampler::work_dev(const void* in, size_t in_len, void* out, size_t out_cap
         const int64_t r_full = counter > 0 ? (counter + D - 1) / D : 0;
         if (r_full >= (int64_t)out_cap) {
             r = (int64_t)out_cap; counter -= r * D;
-            launch_resample(in, out, in_es, r, d_pending.p, 0, I, D, 0, s);
+            emit(in, out, r, 0, 0, s);
             *produced = (size_t)r;
             return RR_WAIT_DST;
         }
         r = r_full; counter -= r * D; has_pending = false;
     }
     if (in_len == 0) {                                                         // :176-179
-        if (r) launch_resample(in, out, in_es, r, d_pending.p, 0, I, D, 0, s);
+        if (r) emit(in, out, r, 0, 0, s);
         *produced = (size_t)r;
         return RR_WAIT_SRC;
     }
@@ -1993,7 +1996,7 @@ int Resampler::work_dev(const void* in, size_t in_len, void* out, size_t out_cap
     const int64_t m_total = a <= 0 ? 0 : (int64_t)((a + D - 1) / D);
     if (m_total < capp) {                                                      // all input taken
         prof_begin(s);
-        launch_resample(in, out, in_es, r, d_pending.p, m_total, I, D, c0, s);
+        emit(in, out, r, m_total, c0, s);
         prof_end(s);
         counter = (int64_t)(a - (__int128)m_total * D);
         *consumed = in_len; *produced = (size_t)(r + m_total);
@@ -2001,7 +2004,7 @@ int Resampler::work_dev(const void* in, size_t in_len, void* out, size_t out_cap
     }
     // output fills at emit number capp (:190-196)
     const int64_t kstar = (int64_t)((((__int128)(capp - 1)) * D - c0) / I);
-    launch_resample(in, out, in_es, r, d_pending.p, capp, I, D, c0, s);
+    emit(in, out, r, capp, c0, s);
     counter = (int64_t)((__int128)c0 + (__int128)(kstar + 1) * I - (__int128)capp * D);
     if (counter > 0) {
         RR_HIP(hipMemcpyAsync(d_pending.p, static_cast<const unsigned char*>(in) + (size_t)kstar * in_es, in_es,
@@ -2187,6 +2190,39 @@ int FastFM::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, s
     }
     *consumed = *produced = n;
     return st;
+}
+
+// ---- Vco (vco.rs:9-37) and RationalResampler -> Vco (examples/fm_tx.rs:84-91) ------------------------------------------------
+VcoState::VcoState(double kk, hipStream_t s) : k(kk) {
+    for (auto& p : phase) { p.reserve(1); RR_HIP(hipMemsetAsync(p.p, 0, sizeof(double), s)); }   // phase: 0.0 (vco.rs:18)
+    RR_HIP(hipStreamSynchronize(s));
+}
+Vco::Vco(double k) : Block("Vco", 4, 8), v(k, stream) {
+    zero_copy_in = false;                            // (the scan reads the window twice: tile sums, then the samples)
+}
+int Vco::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed, size_t* produced, size_t* need,
+                  hipStream_t s) {
+    size_t n = 0;
+    const int st = sync_counts(in_len, out_cap, &n, need);
+    if (n) {
+        prof_begin(s);
+        launch_vco(static_cast<const float*>(in), static_cast<cf*>(out), (long)n, v.k, v.phase[v.cur].p, v.phase[v.cur ^ 1].p,
+                   v.scratch(n), s);
+        prof_end(s);
+        v.cur ^= 1;
+    }
+    *consumed = *produced = n;
+    return st;
+}
+FmTx::FmTx(size_t interp, size_t deci, double k) : Resampler("RationalResampler>Vco", interp, deci, 4, 8), v(k, stream) {
+    zero_copy_in = false;
+}
+void FmTx::emit(const void* in, void* out, int64_t r, int64_t n_gather, int64_t c0, hipStream_t s) {
+    const int64_t n = r + n_gather;
+    if (n <= 0) return;
+    launch_fm_tx(static_cast<const float*>(in), static_cast<cf*>(out), (long)r, reinterpret_cast<const float*>(d_pending.p),
+                 (long)n_gather, (long)I, (long)D, (long)c0, v.k, v.phase[v.cur].p, v.phase[v.cur ^ 1].p, v.scratch((size_t)n), s);
+    v.cur ^= 1;
 }
 
 // ---- RtlSdrDecode (rtlsdr_decode.rs:9-47) ----------------------------------------------------------------------

@@ -495,9 +495,14 @@ struct Resampler : Block {
     int64_t I = 1, D = 1, counter = 0;
     bool has_pending = false;
     DevBuf<unsigned char> d_pending;
-    Resampler(size_t interp, size_t deci, size_t es);
+    Resampler(size_t interp, size_t deci, size_t es) : Resampler("RationalResampler", interp, deci, es, es) {}
     bool eof(bool src_eof) override;
     int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+protected:
+    // a block that fuses something BEHIND the resampler (FmTx) shares the bookkeeping above and replaces only the launch:
+    // out[0 .. r) = *d_pending, out[r + m] = in[floor((m D - c0) / I)] for m < n_gather
+    Resampler(const char* name, size_t interp, size_t deci, size_t ies, size_t oes);
+    virtual void emit(const void* in, void* out, int64_t r, int64_t n_gather, int64_t c0, hipStream_t s);
 };
 
 struct QuadDemod : Block {
@@ -527,6 +532,29 @@ struct FastFM : Block {               // quadrature_demod.rs:144-165; q2, q1 = t
     int cur = 0;
     FastFM();
     int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+};
+// Vco (vco.rs:9-37): Float -> Complex(sin phase, cos phase), phase += k * a in f64.  The running sum is a tiled scan
+// (kernels_tx.hip); the phase carried from call to call stays on the device — the host never reads it, counts depend on lengths only.
+struct VcoState {
+    double k;
+    DevBuf<double> phase[2];          // [cur]: the phase after the last sample of the previous call (0 at start)
+    int cur = 0;
+    DevBuf<double> tiles;             // scan scratch: one double per tile of the largest window so far
+    VcoState(double k, hipStream_t s);
+    double* scratch(size_t n) { tiles.reserve((n + VCO_T - 1) / VCO_T); return tiles.p; }
+};
+struct Vco : Block {
+    VcoState v;
+    explicit Vco(double k);
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+};
+// RationalResampler::new(src, interp, deci) -> Vco::new(_, k) fused (examples/fm_tx.rs:84-91): f32 in, Complex out.  The window
+// protocol, `pending` and eof are the resampler's own code; the interpolated f32 stream exists only as the scan's index map.
+struct FmTx : Resampler {
+    VcoState v;
+    FmTx(size_t interp, size_t deci, double k);
+protected:
+    void emit(const void* in, void* out, int64_t r, int64_t n_gather, int64_t c0, hipStream_t s) override;
 };
 
 // RtlSdrDecode (rtlsdr_decode.rs:9-47): stateless u8 pair -> Complex conversion.

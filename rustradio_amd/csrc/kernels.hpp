@@ -247,6 +247,16 @@ void launch_f32_to_c32(const float* in, cf* out, long n, hipStream_t s);
 void launch_copy_bytes(const void* src, void* dst, size_t bytes, hipStream_t s);   // device <-> device view of registered host memory
 void launch_c32_re(const cf* in, float* out, long n, hipStream_t s);
 
+// ---- kernels_tx.hip: Vco (vco.rs:9-37) as a tiled f64 scan ---------------------------------------------------------------
+// out[i] = (sin p_i, cos p_i), p_i = *carry_in + k (a_0 + ... + a_i) modulo 2 pi, i < n; *carry_out <- p_(n-1).  carry_in and
+// carry_out are distinct device doubles (the block's ping-pong); tiles = device scratch of ceil(n / VCO_T) doubles.
+// n == 0 launches nothing and leaves *carry_out alone.
+constexpr int VCO_T = 2048;                   // samples of one scan tile
+void launch_vco(const float* in, cf* out, long n, double k, const double* carry_in, double* carry_out, double* tiles, hipStream_t s);
+// ... reading its samples through the resampler's index map (launch_resample's r, pending, n_gather, I, D, c0): n = r + n_gather
+void launch_fm_tx(const float* in, cf* out, long r, const float* pending, long n_gather, long I, long D, long c0, double k,
+                  const double* carry_in, double* carry_out, double* tiles, hipStream_t s);
+
 // ---- head fix of the fused FirFilter -> FftFilter blocks (stream start only, a few hundred samples) ----------------
 // z[m] = sum_k t1[k] V[voff + m + L1 - 1 - k], m < n: the front FirFilter's first outputs (fir.rs:166-177) from the virtual stream
 void launch_head_z(VSrc<cf> V, long voff, const cf* t1, int L1, cf* z, long n, hipStream_t s);

@@ -1,0 +1,219 @@
+// kernels_tx.hip — Vco (src/vco.rs:9-37) and the fused RationalResampler -> Vco of examples/fm_tx.rs:84-91.
+//
+// The reference's phase is a running f64 sum: phase += k * a, one wrap by MX = 2 pi when it leaves [-MX, MX], then
+// (sin, cos).  Only sin(phase) and cos(phase) are observable, so any representative of the phase modulo MX serves, and the
+// sum becomes a scan in three launches ordered by the stream alone:
+//   k_vco_sums    per tile of VCO_T samples the sum of its k * a, folded into [-MX, MX]
+//   k_vco_scan    ONE workgroup: exclusive scan of the tile sums on top of the phase carried in from the previous call
+//                 (device memory, ping-pong), in place; writes the phase carried out
+//   k_vco_apply   per tile the inclusive scan of its samples from the tile's base, f64 sincos, one 8-byte store per sample
+// A window of one tile runs k_vco_apply alone, with the carried phase as its base.
+// No workgroup waits on another one: no look-back, no ticket, no spinning on a flag.
+//
+// Every addition of the scan is followed by the reference's own wrap, so no intermediate leaves [-2 MX, 2 MX] and one
+// addition costs at most half an ulp of 4 pi, as in the sequential form (DESIGN.md "Vco").  A non-finite sample makes its
+// own prefix sum and every later one NaN or +-Inf, whose sin and cos are NaN: the reference's behaviour with no pass for it.
+// Exclusive prefixes are built from the earlier elements only (never inclusive minus own), so the samples before stay clean.
+#include "kernels.hpp"
+
+namespace rr {
+
+constexpr int VCO_B = 256;                    // threads of a workgroup
+constexpr int VCO_PER = VCO_T / VCO_B;        // consecutive samples of one thread
+static_assert(VCO_PER == 8 && VCO_B == 256, "k_vco_apply: 8 samples per thread");
+constexpr double VCO_MX = 2.0 * 3.14159265358979323846;   // vco.rs: 2.0 * f64::consts::PI
+
+// vco.rs:27-32, both tests in the reference's order.  |p| <= 2 MX in, |p| <= MX out; v - MX is exact there (Sterbenz).
+// NaN passes both comparisons untouched and Inf - MX = Inf.
+__device__ __forceinline__ double vco_wrap(double p) {
+    if (p > VCO_MX) p -= VCO_MX;
+    if (p < -VCO_MX) p += VCO_MX;
+    return p;
+}
+// one sample's increment k * a into [-MX, MX]: beyond 2 MX by whole turns first (the reference lets such a phase grow instead)
+__device__ __forceinline__ double vco_step(double k, float a) {
+    double d = k * (double)a;
+    if (fabs(d) > 2.0 * VCO_MX) d = fma(-VCO_MX, trunc(d * (1.0 / VCO_MX)), d);
+    return vco_wrap(d);
+}
+
+// sin and cos of a wrapped phase.  |p| <= MX always holds for finite input, so the argument reduction is one rounding to
+// the nearest quarter turn and a two-part pi/2 (exact in the FMA), and what is left on [-pi/4, pi/4] takes the two fdlibm
+// minimax kernels (k_sin.c / k_cos.c, Sun Microsystems 1993, freely usable): under 1.2e-16 absolute against long double
+// over [-MX, MX] (checked on the CPU), an eighth of one sample's share of the error bound.  It saves the library routine's
+// general reduction; measured, that is a few per cent of k_vco_apply (profiles/fm_tx_probe.md).  Anything else — NaN, +-Inf,
+// a phase a huge k * a left outside — takes the library's.
+__device__ __forceinline__ void vco_sincos(double p, double* sn, double* cs) {
+    if (!(fabs(p) <= VCO_MX)) { sincos(p, sn, cs); return; }
+    const double n = rint(p * 6.36619772367581382433e-01);                        // 2 / pi
+    double r = fma(-n, 1.57079632679489655800e+00, p);                            // pi / 2, high part
+    r = fma(-n, 6.12323399573676603587e-17, r);                                   // ... and what f64 left of it
+    const double z = r * r;
+    const double ps = -1.66666666666666324348e-01 + z * (8.33333333332248946124e-03 + z * (-1.98412698298579493134e-04 +
+                      z * (2.75573137070700676789e-06 + z * (-2.50507602534068634195e-08 + z * 1.58969099521155010221e-10))));
+    const double pc = 4.16666666666666019037e-02 + z * (-1.38888888888741095749e-03 + z * (2.48015872894767294178e-05 +
+                      z * (-2.75573143513906633035e-07 + z * (2.08757232129817482790e-09 + z * -1.13596475577881948265e-11))));
+    const double sr = r + r * z * ps;
+    const double hz = 0.5 * z, w = 1.0 - hz;
+    const double cr = w + (((1.0 - w) - hz) + z * z * pc);
+    const int q = (int)n & 3;                 // sin(r + q pi/2), cos(r + q pi/2)
+    const double a = (q & 1) ? cr : sr, b = (q & 1) ? sr : cr;
+    *sn = (q & 2) ? -a : a;
+    *cs = ((q + 1) & 2) ? -b : b;
+}
+
+// The sample behind output o.  FUSED: the resampler's closed-form index map of k_resample (kernels_misc.hip) — the first r
+// outputs repeat the pending sample, output r + m reads in[floor((m D - c0) / I)].
+template <bool FUSED> struct VcoSrc {
+    const float* in;
+    const float* pending;
+    long r, I, D, c0;
+    __device__ __forceinline__ float load(long o) const {
+        if (!FUSED) return in[o];
+        if (o < r) return pending[0];
+        const long m = o - r;
+        return in[(I == 1) ? (m * D - c0) : (m * D - c0) / I];
+    }
+};
+
+// Exclusive scan of one value per thread over a workgroup of NW waves (wrapped sums); total = the sum of all.  s_w: NW doubles.
+template <int NW> __device__ __forceinline__ double vco_block_scan(double v, double* s_w, double& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    double inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double u = __shfl_up(inc, off, 64);
+        if (lane >= off) inc = vco_wrap(u + inc);
+    }
+    double exc = __shfl_up(inc, 1, 64);
+    if (lane == 0) exc = 0.0;
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    double woff = 0.0, tot = 0.0;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        const double t = s_w[j];
+        if (j < w) woff = vco_wrap(woff + t);
+        tot = vco_wrap(tot + t);
+    }
+    __syncthreads();                          // s_w is free again
+    total = tot;
+    return vco_wrap(woff + exc);
+}
+
+template <bool FUSED>
+__global__ __launch_bounds__(VCO_B) void k_vco_sums(VcoSrc<FUSED> src, long n, double k, double* __restrict__ tiles) {
+    __shared__ double s_w[VCO_B / 64];
+    const long ntiles = (n + VCO_T - 1) / VCO_T;
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long o0 = tile * VCO_T;
+        const int cnt = (int)(n - o0 < VCO_T ? n - o0 : VCO_T);
+        double run = 0.0;
+        for (int j = threadIdx.x; j < cnt; j += VCO_B) run = vco_wrap(run + vco_step(k, src.load(o0 + j)));
+        double total;
+        (void)vco_block_scan<VCO_B / 64>(run, s_w, total);
+        if (threadIdx.x == 0) tiles[tile] = total;
+    }
+}
+
+// tiles[i] <- carried phase + tiles[0] + ... + tiles[i - 1]; *carry_out <- carried phase + all of them.  One workgroup of
+// VCO_SB threads walks the tile sums in chunks of VCO_SB * 4 through LDS (coalesced both ways; 1e8 samples are 12 chunks).
+constexpr int VCO_SB = 1024, VCO_SPER = 4, VCO_SCHUNK = VCO_SB * VCO_SPER;
+__global__ __launch_bounds__(VCO_SB) void k_vco_scan(double* __restrict__ tiles, long ntiles, const double* __restrict__ carry_in,
+                                                     double* __restrict__ carry_out) {
+    __shared__ double s_t[VCO_SCHUNK];
+    __shared__ double s_w[VCO_SB / 64];
+    double base = carry_in[0];
+    for (long c0 = 0; c0 < ntiles; c0 += VCO_SCHUNK) {
+        const int cnt = (int)(ntiles - c0 < VCO_SCHUNK ? ntiles - c0 : VCO_SCHUNK);
+        for (int j = threadIdx.x; j < VCO_SCHUNK; j += VCO_SB) s_t[j] = j < cnt ? tiles[c0 + j] : 0.0;
+        __syncthreads();
+        double* mine = s_t + threadIdx.x * VCO_SPER;
+        double e[VCO_SPER], run = 0.0;
+#pragma unroll
+        for (int i = 0; i < VCO_SPER; ++i) { e[i] = run; run = vco_wrap(run + mine[i]); }   // exclusive: earlier tiles only
+        double total;
+        const double exc = vco_block_scan<VCO_SB / 64>(run, s_w, total);
+        const double p0 = vco_wrap(base + exc);
+#pragma unroll
+        for (int i = 0; i < VCO_SPER; ++i) mine[i] = vco_wrap(p0 + e[i]);
+        __syncthreads();
+        for (int j = threadIdx.x; j < cnt; j += VCO_SB) tiles[c0 + j] = s_t[j];
+        base = vco_wrap(base + total);
+        __syncthreads();                      // the next chunk overwrites s_t
+    }
+    if (threadIdx.x == 0) carry_out[0] = base;
+}
+
+// SINGLE: the window is one tile — base[0] is the carried phase and the kernel writes the phase carried out itself.
+template <bool FUSED, bool SINGLE>
+__global__ __launch_bounds__(VCO_B) void k_vco_apply(VcoSrc<FUSED> src, cf* __restrict__ out, long n, double k,
+                                                     const double* __restrict__ base, double* __restrict__ carry_out) {
+    // the tile's samples, then its outputs, so that both are coalesced in HBM whatever the window's alignment; one pad per
+    // thread (8 elements) keeps the threads' own runs on different LDS banks
+    __shared__ cf s_buf[VCO_T + VCO_B];
+    __shared__ double s_w[VCO_B / 64];
+    float* s_a = reinterpret_cast<float*>(s_buf);
+    cf* s_o = s_buf;
+    const long ntiles = (n + VCO_T - 1) / VCO_T;
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long o0 = tile * VCO_T;
+        const int cnt = (int)(n - o0 < VCO_T ? n - o0 : VCO_T);
+        for (int j = threadIdx.x; j < VCO_T; j += VCO_B) s_a[j + j / VCO_PER] = j < cnt ? src.load(o0 + j) : 0.0f;
+        __syncthreads();
+        const int i0 = threadIdx.x * VCO_PER, l0 = threadIdx.x * (VCO_PER + 1);
+        double d[VCO_PER];
+        double run = 0.0;
+#pragma unroll
+        for (int i = 0; i < VCO_PER; ++i) {   // inclusive sums from the thread's first sample
+            if (i0 + i < cnt) run = vco_wrap(run + vco_step(k, s_a[l0 + i]));
+            d[i] = run;
+        }
+        double total;
+        const double exc = vco_block_scan<VCO_B / 64>(run, s_w, total);   // (its barriers: every thread has read s_a before s_o is written)
+        const double b = base[SINGLE ? 0 : tile];
+        const double p0 = vco_wrap(b + exc);
+#pragma unroll
+        for (int i = 0; i < VCO_PER; ++i) {
+            double sn, cs;
+            vco_sincos(vco_wrap(p0 + d[i]), &sn, &cs);
+            s_o[l0 + i] = mkcf((float)sn, (float)cs);          // vco.rs:33-36: re = sin, im = cos
+        }
+        __syncthreads();
+        for (int j = threadIdx.x; j < cnt; j += VCO_B) out[o0 + j] = s_o[j + j / VCO_PER];
+        if (SINGLE && threadIdx.x == 0) carry_out[0] = vco_wrap(b + total);
+        __syncthreads();                      // the next tile overwrites s_buf
+    }
+}
+
+static inline unsigned vco_grid(long ntiles) {
+    const long cap = (long)device_cu_count() * 8;
+    return (unsigned)std::max<long>(1, std::min(ntiles, cap));
+}
+
+template <bool FUSED>
+static void vco_launch(VcoSrc<FUSED> src, cf* out, long n, double k, const double* carry_in, double* carry_out, double* tiles,
+                       hipStream_t s) {
+    if (n <= 0) return;
+    const long ntiles = (n + VCO_T - 1) / VCO_T;
+    if (ntiles == 1) {
+        hipLaunchKernelGGL((k_vco_apply<FUSED, true>), dim3(1), dim3(VCO_B), 0, s, src, out, n, k, carry_in, carry_out);
+        RR_HIP(hipGetLastError());
+        return;
+    }
+    const unsigned g = vco_grid(ntiles);
+    hipLaunchKernelGGL((k_vco_sums<FUSED>), dim3(g), dim3(VCO_B), 0, s, src, n, k, tiles);
+    hipLaunchKernelGGL(k_vco_scan, dim3(1), dim3(VCO_SB), 0, s, tiles, ntiles, carry_in, carry_out);
+    hipLaunchKernelGGL((k_vco_apply<FUSED, false>), dim3(g), dim3(VCO_B), 0, s, src, out, n, k, (const double*)tiles, carry_out);
+    RR_HIP(hipGetLastError());
+}
+
+void launch_vco(const float* in, cf* out, long n, double k, const double* carry_in, double* carry_out, double* tiles, hipStream_t s) {
+    vco_launch(VcoSrc<false>{in, nullptr, 0, 1, 1, 0}, out, n, k, carry_in, carry_out, tiles, s);
+}
+void launch_fm_tx(const float* in, cf* out, long r, const float* pending, long n_gather, long I, long D, long c0, double k,
+                  const double* carry_in, double* carry_out, double* tiles, hipStream_t s) {
+    vco_launch(VcoSrc<true>{in, pending, r, I, D, c0}, out, r + n_gather, k, carry_in, carry_out, tiles, s);
+}
+
+}  // namespace rr

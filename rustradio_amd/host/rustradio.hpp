@@ -798,6 +798,24 @@ public:
         return {std::make_unique<FastFM>(rr_fastfm_create(), std::move(src), std::move(w)), std::move(r)};
     }
 };
+// Vco (src/vco.rs:9-37), also a sync block: Float -> Complex(sin phase, cos phase), phase += k * a in f64.  `k` crosses the
+// C ABI as its IEEE-754 bit pattern (f64::to_bits), so it arrives exactly.
+namespace detail {
+inline unsigned long long f64_bits(double k) {
+    unsigned long long b;
+    static_assert(sizeof b == sizeof k, "binary64");
+    std::memcpy(&b, &k, sizeof b);
+    return b;
+}
+}  // namespace detail
+class Vco : public SyncBlock<Float, Complex> {
+public:
+    using SyncBlock<Float, Complex>::SyncBlock;
+    static std::pair<std::unique_ptr<Vco>, ReadStream<Complex>> new_(ReadStream<Float> src, double k) {
+        auto [w, r] = new_stream<Complex>();
+        return {std::make_unique<Vco>(rr_vco_create(detail::f64_bits(k)), std::move(src), std::move(w)), std::move(r)};
+    }
+};
 
 // ---- graph-level fusions (one block, one kernel; whole-stream output = the reference blocks in sequence) ------------------
 // Tags: what the reference blocks in sequence would deliver (rr_block_tag_rule) — a chain holding a RationalResampler or a
@@ -858,6 +876,12 @@ inline auto HilbertFir(ReadStream<Float> src, size_t hilbert_ntaps, const window
 inline auto AudioChain(ReadStream<Float> src, const std::vector<Float>& taps, size_t interp, size_t deci, Float scale) {
     return Fused<Float, Float>::make(std::move(src), [&] { return rr_audio_chain_create(taps.data(), taps.size(), interp, deci, scale); });
 }
+// RationalResampler(interp, deci) -> Vco(k) (examples/fm_tx.rs:84-91): the resampler's window protocol and eof, tags dropped
+struct FmTx {
+    static auto new_(ReadStream<Float> src, size_t interp, size_t deci, double k) {
+        return Fused<Float, Complex>::make(std::move(src), [&] { return rr_fm_tx_create(interp, deci, detail::f64_bits(k)); });
+    }
+};
 
 // The N-station FM receiver down to audio (rr_fm_receiver_create): Tee (src/tee.rs:10-24) + N x the six blocks of
 // examples/rtl_fm.rs:381-419 on ONE input, N audio streams.  The C ABI takes the N output windows as one buffer of N x out_cap
