@@ -1,5 +1,6 @@
 """CPU-only: the Vco model the GPU tests of rr_vco_create / rr_fm_tx_create rely on (tests/tx_model.py) against the
-long-double truth, its carried phase, its non-finite rule — and the public surface of the two blocks."""
+long-double truth, its carried phase, its non-finite rule, the exact truth on a dyadic grid and the bound for large steps
+that the long GPU cases are judged with — and the public surface of the two blocks."""
 import ctypes
 import math
 
@@ -7,7 +8,8 @@ import numpy as np
 import pytest
 
 import rustradio_amd as rr
-from tx_model import bound, comp_err, vco_model, vco_truth
+from tx_model import (GRID_G, MX, bound, bound_steps, comp_err, fm_tx_truth, fm_tx_truth_grid, grid_noise, grid_signal,
+                      truth_grid_error, vco_model, vco_step_model, vco_truth, vco_truth_grid)
 
 K75 = 2.0 * math.pi * 75000 / 480000
 K5 = 2.0 * math.pi * 5000 / 480000
@@ -61,6 +63,57 @@ def test_model_non_finite_poisons_everything_after(bad, p):
     assert y1[:p].view(np.uint32).tolist() == clean[:p].view(np.uint32).tolist()
     for y in (y1[p:], y2):
         assert np.all(np.isnan(y.real)) and np.all(np.isnan(y.imag))
+
+
+# ---- the exact truth on a dyadic grid, and the bound for large steps ---------------------------------------------------------
+def _apart(t, u):
+    """largest per-component distance of two truths"""
+    return float(max(np.max(np.abs(t.real - u.real)), np.max(np.abs(t.imag - u.imag))))
+
+
+def test_grid_truth_agrees_with_the_long_double_truth():
+    q, a = grid_noise(N, 23)
+    assert a.dtype == np.float32 and np.array_equal(a.astype(np.float64) * 4096.0, q.astype(np.float64))   # the grid is exact
+    d = _apart(vco_truth_grid(q, GRID_G, K75), vco_truth(a, K75))
+    print(f"grid truth vs long-double cumsum, noise: {d:.4e} (own error at most {truth_grid_error(N, K75):.4e})")
+    assert d <= 1e-12 and truth_grid_error(N, K75) <= 1e-12
+    assert _apart(fm_tx_truth_grid(q[:5000], GRID_G, 7, 5, K75, 7000), fm_tx_truth(a[:5000], 7, 5, K75, 7000)) <= 1e-12
+
+
+def test_model_is_within_the_bound_of_the_grid_truth_on_dc():
+    n = 400_000                                   # 61 times round the circle at K75: where vco_truth's own cumsum starts to drift
+    q = np.full(n, 4096, np.int64)
+    y, _ = vco_model(grid_signal(q), K75)
+    e = comp_err(y, vco_truth_grid(q, GRID_G, K75))
+    print(f"dc+1 x {n}: model vs grid truth {e:.4e}, bound {bound(n):.4e}")
+    assert e <= bound(n)
+    assert truth_grid_error(n, K75) <= 0.01 * bound(n)
+
+
+_K_LARGE = [10.0, 4.0 * math.pi, 13.0, 100.0, 1e4, 1e6, -1e6]      # 2 pi < |k| <= 4 pi: wrap only; beyond: whole turns removed
+
+
+@pytest.mark.parametrize("sig", ["noise", "dc+1", "dc-1"])
+@pytest.mark.parametrize("k", _K_LARGE)
+def test_step_model_is_within_bound_steps(k, sig):
+    n = 3 * 2048 + 17
+    q = grid_noise(n, 24)[0] if sig == "noise" else np.full(n, 4096 if sig == "dc+1" else -4096, np.int64)
+    y, ph = vco_step_model(grid_signal(q), k)
+    assert abs(ph) <= MX
+    e = comp_err(y, vco_truth_grid(q, GRID_G, k))
+    print(f"{sig} k={k}: kernel-rule model vs grid truth {e:.4e}, bound_steps {bound_steps(n, abs(k)):.4e}")
+    assert e <= bound_steps(n, abs(k))
+    assert truth_grid_error(n, k) <= 0.01 * bound_steps(n, abs(k))
+
+
+def test_bound_steps_extends_bound_and_bound_is_unchanged():
+    for n in (1, 700, 200_000, 4097 * 2048 + 17):
+        assert bound(n) == 2.0 ** -25 + n * 2.0 ** -48
+        assert bound_steps(n, 0.0) == bound(n)
+        for d in (0.5, MX, 13.0, 1e6):
+            assert bound_steps(n, d) >= bound(n)
+            assert bound_steps(n, d) == 2.0 ** -25 + n * (2.0 ** -48 + d * 2.0 ** -52)
+    assert bound(4097 * 2048 + 17) == pytest.approx(5.96e-8, rel=2e-3)
 
 
 def test_public_surface():

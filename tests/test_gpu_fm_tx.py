@@ -1,6 +1,8 @@
 """GPU: rr_vco_create (Vco, src/vco.rs:9-37) and rr_fm_tx_create (RationalResampler -> Vco, examples/fm_tx.rs:84-91) against
 the long-double truth of tests/tx_model.py within its derived bound, the sync / resampler window protocols call by call, the
-carried phase, the reference's non-finite rule, and a loop-back through QuadratureDemod that needs no reference at all."""
+carried phase, the reference's non-finite rule (through the fused block too), steps beyond 2 pi against the exact truth on a
+dyadic grid, the kernel's own sincos phase by phase, and a loop-back through QuadratureDemod that needs no reference at all.
+Windows of many tiles: tests/test_gpu_fm_tx_scale.py."""
 import ctypes as C
 import math
 import os
@@ -12,7 +14,8 @@ import pytest
 import rustradio_amd as rr
 from harness import AGAIN, WAIT_DST, WAIT_SRC, drive_pageable, drive_registered, run_chain
 from oracle import pyoracle as orc
-from tx_model import bound, comp_err, fm_tx_truth, sync_rule, vco_truth
+from tx_model import (GRID_G, MX, bound, bound_steps, comp_err, fm_tx_truth, fm_tx_truth_grid, grid_noise, grid_signal,
+                      sync_rule, truth_grid_error, vco_truth, vco_truth_grid)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -113,6 +116,137 @@ def test_vco_non_finite(bad, p):
     later = [blk.work(noise(m, 5 + m), m)[4] for m in (700, T + 5)]               # two further calls, finite input
     for part in [y[p:]] + later:
         assert len(part) and np.all(np.isnan(part.real)) and np.all(np.isnan(part.imag))
+
+
+# ---- 4b. steps beyond 2 pi: the kernel takes whole turns out of the step, the reference lets the phase grow ------------------------
+def _grid_signal(sig, n, seed):
+    return grid_noise(n, seed)[0] if sig == "noise" else np.full(n, (1 << GRID_G) if sig == "dc+1" else -(1 << GRID_G), np.int64)
+
+
+@pytest.mark.parametrize("sig", ["noise", "dc+1", "dc-1"])
+@pytest.mark.parametrize("k", [10.0, 4.0 * math.pi, 13.0, 100.0, 1e4, 1e6, -1e6])   # 2 MX = 4 pi = 12.566...: either side of it
+def test_vco_large_steps(k, sig):
+    n = 3 * T + 17
+    q = _grid_signal(sig, n, 11)
+    y = feed_sync(rr.Vco(k), grid_signal(q), [(700, 700), (2 * T + 5, 2 * T + 5), (n, n)])
+    e, b = comp_err(y, vco_truth_grid(q, GRID_G, k)), bound_steps(n, abs(k))
+    print(f"large steps {sig} k={k}: {n} outputs, worst component error {e:.4e}, bound_steps {b:.4e}")
+    assert truth_grid_error(n, k) <= 0.01 * b
+    assert e <= b, (sig, k, e, b)
+
+
+@pytest.mark.parametrize("sig", ["noise", "dc+1", "dc-1"])
+def test_vco_absurd_k(sig):
+    """k = 1e300: what is left of such a step after the whole turns is noise, so there is no truth.  Properties only."""
+    n = 3 * T + 17
+    blk = rr.Vco(1e300)
+    y = feed_sync(blk, grid_signal(_grid_signal(sig, n, 12)), [(700, 700), (2 * T + 5, 2 * T + 5), (n, n)])
+    assert len(y) == n and np.all(np.isfinite(y.real)) and np.all(np.isfinite(y.imag))
+    d = float(np.max(np.abs(y.real.astype(np.float64) ** 2 + y.imag.astype(np.float64) ** 2 - 1.0)))
+    print(f"k=1e300 {sig}: | re^2 + im^2 - 1 | <= {d:.4e}, allowed {2.0 ** -22:.4e}")
+    assert d <= 2.0 ** -22
+    st, c, p, need, y2 = blk.work(noise(T + 5, 13), 900)                          # an output-limited call afterwards
+    assert (st, c, p, need) == sync_rule(T + 5, 900) == (WAIT_DST, 900, 900, 1) and len(y2) == 900
+
+
+# ---- 4c. the kernel's own sincos, phase by phase -----------------------------------------------------------------------------------
+def _edge_phases():
+    ph = []
+    for q in range(-8, 9):                        # every multiple of pi / 4 in [-MX, MX] and its neighbours: the quadrant switches
+        c = q * (math.pi / 4)                     # (the f64 nearest to q pi / 4: pi / 4 is a power of two times f64 pi)
+        up, dn = c, c
+        ph.append(c)
+        for _ in range(3):
+            up, dn = float(np.nextafter(up, np.inf)), float(np.nextafter(dn, -np.inf))
+            ph += [up, dn]
+    assert MX in ph and float(np.nextafter(MX, np.inf)) in ph and float(np.nextafter(-MX, 0.0)) in ph   # the ends, inside and outside
+    ph += [0.0, -0.0, 5e-324, -5e-324, 1e-300, -1e-300, 2.0 ** -27, -2.0 ** -27]
+    ph += np.random.default_rng(14).uniform(-MX, MX, 64).tolist()
+    return ph
+
+
+def test_vco_sincos_edges():
+    """Vco(p) on the one sample 1.0 hands exactly the f64 p to the kernel's sincos: the phase starts at 0 and p * 1.0 = p.
+    Truth: long-double sin / cos of that phase after the reference's one wrap (vco.rs:27-32; p - MX is exact there)."""
+    ld = np.longdouble
+    phases = _edge_phases()
+    assert 180 <= len(phases) <= 260
+    one = np.ones(1, np.float32)
+    worst, quadrants = 0.0, set()
+    for p in phases:
+        st, c, n, need, y = rr.Vco(p).work(one, 1)
+        assert (st, c, n, need) == sync_rule(1, 1) and len(y) == 1
+        w = p - MX if p > MX else p + MX if p < -MX else p
+        assert abs(w) <= MX
+        quadrants.add(int(np.rint(w / (math.pi / 2))))
+        e = max(abs(float(ld(y[0].real) - np.sin(ld(w)))), abs(float(ld(y[0].imag) - np.cos(ld(w)))))
+        assert e <= bound(1), (p, w, y[0], e, bound(1))
+        worst = max(worst, e)
+    assert quadrants == set(range(-4, 5))
+    print(f"sincos edges: {len(phases)} phases, worst component error {worst:.4e}, bound {bound(1):.4e}")
+
+
+# ---- 4d. non-finite samples through the fused block ----------------------------------------------------------------------------------
+def _oracle_stream(I, D, x):
+    """the reference resampler's output for the whole of x"""
+    yo = orc.RationalResampler(I, D, np.float32).work(x, len(x) * I // D + 2)[4]
+    assert len(yo) == -(-len(x) * I // D)
+    return yo
+
+
+def _check_poisoned(y, yo, q, I, D, what):
+    """vco.rs on the stream yo: the first non-finite sample poisons its own output and every later one, none before"""
+    bad = np.flatnonzero(~np.isfinite(yo))
+    first = int(bad[0]) if len(bad) else len(yo)
+    assert len(y) == len(yo)
+    if first:
+        assert_within(y[:first], fm_tx_truth_grid(q, GRID_G, I, D, K75, first), first, f"{what}: clean before output {first}")
+    assert np.all(np.isnan(y[first:].real)) and np.all(np.isnan(y[first:].imag)), what
+    return first
+
+
+def _non_finite_decimating():
+    n_in = 3 * T + 11
+    q, a = grid_noise(n_in, 15)
+    for at, read in ((2, False), (3, True)):      # (m * 3) // 2 = 0, 1, 3, 4, 6, ...: index 2 is never read, index 3 is output 2
+        x = a.copy(); x[at] = np.nan
+        assert (at in ((np.arange(8) * 3) // 2).tolist()) == read
+        yo = _oracle_stream(2, 3, x)
+        st, c, p, need, y = rr.FmTx(2, 3, K75).work(x, len(yo) + 1)
+        assert (st, c, p, need) == (WAIT_SRC, n_in, len(yo), 1)
+        first = _check_poisoned(y, yo, q, 2, 3, f"2:3 NaN at {at}")
+        assert first == (2 if read else len(yo))
+        if not read:
+            assert np.all(np.isfinite(y.real)) and np.all(np.isfinite(y.imag))
+
+
+def _non_finite_interpolating():
+    n_in = 3 * T + 11
+    q, a = grid_noise(n_in, 16)
+    x = a.copy(); x[5] = np.nan
+    yo = _oracle_stream(10, 1, x)
+    st, c, p, need, y = rr.FmTx(10, 1, K75).work(x, len(yo) + 1)
+    assert (st, c, p, need) == (WAIT_SRC, n_in, 10 * n_in, 1)
+    assert _check_poisoned(y, yo, q, 10, 1, "10:1 NaN at 5, one call") == 50
+    # windows of 3 outputs: the NaN sample is the resampler's pending one from output 51 to 59, across three calls
+    blk, ref = rr.FmTx(10, 1, K75), orc.RationalResampler(10, 1, np.float32)
+    pos, outs, outs_o, nan_pending = 0, [], [], 0
+    for cap in [3] * 25 + [10 * n_in]:
+        got, want = blk.work(x[pos:], cap), ref.work(x[pos:], cap)
+        assert got[:4] == want[:4], (pos, cap, got[:4], want[:4])
+        nan_pending += cap == 3 and pos == 6 and bool(np.isnan(want[4][0]))    # sample 5 is consumed, its repeats still come
+        outs.append(got[4]); outs_o.append(want[4]); pos += got[1]
+    assert pos == n_in and nan_pending >= 2
+    y3, yo3 = np.concatenate(outs), np.concatenate(outs_o)
+    assert np.array_equal(yo3, yo, equal_nan=True)
+    assert _check_poisoned(y3, yo3, q, 10, 1, "10:1 NaN at 5, windows of 3") == 50
+    assert np.array_equal(np.isnan(y3.real), np.isnan(y.real)) and np.array_equal(np.isnan(y3.imag), np.isnan(y.imag))
+    assert len(outs[-1]) > 3 * T and np.all(np.isnan(outs[-1].real))              # the later window read finite samples only
+
+
+@pytest.mark.parametrize("ratio", ["2:3", "10:1"])
+def test_fm_tx_non_finite(ratio):
+    {"2:3": _non_finite_decimating, "10:1": _non_finite_interpolating}[ratio]()
 
 
 # ---- 5. the fused block keeps the resampler's protocol ---------------------------------------------------------------------
