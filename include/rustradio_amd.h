@@ -191,6 +191,24 @@ rr_block *rr_hilbert_create(size_t ntaps, int window, float window_parm);
  * on, both components of EVERY later output are NaN, in that call and all later ones (Inf - 2 pi = Inf, sin(Inf) = NaN); the
  * outputs before it are untouched. */
 rr_block *rr_vco_create(unsigned long long k_bits);
+/* ComplexToMag2::new(src) (src/complex_to_mag2.rs:8-21): Complex in, f32 out, re*re + im*im with the reference's three
+ * f32 roundings (num-complex norm_sqr, no FMA).  #[rustradio(sync)].  Bit-exact.  Tags: RR_TAGS_FORWARD, 1. */
+rr_block *rr_complex_to_mag2_create(void);
+
+/* SinglePoleIirFilter::<Float|Complex>::new(src, alpha) (src/single_pole_iir_filter.rs:11-93): elem_size 4 or 8 (Complex:
+ * re and im are two independent recurrences).  y = x*alpha + y_prev*(1 - alpha), y_prev = 0 at the start, carried across calls
+ * in device memory.  NULL + rr_last_error ("alpha out of range") unless 0 <= alpha <= 1 (NaN included: reference returns
+ * None).  #[rustradio(sync)]; tags RR_TAGS_FORWARD, 1.  Accuracy and non-finite samples: below. */
+rr_block *rr_single_pole_iir_create(float alpha, size_t elem_size);
+/* Accuracy of the two scan blocks (this one and rr_burst_detector_create).  With a = alpha and b = fl32(1.0f - alpha), the
+ * reference's two f32 fields, widened to f64, and t[n] = a x[n] + b t[n-1] in real arithmetic: the recurrence runs as a tiled
+ * scan in f64 with ONE cast to f32 at the store, so
+ *   |out[n] - t[n]| <= 2^-24 |t[n]| + 2^-53 X (64 + 4 / alpha),   X = max |x| over the stream so far,
+ * closer to t than the reference's own f32 fold (whose drift is up to 2.01 * 2^-24 X / alpha); not bit-equal to it.  alpha 0
+ * gives exactly 0.0f, alpha 1 gives x bit for bit.  Non-finite samples: a NaN sample makes its own output and EVERY later one
+ * NaN, in that call and in all later calls (the reference's prev_output stays NaN); the outputs before it are untouched.  A
+ * +-Inf sample makes every output from there on non-finite; whether a given one is Inf or NaN is not pinned (Inf times an
+ * underflowed power of b is NaN where the reference may still hold Inf). */
 
 /* Graph-level fusion of three reference blocks wired as in examples/rtl_fm.rs:381-419:
  *   FftFilter::new(src, taps) -> RationalResampler::new(_, interp, deci) -> QuadratureDemod::new(_, gain)
@@ -253,6 +271,23 @@ rr_block *rr_audio_chain_create(const float *taps, size_t ntaps, size_t interp, 
  * NULL (reference: Err) when interp or deci is 0.  Tags are dropped (the resampler's rule).  Accuracy and non-finite samples
  * as rr_vco_create, counted in output samples. */
 rr_block *rr_fm_tx_create(size_t interp, size_t deci, unsigned long long k_bits);
+
+/* Graph-level fusion of the burst path of examples/burst_saver.rs:111-123:
+ *   ComplexToMag2 -> SinglePoleIirFilter(alpha) -> the comparison of BurstTagger(threshold) (src/burst_tagger.rs:68-85)
+ * Complex in; f32 out = the filtered power (what SinglePoleIirFilter delivers to BurstTagger's trigger input); sync protocol.
+ * Besides, every call records the positions i (relative to the call's window) at which cur(i) = (out[i] > threshold) differs
+ * from cur(i-1); cur(-1) is the previous call's last value, false at the start of the stream: exactly where BurstTagger
+ * pushes Tag(pos, tag, Bool(cur)).  alpha as rr_single_pole_iir_create.  The envelope is bit-identical to
+ * rr_complex_to_mag2 -> rr_single_pole_iir on windows of the same lengths, and cur(i) is decided on the f32 actually stored.
+ * Accuracy and non-finite samples as rr_single_pole_iir_create; edges after a +-Inf sample are unspecified, a NaN envelope is
+ * never above the threshold, and a NaN threshold yields no edges. */
+rr_block *rr_burst_detector_create(float alpha, float threshold);
+
+/* The edges of the block's most recent work call, ascending.  Waits for that call (as rr_block_sync), writes the first
+ * min(*total, cap) of them: pos[j] window-relative, val[j] = 1 (rose above threshold) / 0.  *total = how many there were;
+ * a call that moved no samples has none.  No edge is ever dropped on the device: its list holds one entry per sample of the
+ * largest window seen.  RR_ERR for a handle that is not a burst detector. */
+int rr_burst_edges(rr_block *b, size_t *pos, unsigned char *val, size_t cap, size_t *total);
 
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)

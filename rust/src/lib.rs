@@ -55,6 +55,11 @@ unsafe extern "C" {
     fn rr_fastfm_create() -> *mut RrBlock;
     fn rr_vco_create(k_bits: u64) -> *mut RrBlock;
     fn rr_fm_tx_create(interp: usize, deci: usize, k_bits: u64) -> *mut RrBlock;
+    fn rr_complex_to_mag2_create() -> *mut RrBlock;
+    fn rr_single_pole_iir_create(alpha: f32, elem_size: usize) -> *mut RrBlock;
+    // (declared for completeness: the detector's block needs rr_burst_edges too and is not written yet)
+    #[allow(dead_code)]
+    fn rr_burst_detector_create(alpha: f32, threshold: f32) -> *mut RrBlock;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;
@@ -339,6 +344,11 @@ impl<T: Sample> GpuMap<T, T> {
         // SAFETY: plain values.
         Self::wrap(unsafe { rr_resampler_create(interp, deci, std::mem::size_of::<T>()) }, "GpuRationalResampler", false, src)
     }
+    /// `SinglePoleIirFilter::new(src, alpha)` (src/single_pole_iir_filter.rs:11-93), T = Float or Complex; Err where the
+    /// reference returns None (alpha outside 0..=1)
+    pub fn single_pole_iir_filter(src: ReadStream<T>, alpha: Float) -> Result<(Self, ReadStream<T>)> {
+        Self::wrap(unsafe { rr_single_pole_iir_create(alpha, std::mem::size_of::<T>()) }, "GpuSinglePoleIirFilter", true, src)
+    }
 }
 impl GpuMap<Complex, Float> {
     /// `QuadratureDemod::new(src, gain)`; `fast_math` = the Cargo feature the application is built with
@@ -348,6 +358,10 @@ impl GpuMap<Complex, Float> {
     /// `FastFM::new(src)` (src/quadrature_demod.rs:144-165)
     pub fn fast_fm(src: ReadStream<Complex>) -> Result<(Self, ReadStream<Float>)> {
         Self::wrap(unsafe { rr_fastfm_create() }, "GpuFastFM", true, src)
+    }
+    /// `ComplexToMag2::new(src)` (src/complex_to_mag2.rs:8-21)
+    pub fn complex_to_mag2(src: ReadStream<Complex>) -> Result<(Self, ReadStream<Float>)> {
+        Self::wrap(unsafe { rr_complex_to_mag2_create() }, "GpuComplexToMag2", true, src)
     }
 }
 impl GpuMap<Float, Complex> {

@@ -554,6 +554,38 @@ def FmTx(interp: int, deci: int, k: float) -> Block:
     return Block(lib().rr_fm_tx_create(interp, deci, _f64_bits(k)), np.float32, np.complex64)
 
 
+def ComplexToMag2() -> Block:
+    """ComplexToMag2::new(src) (src/complex_to_mag2.rs:8-21): Complex in, re * re + im * im out, bit-exact."""
+    return Block(lib().rr_complex_to_mag2_create(), np.complex64, np.float32)
+
+
+def SinglePoleIirFilter(alpha: float, dtype=np.float32) -> Block:
+    """SinglePoleIirFilter::new(src, alpha) (src/single_pole_iir_filter.rs:11-93), Float or Complex: y = alpha x +
+    (1 - alpha) y_prev as an f64 scan; ValueError ("alpha out of range") unless 0 <= alpha <= 1."""
+    dt = np.dtype(dtype)
+    return Block(lib().rr_single_pole_iir_create(float(alpha), dt.itemsize), dt, dt)
+
+
+class BurstDetector(Block):
+    """ComplexToMag2 -> SinglePoleIirFilter(alpha) -> the comparison of BurstTagger(threshold) fused into one block
+    (rr_burst_detector_create; the burst path of examples/burst_saver.rs:111-123): Complex in, the filtered power out;
+    edges() gives the threshold crossings of the most recent work call."""
+
+    def __init__(self, alpha: float, threshold: float):
+        super().__init__(lib().rr_burst_detector_create(float(alpha), float(threshold)), np.complex64, np.float32)
+
+    def edges(self):
+        """-> (pos: uint64[], val: bool[]) of the most recent work call, ascending, window-relative (rr_burst_edges)"""
+        total = C.c_size_t(0)
+        if lib().rr_burst_edges(self._h, None, None, 0, C.byref(total)) != 0:
+            raise RuntimeError(last_error())
+        pos = np.zeros(max(total.value, 1), np.uint64)
+        val = np.zeros(max(total.value, 1), np.uint8)
+        if total.value and lib().rr_burst_edges(self._h, _ptr(pos), _ptr(val), total.value, C.byref(total)) != 0:
+            raise RuntimeError(last_error())
+        return pos[:total.value], val[:total.value].astype(bool)
+
+
 def FmChainU8(taps, interp: int, deci: int, gain: float = 1.0, mode: int = ATAN2_EXACT) -> Block:
     """RtlSdrDecode -> FmChain fused (examples/rtl_fm.rs:328-419): RTL-SDR bytes in, f32 out; windows,
     consumed and the WAIT_SRC need count bytes."""

@@ -194,6 +194,34 @@ rr_block* rr_vco_create(unsigned long long k_bits) {
 rr_block* rr_fm_tx_create(size_t interp, size_t deci, unsigned long long k_bits) {
     return make_block([&] { return new rr::FmTx(interp, deci, f64_from_bits(k_bits)); });
 }
+rr_block* rr_complex_to_mag2_create(void) {
+    return make_block([&] { return new rr::ComplexToMag2(); }, RR_TAGS_FORWARD, 1);
+}
+// single_pole_iir_filter.rs:38-41: None unless 0 <= alpha <= 1 (NaN fails both comparisons) — said before any device is touched
+static bool iir_alpha_ok(float alpha) {
+    if (alpha >= 0.0f && alpha <= 1.0f) return true;
+    rr::set_build_opts(nullptr);
+    rr::set_last_error("alpha out of range");
+    return false;
+}
+rr_block* rr_single_pole_iir_create(float alpha, size_t elem_size) {
+    if (!iir_alpha_ok(alpha)) return nullptr;
+    return make_block([&] { return new rr::SinglePoleIir(alpha, elem_size); }, RR_TAGS_FORWARD, 1);
+}
+rr_block* rr_burst_detector_create(float alpha, float threshold) {
+    if (!iir_alpha_ok(alpha)) return nullptr;
+    return make_block([&] { return new rr::BurstDetector(alpha, threshold); }, RR_TAGS_FORWARD, 1);
+}
+int rr_burst_edges(rr_block* b, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
+    auto* d = b ? dynamic_cast<rr::BurstDetector*>(b->b.get()) : nullptr;
+    if (!d || !total || (cap && (!pos || !val))) { rr::set_last_error("rr_burst_edges: not a burst detector handle / null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(d->device));
+        const std::vector<unsigned long long>& e = d->fetch_edges();
+        *total = e.size();
+        for (size_t j = 0; j < e.size() && j < cap; j++) { pos[j] = (size_t)(e[j] >> 1); val[j] = (unsigned char)(e[j] & 1); }
+    });
+}
 rr_block* rr_rtlsdr_decode_create(void) {
     return make_block([&] { return new rr::RtlSdrDecode(); });
 }

@@ -2225,6 +2225,98 @@ void FmTx::emit(const void* in, void* out, int64_t r, int64_t n_gather, int64_t 
     v.cur ^= 1;
 }
 
+// ---- ComplexToMag2, SinglePoleIirFilter and the burst detector (kernels_burst.hip) ----------------------------------------------
+ComplexToMag2::ComplexToMag2() : Block("ComplexToMag2", 8, 4) {}
+int ComplexToMag2::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed, size_t* produced,
+                            size_t* need, hipStream_t s) {
+    size_t n = 0;
+    const int st = sync_counts(in_len, out_cap, &n, need);
+    prof_begin(s);
+    launch_mag2(static_cast<const cf*>(in), static_cast<float*>(out), (long)n, s);
+    prof_end(s);
+    *consumed = *produced = n;
+    return st;
+}
+IirState::IirState(float alpha, int nrows, hipStream_t s) : rows(nrows) {
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) throw Error("alpha out of range");          // single_pole_iir_filter.rs:38-41 (None)
+    const float one_minus = 1.0f - alpha;                                              // :42-43: the reference's two f32 fields
+    c.a = (double)alpha;
+    c.b = (double)one_minus;
+    std::vector<double> p8(IIR_PW8_N), ps(IIR_PWS_N);
+    for (int k = 0; k < IIR_PW8_N; k++) p8[k] = (double)powl((long double)c.b, (long double)(8L * k));
+    for (int k = 0; k < IIR_PWS_N; k++) ps[k] = (double)powl((long double)c.b, (long double)((long)IIR_SSPAN * k));
+    c.bT = p8[IIR_PW8_N - 1];
+    pw8.upload(p8.data(), p8.size(), s);
+    pws.upload(ps.data(), ps.size(), s);
+    c.pw8 = pw8.p;
+    c.pws = pws.p;
+    for (auto& v : y) { v.reserve(rows); RR_HIP(hipMemsetAsync(v.p, 0, rows * sizeof(double), s)); }   // prev_output: 0 (:25)
+    RR_HIP(hipStreamSynchronize(s));
+}
+SinglePoleIir::SinglePoleIir(float alpha, size_t es)
+    : Block("SinglePoleIirFilter", es == 4 || es == 8 ? es : throw Error("SinglePoleIirFilter: Float or Complex only"), es),
+      st(alpha, es == 8 ? 2 : 1, stream) {
+    zero_copy_in = false;                            // (the scan reads the window twice: tile responses, then the samples)
+}
+int SinglePoleIir::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed, size_t* produced, size_t* need,
+                            hipStream_t s) {
+    size_t n = 0;
+    const int rc = sync_counts(in_len, out_cap, &n, need);
+    if (n) {
+        prof_begin(s);
+        if (in_es == 4)
+            launch_iir_f32(static_cast<const float*>(in), static_cast<float*>(out), (long)n, st.c, st.y[st.cur].p, st.y[st.cur ^ 1].p,
+                           st.scratch(n), s);
+        else
+            launch_iir_c32(static_cast<const cf*>(in), static_cast<cf*>(out), (long)n, st.c, st.y[st.cur].p, st.y[st.cur ^ 1].p,
+                           st.scratch(n), s);
+        prof_end(s);
+        st.cur ^= 1;
+    }
+    *consumed = *produced = n;
+    return rc;
+}
+BurstDetector::BurstDetector(float alpha, float threshold)
+    : Block("ComplexToMag2>SinglePoleIirFilter>BurstTagger", 8, 4), st(alpha, 1, stream), thr(threshold) {
+    zero_copy_in = false;
+    for (auto& f : flag) { f.reserve(1); RR_HIP(hipMemsetAsync(f.p, 0, sizeof(int), stream)); }      // last_state: false (burst_tagger.rs:62)
+    for (auto& k : count) { k.reserve(1); RR_HIP(hipMemsetAsync(k.p, 0, sizeof(unsigned long long), stream)); }
+    RR_HIP(hipStreamSynchronize(stream));
+}
+int BurstDetector::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed, size_t* produced, size_t* need,
+                            hipStream_t s) {
+    size_t n = 0;
+    const int rc = sync_counts(in_len, out_cap, &n, need);
+    edges.clear();
+    fetched = true;                                  // a call that moves nothing has no edges and leaves every state alone
+    if (n) {
+        list.reserve(n);
+        prof_begin(s);
+        // (this call's counter was zeroed by the previous call's launch, or at construction; it zeroes the other one)
+        launch_burst_detector(static_cast<const cf*>(in), static_cast<float*>(out), (long)n, st.c, st.y[st.cur].p, st.y[st.cur ^ 1].p,
+                              st.scratch(n), thr, flag[st.cur].p, flag[st.cur ^ 1].p, count[ccur ^ 1].p, count[ccur].p, list.p, s);
+        prof_end(s);
+        st.cur ^= 1;
+        ccur ^= 1;
+        fetched = false;
+    }
+    *consumed = *produced = n;
+    return rc;
+}
+const std::vector<unsigned long long>& BurstDetector::fetch_edges() {
+    sync();
+    if (!fetched) {
+        unsigned long long total = 0;
+        stage_download_sync(&total, count[ccur].p, sizeof total, stream);
+        if (total > list.cap) throw Error("burst detector: edge count beyond the window");
+        edges.resize((size_t)total);
+        if (total) stage_download_sync(edges.data(), list.p, (size_t)total * sizeof(unsigned long long), stream);
+        std::sort(edges.begin(), edges.end());       // the device appends in no order; the position is the high part
+        fetched = true;
+    }
+    return edges;
+}
+
 // ---- RtlSdrDecode (rtlsdr_decode.rs:9-47) ----------------------------------------------------------------------
 RtlSdrDecode::RtlSdrDecode() : Block("RtlSdrDecode", 1, 8) {}
 int RtlSdrDecode::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed,

@@ -557,6 +557,43 @@ protected:
     void emit(const void* in, void* out, int64_t r, int64_t n_gather, int64_t c0, hipStream_t s) override;
 };
 
+// ComplexToMag2 (complex_to_mag2.rs:8-21): Complex -> re * re + im * im, a sync block.  Bit-exact.
+struct ComplexToMag2 : Block {
+    ComplexToMag2();
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+};
+// SinglePoleIirFilter (single_pole_iir_filter.rs:11-93): y = alpha x + fl32(1 - alpha) y_prev as a tiled f64 scan
+// (kernels_burst.hip).  y_prev stays on the device, one f64 per row (Complex: re, im); the host never reads it.
+struct IirState {
+    IirCoef c{};
+    DevBuf<double> pw8, pws;          // the powers of b the scan combines runs with
+    DevBuf<double> y[2];              // [cur]: y after the last sample of the previous call (0 at start)
+    int cur = 0, rows = 1;
+    DevBuf<double> tiles;             // scan scratch: one double per row and tile of the largest window so far
+    IirState(float alpha, int rows, hipStream_t s);    // throws "alpha out of range" unless 0 <= alpha <= 1
+    double* scratch(size_t n) { tiles.reserve((size_t)rows * ((n + IIR_T - 1) / IIR_T)); return tiles.p; }
+};
+struct SinglePoleIir : Block {
+    IirState st;
+    SinglePoleIir(float alpha, size_t es);
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+};
+// ComplexToMag2 -> SinglePoleIirFilter(alpha) -> the comparison of BurstTagger(threshold) (burst_tagger.rs:68-85) fused
+// (examples/burst_saver.rs:111-123): Complex in, the filtered power out, and per call the list of threshold crossings.
+struct BurstDetector : Block {
+    IirState st;
+    float thr;
+    DevBuf<int> flag[2];                      // [cur]: out > threshold at the last sample of the previous call (false at start)
+    DevBuf<unsigned long long> count[2];      // [ccur]: entries of the most recent call's list
+    int ccur = 0;
+    DevBuf<unsigned long long> list;          // (pos << 1) | cur, unordered; one slot per sample of the largest window so far
+    bool fetched = true;                      // `edges` holds the most recent call's list
+    std::vector<unsigned long long> edges;    // ... ascending
+    BurstDetector(float alpha, float threshold);
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+    const std::vector<unsigned long long>& fetch_edges();   // waits for the most recent call
+};
+
 // RtlSdrDecode (rtlsdr_decode.rs:9-47): stateless u8 pair -> Complex conversion.
 struct RtlSdrDecode : Block {
     RtlSdrDecode();

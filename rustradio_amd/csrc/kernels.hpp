@@ -257,6 +257,32 @@ void launch_vco(const float* in, cf* out, long n, double k, const double* carry_
 void launch_fm_tx(const float* in, cf* out, long r, const float* pending, long n_gather, long I, long D, long c0, double k,
                   const double* carry_in, double* carry_out, double* tiles, hipStream_t s);
 
+// ---- kernels_burst.hip: ComplexToMag2, SinglePoleIirFilter and the burst detector as a tiled f64 scan ------------------------
+// out[i] = (f32) y_i, y_i = a x_i + b y_(i-1) in f64 fma, y_(-1) = *y_in, i < n; *y_out <- y_(n-1).  y_in and y_out are distinct
+// device doubles per row (the block's ping-pong); tiles = device scratch of rows * ceil(n / IIR_T) doubles.  n == 0 launches
+// nothing and leaves *y_out alone.
+constexpr int IIR_T = 2048;                   // samples of one scan tile
+constexpr int IIR_PW8_N = IIR_T / 8 + 1;      // pw8[k] = b^(8 k), k <= IIR_T / 8
+constexpr int IIR_SSPAN = 4 * IIR_T;          // samples one thread of k_iir_scan covers
+constexpr int IIR_PWS_N = 1024 + 1;           // pws[k] = b^(IIR_SSPAN k), k <= 1024
+struct IirCoef {
+    double a, b, bT;                          // alpha and fl32(1 - alpha) widened; b^IIR_T
+    const double* pw8;                        // device tables of IIR_PW8_N / IIR_PWS_N doubles
+    const double* pws;
+};
+void launch_iir_f32(const float* in, float* out, long n, const IirCoef& c, const double* y_in, double* y_out, double* tiles, hipStream_t s);
+// Complex: re and im are two rows of the same launches (y_in / y_out: two doubles)
+void launch_iir_c32(const cf* in, cf* out, long n, const IirCoef& c, const double* y_in, double* y_out, double* tiles, hipStream_t s);
+// x_i = norm_sqr(in[i]) with the reference's three f32 roundings: ComplexToMag2 -> SinglePoleIirFilter on the same scan
+void launch_mag2_iir(const cf* in, float* out, long n, const IirCoef& c, const double* y_in, double* y_out, double* tiles, hipStream_t s);
+// ... and the positions i where (out[i] > thr) differs from (out[i - 1] > thr), out[-1] > thr = *flag_in: entry (i << 1) | cur
+// appended at list[atomicAdd(count)], unordered; *flag_out <- out[n - 1] > thr; *count must be 0 on entry, *count_next is zeroed.
+// list: n slots.
+void launch_burst_detector(const cf* in, float* out, long n, const IirCoef& c, const double* y_in, double* y_out, double* tiles,
+                           float thr, const int* flag_in, int* flag_out, unsigned long long* count, unsigned long long* count_next,
+                           unsigned long long* list, hipStream_t s);
+void launch_mag2(const cf* in, float* out, long n, hipStream_t s);    // out[i] = re * re + im * im, three f32 roundings
+
 // ---- head fix of the fused FirFilter -> FftFilter blocks (stream start only, a few hundred samples) ----------------
 // z[m] = sum_k t1[k] V[voff + m + L1 - 1 - k], m < n: the front FirFilter's first outputs (fir.rs:166-177) from the virtual stream
 void launch_head_z(VSrc<cf> V, long voff, const cf* t1, int L1, cf* z, long n, hipStream_t s);

@@ -30,6 +30,7 @@
 #include <condition_variable>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -817,6 +818,27 @@ public:
     }
 };
 
+// ComplexToMag2 (src/complex_to_mag2.rs:8-21) and SinglePoleIirFilter<Float|Complex> (src/single_pole_iir_filter.rs:11-93): sync
+// blocks.  SinglePoleIirFilter::new_ returns an empty optional for an alpha outside 0..=1 (NaN included), the reference's None.
+class ComplexToMag2 : public SyncBlock<Complex, Float> {
+public:
+    using SyncBlock<Complex, Float>::SyncBlock;
+    static std::pair<std::unique_ptr<ComplexToMag2>, ReadStream<Float>> new_(ReadStream<Complex> src) {
+        auto [w, r] = new_stream<Float>();
+        return {std::make_unique<ComplexToMag2>(rr_complex_to_mag2_create(), std::move(src), std::move(w)), std::move(r)};
+    }
+};
+template <class T> class SinglePoleIirFilter : public SyncBlock<T, T> {
+public:
+    using SyncBlock<T, T>::SyncBlock;
+    static std::optional<std::pair<std::unique_ptr<SinglePoleIirFilter<T>>, ReadStream<T>>> new_(ReadStream<T> src, Float alpha) {
+        if (!(alpha >= 0.0f && alpha <= 1.0f)) return std::nullopt;                // :38-41
+        auto [w, r] = new_stream<T>();
+        return std::make_pair(std::make_unique<SinglePoleIirFilter<T>>(rr_single_pole_iir_create(alpha, sizeof(T)), std::move(src), std::move(w)),
+                              std::move(r));
+    }
+};
+
 // ---- graph-level fusions (one block, one kernel; whole-stream output = the reference blocks in sequence) ------------------
 // Tags: what the reference blocks in sequence would deliver (rr_block_tag_rule) — a chain holding a RationalResampler or a
 // QuadratureDemod drops them, FirFilter -> FftFilter and Hilbert -> FirFilter forward them.
@@ -880,6 +902,53 @@ inline auto AudioChain(ReadStream<Float> src, const std::vector<Float>& taps, si
 struct FmTx {
     static auto new_(ReadStream<Float> src, size_t interp, size_t deci, double k) {
         return Fused<Float, Complex>::make(std::move(src), [&] { return rr_fm_tx_create(interp, deci, detail::f64_bits(k)); });
+    }
+};
+
+// The burst path of examples/burst_saver.rs:111-123 as one block (rr_burst_detector_create): Tee, ComplexToMag2,
+// SinglePoleIirFilter(alpha) and BurstTagger(threshold, tag).  The DATA stream passes through unchanged, as BurstTagger does
+// (src/burst_tagger.rs:68-85); the filtered power stays in a private scratch, and where it crosses the threshold the output
+// gets Tag(pos, tag, Bool(cur)) next to the input's own tags: process_sync_tags in one place.  Feeds StreamToPdu directly.
+// Throws for an alpha outside 0..=1 (where SinglePoleIirFilter::new returns None in the reference's wiring).
+class BurstDetector : public Block {
+    detail::Handle h_;
+    ReadStream<Complex> src_;
+    WriteStream<Complex> dst_;
+    std::string tag_;
+    std::vector<Float> env_;
+    std::vector<size_t> pos_;
+    std::vector<unsigned char> val_;
+public:
+    BurstDetector(rr_block* h, ReadStream<Complex> src, WriteStream<Complex> dst, std::string tag)
+        : h_(h), src_(std::move(src)), dst_(std::move(dst)), tag_(std::move(tag)) {}
+    static std::pair<std::unique_ptr<BurstDetector>, ReadStream<Complex>> new_(ReadStream<Complex> src, Float alpha, Float threshold,
+                                                                               std::string tag) {
+        auto [w, r] = new_stream<Complex>();
+        return {std::make_unique<BurstDetector>(rr_burst_detector_create(alpha, threshold), std::move(src), std::move(w), std::move(tag)),
+                std::move(r)};
+    }
+    const char* block_name() const override { return rr_block_name(h_.h); }
+    bool eof() override { return rr_block_eof(h_.h, src_.eof()) != 0; }
+    BlockRet work() override {
+        auto [input, tags] = src_.read_buf();
+        auto out = dst_.write_buf();
+        if (input.device() || out.device()) throw Error("BurstDetector: host streams only (the data stream is copied on the host)");
+        env_.resize(std::max<size_t>(out.len(), 1));
+        auto w = detail::work(h_.h, input.slice(), input.len(), env_.data(), out.len());     // n = min(in, out) samples
+        std::vector<Tag> keep;
+        for (auto& t : tags) if (t.pos() < w.produced) keep.push_back(t);
+        if (w.produced) {
+            out.fill_from_slice(input.slice(), w.produced);
+            size_t total = 0;
+            if (rr_burst_edges(h_.h, nullptr, nullptr, 0, &total) != 0) throw Error(rr_last_error());
+            pos_.resize(total); val_.resize(total);
+            if (total && rr_burst_edges(h_.h, pos_.data(), val_.data(), total, &total) != 0) throw Error(rr_last_error());
+            for (size_t j = 0; j < total; j++) keep.emplace_back(pos_[j], tag_, val_[j] != 0);
+            std::stable_sort(keep.begin(), keep.end(), [](const Tag& a, const Tag& b) { return a.pos() < b.pos(); });
+        }
+        input.consume(w.consumed);
+        out.produce(w.produced, keep);
+        return w.st == RR_WAIT_DST ? BlockRet::wait(dst_.wait_handle(), w.need) : BlockRet::wait(src_.wait_handle(), w.need);
     }
 };
 
