@@ -289,6 +289,43 @@ rr_block *rr_burst_detector_create(float alpha, float threshold);
  * largest window seen.  RR_ERR for a handle that is not a burst detector. */
 int rr_burst_edges(rr_block *b, size_t *pos, unsigned char *val, size_t cap, size_t *total);
 
+/* The bit-level sync blocks every data receiver of the reference runs after its symbol clock
+ * (examples/ax25-9600-rx.rs:195-204, examples/il2p-1200-rx.rs:118-126).  All are #[rustradio(sync)] / sync_tag: n = min(in_len,
+ * out_cap) samples per call, tags RR_TAGS_FORWARD, 1.  All are exact in integers: bit-identical to the reference, whatever the
+ * split of the stream into calls; the state between calls stays on the device.  One kernel launch per call.
+ * The u8-input blocks are specified for inputs 0 and 1 only (the reference's Descrambler panics on anything else,
+ * src/descrambler.rs:35; here only the lowest bit of a byte is looked at).
+ *
+ * BinarySlicer::new(src) (src/binary_slicer.rs:8-20): f32 in, u8 out, out = x > 0.0, so NaN, -0.0, 0.0 and -Inf give 0. */
+rr_block *rr_binary_slicer_create(void);
+/* NrziDecode::new(src) (src/nrzi.rs:25-42): u8 in, u8 out, out[n] = 1 ^ in[n] ^ in[n-1], in[-1] = 0 at the start of the stream. */
+rr_block *rr_nrzi_decode_create(void);
+/* Descrambler::new(src, mask, seed, len) (src/descrambler.rs:13-39,50-93): u8 in, u8 out, the self-synchronising LFSR
+ * out = parity(shift_reg & mask) ^ in, shift_reg = shift_reg >> 1 | in << len.  G3RUH is (0x21, 0, 16).  NULL + rr_last_error:
+ * "descrambler length out of range" for len >= 64 (the reference asserts), "seed wider than the register" for a seed with a
+ * bit above bit len (a deviation: the reference would let such bits shift down into the mask; no example has one).  Mask bits
+ * above bit len never meet a set bit and are ignored. */
+rr_block *rr_descrambler_create(unsigned long long mask, unsigned long long seed, unsigned len);
+/* CorrelateAccessCodeTag::new(src, code, tag, allowed_diffs) (src/correlate_access_code.rs:58-119): u8 in, the same u8 out; every
+ * position whose last code_len bits differ from the code in at most allowed_diffs places is recorded for rr_bit_tags, once
+ * code_len bits of the stream have been seen.  The code travels packed: bit k of `code` is code[k], code[0] (the oldest bit)
+ * in bit 0.  NULL + rr_last_error: "access code must be nonempty" (the reference's assert), "access code longer than 64 bits". */
+rr_block *rr_correlate_access_code_tag_create(unsigned long long code, unsigned code_len, size_t allowed_diffs);
+/* Graph-level fusion of the chain above: BinarySlicer -> [XorConst(1)] -> [NrziDecode] -> [Descrambler(mask, seed, len)] ->
+ * [CorrelateAccessCodeTag(code, allowed_diffs)], the stages in this order, f32 soft symbols in, u8 bits after the last enabled
+ * stage out.  flags: which optional stages run; mask, seed, len are read only with RR_BITS_DESCRAMBLE; code_len == 0: no
+ * correlator.  Errors as the single blocks, and "unknown bit decoder flags".  Output and tags are bit-identical to the
+ * separate blocks in sequence. */
+enum { RR_BITS_INVERT = 1, RR_BITS_NRZI = 2, RR_BITS_DESCRAMBLE = 4 };
+rr_block *rr_bit_decoder_create(int flags, unsigned long long mask, unsigned long long seed, unsigned len,
+                                unsigned long long code, unsigned code_len, size_t allowed_diffs);
+/* The sync-word tags of the block's most recent work call, ascending: where process_sync_tags pushes Tag(pos, tag, U64(diffs))
+ * (src/correlate_access_code.rs:93-118).  Waits for that call (as rr_block_sync), writes the first min(*total, cap) of them:
+ * pos[j] window-relative, diffs[j] the number of differing bits.  *total = how many there were; pos == NULL with cap == 0
+ * only counts; a call that moved no samples has none.  No tag is ever dropped on the device: its list holds one entry per
+ * sample of the largest window seen.  RR_ERR for a handle without a correlator stage. */
+int rr_bit_tags(rr_block *b, size_t *pos, unsigned char *diffs, size_t cap, size_t *total);
+
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)
  * as wired in examples/ax25-1200-rx.rs:238-247: f32 in, Complex out, ONE decimating FIR with the composite

@@ -60,6 +60,17 @@ unsafe extern "C" {
     // (declared for completeness: the detector's block needs rr_burst_edges too and is not written yet)
     #[allow(dead_code)]
     fn rr_burst_detector_create(alpha: f32, threshold: f32) -> *mut RrBlock;
+    // (the bit-level blocks: declared for completeness, their typed blocks are not written yet — u8 streams and rr_bit_tags)
+    #[allow(dead_code)]
+    fn rr_binary_slicer_create() -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_nrzi_decode_create() -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_descrambler_create(mask: u64, seed: u64, len: c_uint) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_correlate_access_code_tag_create(code: u64, code_len: c_uint, allowed_diffs: usize) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_bit_decoder_create(flags: c_int, mask: u64, seed: u64, len: c_uint, code: u64, code_len: c_uint, allowed_diffs: usize) -> *mut RrBlock;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;

@@ -586,6 +586,77 @@ class BurstDetector(Block):
         return pos[:total.value], val[:total.value].astype(bool)
 
 
+BITS_INVERT, BITS_NRZI, BITS_DESCRAMBLE = 1, 2, 4      # RR_BITS_*
+
+
+def pack_code(code_bits) -> tuple:
+    """a sequence of 0/1 -> (packed, length) as the C ABI takes an access code: bit k of the word is code[k], code[0] the
+    oldest bit.  Longer than 64 bits: the length is passed on and the library says so."""
+    bits = [int(b) for b in code_bits]
+    if any(b not in (0, 1) for b in bits):
+        raise ValueError("access code bits must be 0 or 1")
+    return sum(b << k for k, b in enumerate(bits[:64])), len(bits)
+
+
+class _TagBlock(Block):
+    """a block with a correlator stage: tags() gives the sync-word tags of the most recent work call"""
+
+    def tags(self):
+        """-> (pos: uint64[], diffs: uint8[]) of the most recent work call, ascending, window-relative (rr_bit_tags)"""
+        total = C.c_size_t(0)
+        if lib().rr_bit_tags(self._h, None, None, 0, C.byref(total)) != 0:
+            raise RuntimeError(last_error())
+        pos = np.zeros(max(total.value, 1), np.uint64)
+        diffs = np.zeros(max(total.value, 1), np.uint8)
+        if total.value and lib().rr_bit_tags(self._h, _ptr(pos), _ptr(diffs), total.value, C.byref(total)) != 0:
+            raise RuntimeError(last_error())
+        return pos[:total.value], diffs[:total.value]
+
+
+def BinarySlicer() -> Block:
+    """BinarySlicer::new(src) (src/binary_slicer.rs:8-20): f32 in, u8 out = x > 0.0."""
+    return Block(lib().rr_binary_slicer_create(), np.float32, np.uint8)
+
+
+def NrziDecode() -> Block:
+    """NrziDecode::new(src) (src/nrzi.rs:25-42): u8 in, out[n] = 1 ^ in[n] ^ in[n-1]."""
+    return Block(lib().rr_nrzi_decode_create(), np.uint8, np.uint8)
+
+
+class Descrambler(Block):
+    """Descrambler::new(src, mask, seed, len) (src/descrambler.rs:50-93): u8 in, u8 out, the self-synchronising LFSR."""
+
+    def __init__(self, mask: int, seed: int, length: int):
+        super().__init__(lib().rr_descrambler_create(int(mask), int(seed), int(length)), np.uint8, np.uint8)
+
+    @classmethod
+    def g3ruh(cls):
+        """Descrambler::g3ruh (src/descrambler.rs:78-88): mask 0x21, seed 0, length 16"""
+        return cls(0x21, 0, 16)
+
+
+class CorrelateAccessCodeTag(_TagBlock):
+    """CorrelateAccessCodeTag::new(src, code, tag, allowed_diffs) (src/correlate_access_code.rs:58-119): u8 in, the same u8
+    out; tags() gives where the last len(code) bits matched."""
+
+    def __init__(self, code_bits, allowed_diffs: int = 0):
+        code, n = pack_code(code_bits)
+        super().__init__(lib().rr_correlate_access_code_tag_create(code, n, int(allowed_diffs)), np.uint8, np.uint8)
+
+
+class BitDecoder(_TagBlock):
+    """BinarySlicer -> [XorConst(1)] -> [NrziDecode] -> [Descrambler] -> [CorrelateAccessCodeTag] fused into one block and
+    one kernel launch per call (rr_bit_decoder_create; examples/ax25-9600-rx.rs:195-204, examples/il2p-1200-rx.rs:118-126):
+    f32 soft symbols in, u8 bits out.  descrambler: (mask, seed, length) or None; code: a sequence of 0/1 or None."""
+
+    def __init__(self, invert: bool = False, nrzi: bool = False, descrambler=None, code=None, allowed_diffs: int = 0):
+        flags = (BITS_INVERT if invert else 0) | (BITS_NRZI if nrzi else 0) | (BITS_DESCRAMBLE if descrambler is not None else 0)
+        mask, seed, length = descrambler if descrambler is not None else (0, 0, 0)
+        packed, n = pack_code(code) if code is not None else (0, 0)
+        super().__init__(lib().rr_bit_decoder_create(flags, int(mask), int(seed), int(length), packed, n, int(allowed_diffs)),
+                         np.float32, np.uint8)
+
+
 def FmChainU8(taps, interp: int, deci: int, gain: float = 1.0, mode: int = ATAN2_EXACT) -> Block:
     """RtlSdrDecode -> FmChain fused (examples/rtl_fm.rs:328-419): RTL-SDR bytes in, f32 out; windows,
     consumed and the WAIT_SRC need count bytes."""

@@ -222,6 +222,47 @@ int rr_burst_edges(rr_block* b, size_t* pos, unsigned char* val, size_t cap, siz
         for (size_t j = 0; j < e.size() && j < cap; j++) { pos[j] = (size_t)(e[j] >> 1); val[j] = (unsigned char)(e[j] & 1); }
     });
 }
+// the bit-level blocks: parameter errors are said before any device is touched
+static rr_block* make_bits(const char* nm, bool f32src, int flags, unsigned long long mask, unsigned long long seed, unsigned len,
+                           unsigned long long code, unsigned code_len, size_t allowed_diffs) {
+    if (const char* e = rr::bits_check(flags, seed, len, code_len)) {
+        rr::set_build_opts(nullptr);
+        rr::set_last_error(e);
+        return nullptr;
+    }
+    return make_block([&] { return new rr::BitDecoder(nm, f32src, flags, mask, seed, len, code, code_len, allowed_diffs); },
+                      RR_TAGS_FORWARD, 1);
+}
+rr_block* rr_binary_slicer_create(void) { return make_bits("BinarySlicer", true, 0, 0, 0, 0, 0, 0, 0); }
+rr_block* rr_nrzi_decode_create(void) { return make_bits("NrziDecode", false, RR_BITS_NRZI, 0, 0, 0, 0, 0, 0); }
+rr_block* rr_descrambler_create(unsigned long long mask, unsigned long long seed, unsigned len) {
+    return make_bits("Descrambler", false, RR_BITS_DESCRAMBLE, mask, seed, len, 0, 0, 0);
+}
+rr_block* rr_correlate_access_code_tag_create(unsigned long long code, unsigned code_len, size_t allowed_diffs) {
+    if (code_len == 0) {                             // correlate_access_code.rs:79 (assert)
+        rr::set_build_opts(nullptr);
+        rr::set_last_error("access code must be nonempty");
+        return nullptr;
+    }
+    return make_bits("CorrelateAccessCodeTag", false, 0, 0, 0, 0, code, code_len, allowed_diffs);
+}
+rr_block* rr_bit_decoder_create(int flags, unsigned long long mask, unsigned long long seed, unsigned len, unsigned long long code,
+                                unsigned code_len, size_t allowed_diffs) {
+    return make_bits("BitDecoder", true, flags, mask, seed, len, code, code_len, allowed_diffs);
+}
+int rr_bit_tags(rr_block* b, size_t* pos, unsigned char* diffs, size_t cap, size_t* total) {
+    auto* d = b ? dynamic_cast<rr::BitDecoder*>(b->b.get()) : nullptr;
+    if (!d || !d->has_correlator() || !total || (cap && (!pos || !diffs))) {
+        rr::set_last_error("rr_bit_tags: not a handle with a correlator stage / null argument");
+        return RR_ERR;
+    }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(d->device));
+        const std::vector<unsigned long long>& e = d->fetch_tags();
+        *total = e.size();
+        for (size_t j = 0; j < e.size() && j < cap; j++) { pos[j] = (size_t)(e[j] >> 8); diffs[j] = (unsigned char)(e[j] & 0xff); }
+    });
+}
 rr_block* rr_rtlsdr_decode_create(void) {
     return make_block([&] { return new rr::RtlSdrDecode(); });
 }

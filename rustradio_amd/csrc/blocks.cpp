@@ -2317,6 +2317,83 @@ const std::vector<unsigned long long>& BurstDetector::fetch_edges() {
     return edges;
 }
 
+// ---- BinarySlicer, NrziDecode, Descrambler, CorrelateAccessCodeTag and their fusion (kernels_bits.hip) ---------------------------
+const char* bits_check(int flags, unsigned long long seed, unsigned len, unsigned code_len) {
+    if (flags & ~(RR_BITS_INVERT | RR_BITS_NRZI | RR_BITS_DESCRAMBLE)) return "unknown bit decoder flags";
+    if (flags & RR_BITS_DESCRAMBLE) {
+        if (len >= 64) return "descrambler length out of range";                       // descrambler.rs:22 (assert)
+        if (len < 63 && seed >> (len + 1)) return "seed wider than the register";
+    }
+    if (code_len > 64) return "access code longer than 64 bits";
+    return nullptr;
+}
+BitDecoder::BitDecoder(const char* nm, bool f32src, int flags, unsigned long long mask, unsigned long long seed, unsigned len,
+                       unsigned long long code, unsigned code_len, size_t allowed_diffs)
+    : Block(nm, f32src ? 4 : 1, 1) {
+    if (const char* e = bits_check(flags, seed, len, code_len)) throw Error(e);
+    cfg.invert = flags & RR_BITS_INVERT ? 1 : 0;
+    cfg.nrzi = flags & RR_BITS_NRZI ? 1 : 0;
+    unsigned long long init[BITS_ST_N] = {0, 0, 0, 0};                                // last: 0 (nrzi.rs:32-33); nothing seen
+    if (flags & RR_BITS_DESCRAMBLE) {
+        // shift_reg holds d[n-1-k] in bit len-k (descrambler.rs:37), so mask bit j reads d[n - delta], delta = 1 + len - j;
+        // before the stream the register is the seed: d[-1-k] = bit len-k of it
+        for (unsigned j = 0; j <= len; j++)
+            if (mask >> j & 1) cfg.dmask |= 1ull << (len - j);
+        init[BITS_ST_DHIST] = seed << (63 - len);
+    }
+    cfg.L = (int)code_len;
+    cfg.code = code_len == 64 ? code : code & ((1ull << code_len) - 1ull);
+    cfg.allowed = (unsigned)std::min<size_t>(allowed_diffs, 64);
+    st[0].upload(init, BITS_ST_N, stream);
+    st[1].reserve(BITS_ST_N);
+    total.reserve(1);
+    zero_copy_in = false;                            // (tiles re-read their 128 samples of history, and a misaligned window is read one
+                                                     //  sample per lane: a page-locked host window is copied down first)
+    RR_HIP(hipStreamSynchronize(stream));
+}
+int BitDecoder::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed, size_t* produced, size_t* need,
+                         hipStream_t s) {
+    size_t n = 0;
+    const int rc = sync_counts(in_len, out_cap, &n, need);
+    tags.clear();
+    fetched = true;                                  // a call that moves nothing has no tags and leaves every state alone
+    if (n) {
+        const size_t ntiles = (n + BITS_T - 1) / BITS_T;
+        if (cfg.L) { tilecnt.reserve(ntiles); list.reserve(ntiles * BITS_T); }
+        prof_begin(s);
+        if (in_es == 4)
+            launch_bits_f32(static_cast<const float*>(in), static_cast<unsigned char*>(out), (long)n, cfg, st[cur].p, st[cur ^ 1].p,
+                            tilecnt.p, list.p, s);
+        else
+            launch_bits_u8(static_cast<const unsigned char*>(in), static_cast<unsigned char*>(out), (long)n, cfg, st[cur].p,
+                           st[cur ^ 1].p, tilecnt.p, list.p, s);
+        prof_end(s);
+        cur ^= 1;
+        if (cfg.L) { last_tiles = ntiles; fetched = false; }
+    }
+    *consumed = *produced = n;
+    return rc;
+}
+const std::vector<unsigned long long>& BitDecoder::fetch_tags() {
+    sync();
+    if (!fetched) {
+        // the tiles' entries without the gaps between them, in two small launches; tiles and the entries of a tile are ascending
+        offs.reserve(last_tiles);
+        launch_bits_tag_offsets(tilecnt.p, (long)last_tiles, offs.p, total.p, stream);
+        unsigned long long nt = 0;
+        stage_download_sync(&nt, total.p, sizeof nt, stream);
+        if (nt > last_tiles * (size_t)BITS_T) throw Error("bit decoder: tag count beyond the window");
+        tags.resize((size_t)nt);
+        if (nt) {
+            packed.reserve((size_t)nt);
+            launch_bits_tag_gather(tilecnt.p, offs.p, list.p, (long)last_tiles, packed.p, stream);
+            stage_download_sync(tags.data(), packed.p, (size_t)nt * sizeof(unsigned long long), stream);
+        }
+        fetched = true;
+    }
+    return tags;
+}
+
 // ---- RtlSdrDecode (rtlsdr_decode.rs:9-47) ----------------------------------------------------------------------
 RtlSdrDecode::RtlSdrDecode() : Block("RtlSdrDecode", 1, 8) {}
 int RtlSdrDecode::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed,

@@ -594,6 +594,30 @@ struct BurstDetector : Block {
     const std::vector<unsigned long long>& fetch_edges();   // waits for the most recent call
 };
 
+// The bit-level sync blocks (kernels_bits.hip): BinarySlicer (binary_slicer.rs:17-19), XorConst(1), NrziDecode
+// (nrzi.rs:36-41), Descrambler (descrambler.rs:34-39), CorrelateAccessCodeTag (correlate_access_code.rs:93-118) — any subset,
+// in that order, as ONE kernel.  f32 in (the slicer is then the first stage) or u8 in; u8 out.  The state between calls
+// (BITS_ST_*) stays on the device; the host reads only the tag list, and only when asked.
+struct BitDecoder : Block {
+    BitsCfg cfg{};
+    DevBuf<unsigned long long> st[2];         // [cur]: what the stream so far left behind
+    int cur = 0;
+    DevBuf<unsigned> tilecnt;                 // tags of every tile of the most recent call
+    DevBuf<unsigned long long> list;          // (pos << 8) | diffs: tile t's at [t BITS_T ..), BITS_T slots each; grows with the window
+    DevBuf<unsigned long long> offs, total, packed;   // rr_bit_tags: the entries before each tile, their sum, the list without gaps
+    size_t last_tiles = 0;                    // tiles of the most recent call
+    bool fetched = true;                      // `tags` holds the most recent call's list
+    std::vector<unsigned long long> tags;     // ... ascending
+    // f32src: the slicer in front.  code_len == 0: no correlator.  Throws on the parameter errors of bits_check().
+    BitDecoder(const char* nm, bool f32src, int flags, unsigned long long mask, unsigned long long seed, unsigned len,
+               unsigned long long code, unsigned code_len, size_t allowed_diffs);
+    bool has_correlator() const { return cfg.L != 0; }
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+    const std::vector<unsigned long long>& fetch_tags();    // waits for the most recent call
+};
+// nullptr, or what is wrong with the parameters (said before any device is touched)
+const char* bits_check(int flags, unsigned long long seed, unsigned len, unsigned code_len);
+
 // RtlSdrDecode (rtlsdr_decode.rs:9-47): stateless u8 pair -> Complex conversion.
 struct RtlSdrDecode : Block {
     RtlSdrDecode();

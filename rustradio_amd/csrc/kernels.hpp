@@ -283,6 +283,35 @@ void launch_burst_detector(const cf* in, float* out, long n, const IirCoef& c, c
                            unsigned long long* list, hipStream_t s);
 void launch_mag2(const cf* in, float* out, long n, hipStream_t s);    // out[i] = re * re + im * im, three f32 roundings
 
+// ---- kernels_bits.hip: BinarySlicer, XorConst(1), NrziDecode, Descrambler and CorrelateAccessCodeTag as one tile kernel -------
+// out[i] = the bit after the last enabled stage, one u8 (0 / 1) per sample, i < n; ONE launch.  st_in / st_out: distinct
+// device arrays of BITS_ST_N words (the block's ping-pong): what the stream before the window left, and what this window
+// leaves.  With L != 0: for every i whose last L bits differ from the code in <= allowed places once L bits of the stream have
+// been seen, an entry (i << 8) | diffs; tile t (BITS_T samples) writes its entries, ascending, to list[t BITS_T ..) and their
+// number to tilecnt[t]: ceil(n / BITS_T) counters, as many times BITS_T slots.  No atomics.  n == 0 launches nothing and
+// leaves *st_out alone.  launch_bits_tag_offsets / _gather close the gaps: offs[t] = the entries before tile t, *total = all,
+// out[0 .. total) = the entries in ascending order.
+constexpr int BITS_T = 4096;                  // samples of one tile
+enum { BITS_ST_RLAST = 0,                     // r[-1]: the last sliced (and inverted) bit; 0 at the start (nrzi.rs:32-33)
+       BITS_ST_DHIST = 1,                     // bit 63 - k = d[-1 - k]: the last 64 bits in front of the descrambler
+       BITS_ST_SHIST = 2,                     // bit 63 - k = s[-1 - k]: the last 64 bits in front of the correlator
+       BITS_ST_SEEN = 3,                      // bits of the stream so far, saturating at 64
+       BITS_ST_N = 4 };
+struct BitsCfg {
+    int invert, nrzi;                         // XorConst(1); NrziDecode
+    unsigned long long dmask;                 // bit (delta - 1) set: s[n] ^= d[n - delta], delta = 1 .. 64; 0 = no descrambler
+    unsigned long long code;                  // bit k = code[k], code[0] the oldest
+    int L;                                    // code length 1 .. 64; 0 = no correlator
+    unsigned allowed;
+};
+void launch_bits_f32(const float* in, unsigned char* out, long n, const BitsCfg& c, const unsigned long long* st_in,
+                     unsigned long long* st_out, unsigned* tilecnt, unsigned long long* list, hipStream_t s);
+void launch_bits_u8(const unsigned char* in, unsigned char* out, long n, const BitsCfg& c, const unsigned long long* st_in,
+                    unsigned long long* st_out, unsigned* tilecnt, unsigned long long* list, hipStream_t s);
+void launch_bits_tag_offsets(const unsigned* tilecnt, long ntiles, unsigned long long* offs, unsigned long long* total, hipStream_t s);
+void launch_bits_tag_gather(const unsigned* tilecnt, const unsigned long long* offs, const unsigned long long* list, long ntiles,
+                            unsigned long long* out, hipStream_t s);
+
 // ---- head fix of the fused FirFilter -> FftFilter blocks (stream start only, a few hundred samples) ----------------
 // z[m] = sum_k t1[k] V[voff + m + L1 - 1 - k], m < n: the front FirFilter's first outputs (fir.rs:166-177) from the virtual stream
 void launch_head_z(VSrc<cf> V, long voff, const cf* t1, int L1, cf* z, long n, hipStream_t s);

@@ -839,6 +839,102 @@ public:
     }
 };
 
+// ---- the bit-level sync blocks behind a symbol clock (examples/ax25-9600-rx.rs:195-204, examples/il2p-1200-rx.rs:118-126) -----
+// BinarySlicer (src/binary_slicer.rs:8-20), NrziDecode (src/nrzi.rs:25-42), Descrambler (src/descrambler.rs:50-93) are sync
+// blocks; CorrelateAccessCodeTag (src/correlate_access_code.rs:58-119) is a sync_tag block: the data passes through and every
+// match adds Tag(pos, tag, U64(diffs)) BEHIND the input's own tags at that position, as process_sync_tags orders them.
+// BitDecoder is the fusion of all of them (rr_bit_decoder_create).  A constructor the C ABI refuses throws its message.
+class BinarySlicer : public SyncBlock<Float, uint8_t> {
+public:
+    using SyncBlock<Float, uint8_t>::SyncBlock;
+    static std::pair<std::unique_ptr<BinarySlicer>, ReadStream<uint8_t>> new_(ReadStream<Float> src) {
+        auto [w, r] = new_stream<uint8_t>();
+        return {std::make_unique<BinarySlicer>(rr_binary_slicer_create(), std::move(src), std::move(w)), std::move(r)};
+    }
+};
+class NrziDecode : public SyncBlock<uint8_t, uint8_t> {
+public:
+    using SyncBlock<uint8_t, uint8_t>::SyncBlock;
+    static std::pair<std::unique_ptr<NrziDecode>, ReadStream<uint8_t>> new_(ReadStream<uint8_t> src) {
+        auto [w, r] = new_stream<uint8_t>();
+        return {std::make_unique<NrziDecode>(rr_nrzi_decode_create(), std::move(src), std::move(w)), std::move(r)};
+    }
+};
+class Descrambler : public SyncBlock<uint8_t, uint8_t> {
+public:
+    using SyncBlock<uint8_t, uint8_t>::SyncBlock;
+    static std::pair<std::unique_ptr<Descrambler>, ReadStream<uint8_t>> new_(ReadStream<uint8_t> src, uint64_t mask, uint64_t seed,
+                                                                              unsigned len) {
+        auto [w, r] = new_stream<uint8_t>();
+        return {std::make_unique<Descrambler>(rr_descrambler_create(mask, seed, len), std::move(src), std::move(w)), std::move(r)};
+    }
+    static std::pair<std::unique_ptr<Descrambler>, ReadStream<uint8_t>> g3ruh(ReadStream<uint8_t> src) {      // :78-88
+        return new_(std::move(src), 0x21, 0, 16);
+    }
+};
+namespace detail {
+// an access code as the C ABI takes it: bit k of the word = code[k], code[0] the oldest bit; the length goes along unclipped
+inline unsigned long long pack_code(const std::vector<uint8_t>& code) {
+    unsigned long long w = 0;
+    for (size_t k = 0; k < code.size(); k++) {
+        if (code[k] > 1) throw Error("access code bits must be 0 or 1");
+        if (k < 64) w |= (unsigned long long)code[k] << k;
+    }
+    return w;
+}
+// a sync block whose handle has a correlator stage: the forwarded input tags, then the handle's own (rr_bit_tags)
+template <class In> class SyncTagBlock : public SyncBlock<In, uint8_t> {
+    std::string tag_;
+    bool corr_;
+    std::vector<size_t> pos_;
+    std::vector<unsigned char> diffs_;
+public:
+    SyncTagBlock(rr_block* h, ReadStream<In> src, WriteStream<uint8_t> dst, std::string tag, bool corr)
+        : SyncBlock<In, uint8_t>(h, std::move(src), std::move(dst)), tag_(std::move(tag)), corr_(corr) {}
+    BlockRet work() override {
+        auto [input, tags] = this->src_.read_buf();
+        auto out = this->dst_.write_buf();
+        auto w = detail::work(this->h_.h, input, out);
+        std::vector<Tag> keep;
+        for (auto& t : tags) if (t.pos() < w.produced) keep.push_back(t);
+        if (corr_ && w.produced) {
+            size_t total = 0;
+            if (rr_bit_tags(this->h_.h, nullptr, nullptr, 0, &total) != 0) throw Error(rr_last_error());
+            pos_.resize(total); diffs_.resize(total);
+            if (total && rr_bit_tags(this->h_.h, pos_.data(), diffs_.data(), total, &total) != 0) throw Error(rr_last_error());
+            for (size_t j = 0; j < total; j++) keep.emplace_back(pos_[j], tag_, (uint64_t)diffs_[j]);
+            std::stable_sort(keep.begin(), keep.end(), [](const Tag& a, const Tag& b) { return a.pos() < b.pos(); });
+        }
+        input.consume(w.consumed);
+        out.produce(w.produced, keep);
+        return w.st == RR_WAIT_DST ? BlockRet::wait(this->dst_.wait_handle(), w.need) : BlockRet::wait(this->src_.wait_handle(), w.need);
+    }
+};
+}  // namespace detail
+class CorrelateAccessCodeTag : public detail::SyncTagBlock<uint8_t> {
+public:
+    using detail::SyncTagBlock<uint8_t>::SyncTagBlock;
+    static std::pair<std::unique_ptr<CorrelateAccessCodeTag>, ReadStream<uint8_t>> new_(ReadStream<uint8_t> src, const std::vector<uint8_t>& code,
+                                                                                         std::string tag, size_t allowed_diffs) {
+        auto [w, r] = new_stream<uint8_t>();
+        rr_block* h = rr_correlate_access_code_tag_create(detail::pack_code(code), (unsigned)code.size(), allowed_diffs);
+        return {std::make_unique<CorrelateAccessCodeTag>(h, std::move(src), std::move(w), std::move(tag), true), std::move(r)};
+    }
+};
+// flags: RR_BITS_INVERT | RR_BITS_NRZI | RR_BITS_DESCRAMBLE; mask, seed, len are read only with RR_BITS_DESCRAMBLE; an empty code:
+// no correlator and no tags of its own
+class BitDecoder : public detail::SyncTagBlock<Float> {
+public:
+    using detail::SyncTagBlock<Float>::SyncTagBlock;
+    static std::pair<std::unique_ptr<BitDecoder>, ReadStream<uint8_t>> new_(ReadStream<Float> src, int flags, uint64_t mask, uint64_t seed,
+                                                                             unsigned len, const std::vector<uint8_t>& code, std::string tag,
+                                                                             size_t allowed_diffs) {
+        auto [w, r] = new_stream<uint8_t>();
+        rr_block* h = rr_bit_decoder_create(flags, mask, seed, len, detail::pack_code(code), (unsigned)code.size(), allowed_diffs);
+        return {std::make_unique<BitDecoder>(h, std::move(src), std::move(w), std::move(tag), !code.empty()), std::move(r)};
+    }
+};
+
 // ---- graph-level fusions (one block, one kernel; whole-stream output = the reference blocks in sequence) ------------------
 // Tags: what the reference blocks in sequence would deliver (rr_block_tag_rule) — a chain holding a RationalResampler or a
 // QuadratureDemod drops them, FirFilter -> FftFilter and Hilbert -> FirFilter forward them.
