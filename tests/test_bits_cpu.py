@@ -98,6 +98,48 @@ def test_vectorised_chain_equals_the_sequential_one():
         assert np.array_equal(vb, bits) and np.array_equal(vp, pos) and np.array_equal(vd, diffs)
 
 
+# ---- the generator of tests/test_gpu_bits_fuzz.py, held to its own conditions ------------------------------------------------------
+def test_fuzz_generator_meets_its_conditions():
+    from test_gpu_bits_fuzz import (CODE_LENS, DESCRAMBLER_LENS, ONES_FIRST, SEEDS, fuzz_case, moving_calls, nrzi_inverse,
+                                    unscramble_inverse)
+    assert len(SEEDS) == 48
+    d = np.random.default_rng(1).integers(0, 2, 300).tolist()
+    assert Lfsr(0x8000000000000001, 5, 63).run(unscramble_inverse(d, 0x8000000000000001, 5, 63)) == d
+    assert Nrzi().run(nrzi_inverse(d)) == d
+    with_tags = quiet_call = long_hard = short = singles = past_64 = 0
+    lens, dlens, alloweds = set(), set(), set()
+    for seed in SEEDS:
+        c = fuzz_case(seed)
+        n, L = c["n"], c["L"]
+        assert len(c["x"]) == len(c["bits"]) == n and 1 <= n <= 3 * 4096 + 200
+        assert np.array_equal(c["bits"], c["s"])                  # the stream decodes to the bits that were drawn and planted
+        assert [p for p, _ in c["tags"]] == sorted({p for p, _ in c["tags"]}) and all(L - 1 <= p < n for p, _ in c["tags"])
+        found = dict(c["tags"])
+        for start in c["plants"]:                                 # a planted code is a certain match
+            assert found.get(start + L - 1, 99) <= min(c["allowed"], L), (seed, start)
+        calls = moving_calls(c["windows"], n)
+        assert calls[:min(ONES_FIRST, n)] == [(i, i + 1) for i in range(min(ONES_FIRST, n))]
+        assert [b for _, b, _, _ in c["dev"]][-1] == n and c["dev"][0][0] == 0
+        with_tags += bool(c["tags"])
+        quiet_call += any(not any(a <= p < b for p in found) for a, b in calls)
+        if L:
+            lens.add(L); alloweds.add(min(c["allowed"], 65))
+            if c["cut"] is not None and len(c["plants"]) == 3:    # one at the start, one across the tile seam, one across a call cut
+                assert c["plants"][0] == 0 and c["plants"][1] <= 4096 < c["plants"][1] + L and c["plants"][2] < c["cut"] <= c["plants"][2] + L
+                assert any(b == c["cut"] for _, b in calls)
+                past_64 += L > 8
+        if c["descrambler"] is not None:
+            dlens.add(c["descrambler"][2])
+        long_hard += L >= 33 and c["nrzi"] and c["descrambler"] is not None and c["descrambler"][2] == 63 and len(c["plants"]) == 3
+        short += 1 <= L <= 32
+        singles += c["single"] is not None
+    print(f"{with_tags} cases with tags, {quiet_call} with a call without, code lengths {sorted(lens)}, descrambler lengths "
+          f"{sorted(dlens)}, allowed {sorted(alloweds)}, {singles} single-stage, {past_64} with L > 8 and all three plants")
+    assert with_tags >= 12 and quiet_call >= 12 and long_hard >= 1 and short >= 1
+    assert lens == set(CODE_LENS) and dlens == set(DESCRAMBLER_LENS) and alloweds >= {0, 1, 3, 65}
+    assert singles >= 5 and past_64 >= 5
+
+
 # ---- public surface ----------------------------------------------------------------------------------------------------------
 _U64, _UINT, _SZ = ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_size_t
 

@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 import rustradio_amd as rr
-from burst_model import (bound_gpu, bound_ref, burst_signal, coefficients, edges, iir_ref_f32, iir_truth, iir_truth_const,
-                         mag2_f32)
+from burst_model import (bound_gpu, bound_gpu_any, bound_ref, bound_terms_any, burst_signal, coefficients, edges, iir_ref_f32,
+                         iir_truth, iir_truth_const, iir_truth_ld, ld_truth_error, mag2_f32, state_size)
 
 
 def test_reference_tag_it_through_the_model():
@@ -103,6 +103,87 @@ def test_no_sample_of_the_burst_signal_is_ambiguous(alpha, nedges):
     pm, vm = edges(t.astype(np.float32), thr)
     assert np.array_equal(pr, pm) and np.array_equal(vr, vm)
     assert len(pr) == nedges and vr.tolist() == [True, False] * (nedges // 2)
+
+
+# ---- the bound for every alpha (bound_gpu_any) is satisfiable, not loose, and never looser than bound_gpu -------------------------
+T = 2048
+_ALPHAS_ANY = [0.3, 1e-3, 2.0 ** -12, 1e-5, 0.6 * 2.0 ** -24, 2.0 ** -26, 0.999, 1.0 - 2.0 ** -24]
+
+
+def dc_noise(n, seed):
+    """0.5 + U(-0.5, 0.5): the DC keeps |t| away from zero, so the cast term is what a result is held to"""
+    return (0.5 + np.random.default_rng(seed).uniform(-0.5, 0.5, n)).astype(np.float32)
+
+
+def emulate_tile_tree(x, alpha):
+    """The shape of the GPU's tree in f64 on the CPU, with MORE roundings than the kernel (multiply and add rounded
+    separately where it has one fma): 8 samples per thread folded from zero, a Hillis-Steele scan over the 256 threads of a
+    tile with pw8[k] = b^(8k) (long double, rounded once), y_in = base pw8[thread] + prefix, the fold again from y_in, one
+    cast; tile bases sequentially, base' = base b^T + the tile's response.  One call from a zero state -> float32 outputs."""
+    a, b = coefficients(alpha)
+    pw8 = np.power(np.longdouble(b), np.arange(257, dtype=np.float64).astype(np.longdouble) * 8).astype(np.float64)
+    n = len(x)
+    xs = np.zeros((n + T - 1) // T * T)
+    xs[:n] = np.asarray(x, np.float32)
+    out, base, k = np.empty(len(xs)), 0.0, np.arange(256)
+    for t0 in range(0, len(xs), T):
+        v = xs[t0:t0 + T].reshape(256, 8)
+        r = np.zeros(256)
+        for i in range(8):
+            r = b * r + a * v[:, i]
+        inc, off = r.copy(), 1
+        while off < 256:
+            u = np.concatenate([np.zeros(off), inc[:-off]])
+            inc = np.where(k >= off, u * pw8[off] + inc, inc)
+            off *= 2
+        y = base * pw8[k] + np.concatenate([[0.0], inc[:-1]])
+        for i in range(8):
+            y = b * y + a * v[:, i]
+            out[t0 + i:t0 + T:8] = y
+        base = base * pw8[256] + inc[255]
+    return out[:n].astype(np.float32)
+
+
+def test_long_double_has_64_bits():
+    assert np.finfo(np.longdouble).eps < 2.0 ** -60
+    x = dc_noise(500, 1)
+    assert np.max(np.abs(iir_truth_ld(x, 0.1)[0].astype(np.float64) - iir_truth(x, 0.1)[0])) <= 2.0 ** -53 * 4.0 / 0.1
+    assert float(iir_truth_ld(x, 0.1)[1]) == float(iir_truth_ld(x, 0.1)[0][-1])
+
+
+@pytest.mark.parametrize("alpha", _ALPHAS_ANY, ids=lambda a: f"{a:.9g}")
+def test_any_alpha_bound_is_satisfiable_and_not_loose(alpha):
+    """a correct tree fits the bound at every alpha, and the bound is at f32-ulp level everywhere: the f64 term stays far
+    below the cast term, and the worst sample uses most of the allowance"""
+    x = dc_noise(3 * T + 17, 40)
+    t = iir_truth_ld(x, alpha)[0]
+    y = emulate_tile_tree(x, alpha)
+    cast, f64 = bound_terms_any(t, x, alpha)
+    d = np.abs(y.astype(np.longdouble) - t).astype(np.float64)
+    allow = cast + f64 + ld_truth_error(x, alpha)
+    worst, ratio = float(np.max(d / allow)), float(np.median(f64 / cast))
+    print(f"alpha {alpha:.6g}: emulated tree uses {worst:.3f} of bound_gpu_any, f64 term / cast term {ratio:.2e}")
+    assert np.all(d <= allow)
+    assert worst > 0.9 and ratio < 1e-3
+    assert float(np.median(ld_truth_error(x, alpha) / cast)) < 1e-6                # the truth's own error blurs nothing
+
+
+@pytest.mark.parametrize("alpha", [0.01, 0.3, 0.999])
+def test_any_alpha_bound_is_never_looser_than_bound_gpu(alpha):
+    x = dc_noise(3 * T + 17, 41)
+    t = iir_truth(x, alpha)[0]
+    for calls in (1, 7, 10_000):
+        assert np.all(bound_gpu_any(t, x, alpha, calls) <= bound_gpu(t, float(np.max(np.abs(x))), alpha) * (1 + 1e-6))
+
+
+def test_any_alpha_bound_at_the_ends():
+    x = dc_noise(100, 42)
+    a0, a1 = bound_terms_any(np.zeros(100), x, 0.0), bound_terms_any(x, x, 1.0, calls=3)
+    assert np.all(a0[0] == 2.0 ** -150) and not a0[1].any()                        # alpha 0: the state is 0, only the floor
+    assert np.all(a1[1] <= 2.0 ** -53 * 68.0)                                      # alpha 1: b = 0, M = X, R = 64 + 4
+    assert state_size(x, 2.0 ** -26)[-1] == float(np.max(x)) * 2.0 ** -26 * 100    # b == 1: a plain sum
+    sub = np.full(4, 2.0 ** -149, np.float32)
+    assert np.all(bound_gpu_any(iir_truth(sub, 0.5)[0], sub, 0.5) < 2.0 ** -149)   # a subnormal result: under one ulp
 
 
 def test_public_surface():

@@ -244,7 +244,7 @@ def test_descrambler_parameters(mask, seed, length):
 
 
 # ---- 4. the correlator ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("L", [1, 2, 8, 32, 63, 64])
+@pytest.mark.parametrize("L", [1, 2, 8, 31, 32, 33, 63, 64])
 @pytest.mark.parametrize("allowed", [0, 3, "L"])
 def test_correlator_lengths(L, allowed):
     rng = np.random.default_rng(100 + L)
