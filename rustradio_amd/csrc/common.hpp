@@ -131,9 +131,44 @@ template <class T, class SRC> __device__ __forceinline__ void carry_store(const 
 #if defined(__HIP_DEVICE_COMPILE__)
 template <class T> using gptr = const T __attribute__((address_space(1)))*;
 template <class T> __device__ __forceinline__ gptr<T> as_global(const T* p) { return (gptr<T>)p; }
+template <class T> using gptr_w = T __attribute__((address_space(1)))*;
+// Scalar-base form of the same: a WORKGROUP-UNIFORM base address held in a scalar register pair, and each lane's element
+// addressed as base + one 32-bit lane offset (loop-invariant: thread index * element size) + an immediate — the
+// `global_* v, v_off, s[base:base+1] offset:imm` encoding.  Left to itself hipcc adds the lane offset to the base as a 64-bit
+// VECTOR add per tile (+ a carry pair per 4 KiB of rows, + the address register pairs that live across the tile loop).
+// The empty asm pins the base to scalar registers and keeps the optimiser from folding two bases of one tile back into one
+// vector address; it emits nothing.  `imm` must fit the instruction's 13-bit signed field ([-4096, 4096) bytes): callers
+// take one base per 4 KiB of rows and advance it with scalar adds.
+__device__ __forceinline__ const char* scalar_base(const void* p) {
+    const char* c = static_cast<const char*>(p);
+    asm("" : "+s"(c));
+    return c;
+}
+// (The lane offset reaches the address as a 32-bit value of the SAME basic block as the memory operation: instruction
+//  selection works block by block, and a zero-extension hoisted out of the tile loop arrives as a 64-bit vector register
+//  pair, which selects the 64-bit vector add again.  Costs one v_mov per block of loads / stores.)
+__device__ __forceinline__ unsigned lane_in_block(unsigned lane_bytes) {
+    asm volatile("" : "+v"(lane_bytes));
+    return lane_bytes;
+}
+template <class T> __device__ __forceinline__ gptr<T> lane_at(const char* sbase, unsigned lane_bytes, int imm) {
+    return (gptr<T>)(sbase + lane_bytes + imm);
+}
+template <class T> __device__ __forceinline__ gptr_w<T> lane_at_w(const char* sbase, unsigned lane_bytes, int imm) {
+    return (gptr_w<T>)(sbase + lane_bytes + imm);
+}
 #else           // (host pass of the same translation unit: plain pointers)
 template <class T> using gptr = const T*;
+template <class T> using gptr_w = T*;
 template <class T> __host__ __device__ inline gptr<T> as_global(const T* p) { return p; }
+__host__ __device__ inline const char* scalar_base(const void* p) { return static_cast<const char*>(p); }
+__host__ __device__ inline unsigned lane_in_block(unsigned lane_bytes) { return lane_bytes; }
+template <class T> __host__ __device__ inline gptr<T> lane_at(const char* sbase, unsigned lane_bytes, int imm) {
+    return reinterpret_cast<gptr<T>>(sbase + lane_bytes + imm);
+}
+template <class T> __host__ __device__ inline gptr_w<T> lane_at_w(const char* sbase, unsigned lane_bytes, int imm) {
+    return reinterpret_cast<gptr_w<T>>(const_cast<char*>(sbase) + lane_bytes + imm);
+}
 #endif
 #endif
 

@@ -223,9 +223,23 @@ __device__ __attribute__((noinline)) void stage_tile_slow(creg* lds, const cf* p
 template <int LOG2F> __device__ __forceinline__ void load_tile16(creg* v, const VSrc<cf>& src, long v0, int t, creg* lds) {
     constexpr int T = 1 << (LOG2F - 4);
     if (v0 >= src.plen && v0 - src.plen + 16 * T <= src.in_len) {
-        const gptr<creg> p = as_global(reinterpret_cast<const creg*>(src.in) + (v0 - src.plen) + t);
+        // (scalar bases, one per 4 KiB of rows, + the lane's 32-bit offset + an immediate: common.hpp scalar_base.  Not for
+        //  the 512- / 1024-thread tiles: a base per row there, sixteen scalar pairs that these kernels do not have to spare)
+        if constexpr (T > 256) {
+            const gptr<creg> p = as_global(reinterpret_cast<const creg*>(src.in) + (v0 - src.plen) + t);
 #pragma unroll
-        for (int n = 0; n < 16; n++) v[n] = p[n * T];
+            for (int n = 0; n < 16; n++) v[n] = p[n * T];
+            return;
+        }
+        constexpr int ROWB = T * (int)sizeof(creg), RPB = ROWB >= 4096 ? 1 : (4096 / ROWB < 16 ? 4096 / ROWB : 16);
+        const char* w0 = reinterpret_cast<const char*>(reinterpret_cast<const creg*>(src.in) + (v0 - src.plen));
+        const unsigned lane = lane_in_block((unsigned)t * (unsigned)sizeof(creg));
+#pragma unroll
+        for (int g = 0; g < 16; g += RPB) {
+            const char* b = scalar_base(w0 + g * ROWB);
+#pragma unroll
+            for (int n = g; n < g + RPB; n++) v[n] = *lane_at<creg>(b, lane, (n - g) * ROWB);
+        }
     } else {
         stage_tile_slow<T>(lds, src.prefix, src.plen, src.in, src.in_len, v0, t);
         tile_sync<T>();          // (own slots only: each thread reads back what it wrote)
@@ -247,10 +261,25 @@ __device__ __attribute__((noinline)) void stage_tile_slow_iq8(creg* lds, VSrcIQ8
 template <int LOG2F> __device__ __forceinline__ void load_tile16(creg* v, const VSrcIQ8& src, long v0, int t, creg* lds) {
     constexpr int T = 1 << (LOG2F - 4);
     if (v0 >= src.plen && v0 - src.plen + 16 * T <= src.in_len) {
-        const gptr<unsigned short> p = as_global(reinterpret_cast<const unsigned short*>(src.in) + (v0 - src.plen) + t);
+        if constexpr (T > 256) {
+            const gptr<unsigned short> p = as_global(reinterpret_cast<const unsigned short*>(src.in) + (v0 - src.plen) + t);
+            unsigned short w[16];
+#pragma unroll
+            for (int n = 0; n < 16; n++) w[n] = p[n * T];
+#pragma unroll
+            for (int n = 0; n < 16; n++) v[n] = to_reg(VSrcIQ8::decode(w[n]));
+            return;
+        }
+        constexpr int ROWB = T * 2, RPB = ROWB >= 4096 ? 1 : (4096 / ROWB < 16 ? 4096 / ROWB : 16);
+        const char* w0 = reinterpret_cast<const char*>(reinterpret_cast<const unsigned short*>(src.in) + (v0 - src.plen));
+        const unsigned lane = lane_in_block((unsigned)t * 2u);
         unsigned short w[16];
 #pragma unroll
-        for (int n = 0; n < 16; n++) w[n] = p[n * T];
+        for (int g = 0; g < 16; g += RPB) {
+            const char* b = scalar_base(w0 + g * ROWB);
+#pragma unroll
+            for (int n = g; n < g + RPB; n++) w[n] = *lane_at<unsigned short>(b, lane, (n - g) * ROWB);
+        }
 #pragma unroll
         for (int n = 0; n < 16; n++) v[n] = to_reg(VSrcIQ8::decode(w[n]));
     } else {
@@ -268,6 +297,64 @@ __device__ __forceinline__ void store_stream(creg* p, creg v) {
     *p = v;
 #endif
 }
+#if defined(__HIP_DEVICE_COMPILE__)       // (host pass: gptr_w<creg> is creg*)
+__device__ __forceinline__ void store_stream(gptr_w<creg> p, creg v) { __builtin_nontemporal_store(v, p); }
+#endif
+
+__device__ __forceinline__ creg opaque_copy(creg a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(a));
+#endif
+    return a;
+}
+
+// v[r] for a workgroup-uniform r in [LO, HI]: nested two-way branches (a `switch` the compiler flattens into a cascade of flag
+// tests) down to opaque copies (a plain selection it turns into a run-time index into v[], through scratch memory)
+template <int LO, int HI> __device__ __forceinline__ creg pick_row(const creg* v, int r) {
+    if constexpr (LO == HI) {
+        return opaque_copy(v[LO]);
+    } else {
+        constexpr int MID = (LO + HI) / 2;
+        if (r <= MID) return pick_row<LO, MID>(v, r);
+        return pick_row<MID + 1, HI>(v, r);
+    }
+}
+
+// Whole-tile store of an overlap-save tile: tile positions [first, F) of v[n] = y[n*T + t] go to out0[n*T + t]
+// (out0 = the workgroup-uniform address of tile position 0).  Which rows are stored depends on `first` alone, so nothing
+// of it is decided per tile and per row: rows below row0 = first / T are never stored, rows above it need no mask, and
+// row0 itself takes the lane predicate keep0 = (t >= first % T), evaluated once before the tile loop.  Per tile that is
+// a scalar compare and branch per row, unmasked stores, and ONE exec-mask change, around the store of row0's register.
+// (As sixteen `if (n*T + t >= first)` the compiler hoisted sixteen lane masks out of the loop — 32
+// scalar registers, half of them spilled to vector lanes and read back every tile — and changed exec around every store.)
+// Addresses: scalar bases + lane offset + immediate (common.hpp scalar_base).
+template <int T> struct TileStore {
+    static constexpr int ROWB = T * (int)sizeof(creg), RPB = ROWB >= 4096 ? 1 : (4096 / ROWB < 16 ? 4096 / ROWB : 16), NB = 16 / RPB;
+    int row0;
+    bool keep0;
+    unsigned lane;
+    __device__ __forceinline__ TileStore(int first, int t)
+        : row0(first / T), keep0(t >= first % T), lane((unsigned)t * (unsigned)sizeof(creg)) {}
+    __device__ __forceinline__ void operator()(creg* out0, const creg* v) const {
+        const char* b[NB];
+#pragma unroll
+        for (int g = 0; g < NB; g++) b[g] = scalar_base(reinterpret_cast<const char*>(out0) + g * RPB * ROWB);
+        // A scalar compare and branch per row on row0 — re-read per tile through an empty asm: left loop-invariant, the
+        // compiler hoists the comparisons out of the tile loop as sixteen 64-bit lane masks again.  The chain is uniform
+        // from end to end (a lane-masked store inside it makes the compiler turn every branch of it into exec arithmetic).
+        int r0 = row0;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(r0));
+#endif
+#pragma unroll
+        for (int n = 1; n < 16; n++)
+            if (n > r0) store_stream(lane_at_w<creg>(b[n / RPB], lane_in_block(lane), (n % RPB) * ROWB), v[n]);
+        // row0 under its lane mask: its register is copied out by a uniform binary branch tree
+        const creg edge = pick_row<0, 15>(v, r0);
+        const char* b0 = scalar_base(reinterpret_cast<const char*>(out0) + r0 * ROWB);
+        if (keep0) store_stream(lane_at_w<creg>(b0, lane_in_block(lane), 0), edge);
+    }
+};
 
 // ---- FftFilter -----------------------------------------------------------------------------------
 // (FIX 1: FirFilter on these tiles — nan_fix.hpp nf_finish; FIX 2: the FftFilter BLOCK — the reference's blocks, rb_finish;
@@ -290,6 +377,7 @@ void k_fftfilt_os(NanFixCtx nfx, VSrc<cf> src, cf* __restrict__ out, long n_out,
     TileXform<LOG2F, VAR> X;
     X.init(t, tw, hpos);
     creg* out_reg = reinterpret_cast<creg*>(out);
+    const TileStore<T> store_tile(first, t);
 
     int iter = 0;
     for (TileIter it(ntiles); it.tile < it.end; it.tile += it.step, iter++) {
@@ -323,14 +411,19 @@ void k_fftfilt_os(NanFixCtx nfx, VSrc<cf> src, cf* __restrict__ out, long n_out,
         }
         // tile positions [L-1, F) are valid linear-convolution outputs
         const long o0 = (RR_ABLATE(32) ? 8 + (tile & 63) : tile) * S - first;
-        creg* po = out_reg + o0 + t;
         if (o0 + F <= n_out) {                                  // whole tile inside the output window
+            if constexpr (T <= 256) {
+                store_tile(out_reg + o0, v);
+            } else {                     // (512- / 1024-thread tiles, a scalar base per row: per-row masks and vector addresses)
+                creg* po = out_reg + o0 + t;
 #pragma unroll
-            for (int n = 0; n < 16; n++) {
-                if (n * T >= first) store_stream(&po[n * T], v[n]);           // wave-uniform
-                else if ((n + 1) * T > first) { if (n * T + t >= first) store_stream(&po[n * T], v[n]); }
+                for (int n = 0; n < 16; n++) {
+                    if (n * T >= first) store_stream(&po[n * T], v[n]);           // wave-uniform
+                    else if ((n + 1) * T > first) { if (n * T + t >= first) store_stream(&po[n * T], v[n]); }
+                }
             }
         } else {
+            creg* po = out_reg + o0 + t;
 #pragma unroll
             for (int n = 0; n < 16; n++) {
                 const int idx = n * T + t;

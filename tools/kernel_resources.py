@@ -2,10 +2,17 @@
 """Per-kernel register / scratch / LDS figures from hipcc's device assembly (the .amdhsa metadata block).
 
     tools/kernel_resources.py [--build DIR] [--diff OLD_DIR] [file.hip ...]
+    tools/kernel_resources.py [--build DIR] [--no-build] --loop 'k_fftfilt_os<11, 0, 0>' [--blocks 0-3,7] [file.hip ...]
 
 --build DIR : compile every rustradio_amd/csrc/kernels_*.hip (or the files named) to DIR/<name>.s with the product's flags
               (device only, no GPU needed) and print one line per kernel: VGPRs, AGPRs, SGPRs, spilled VGPRs, scratch bytes
 --diff OLD  : print only the kernels whose figures differ from OLD/<name>.s (a build of another revision)
+
+--loop NAME : instruction histogram of the tile loop of the kernel whose demangled name contains NAME: the loop (a backward
+              branch and its target) that holds the most packed-f32 instructions, innermost on a tie.  One line per basic block
+              of the loop and the sum; --blocks sums a chosen subset instead (block numbers as printed), which is how the
+              steady-state path is counted apart from the boundary-tile blocks that sit in the same loop.
+--no-build  : read DIR/<name>.s as it is
 
 A tile kernel that starts to spill is 1.5-2x slower (every scratch access waits on the whole in-order vmcnt queue,
 profiles/TUNING_LOG.md §4.1), so every change to a kernel is checked with this before it goes to the GPU.
@@ -53,12 +60,125 @@ def parse(path):
     return out
 
 
+CLASSES = ["pk_f32", "lds", "gload", "gstore", "flat", "wait_sync", "s_nop", "lane", "valu_addr64", "valu_other", "exec", "branch", "salu_other"]
+
+
+def classify(ins, ops):
+    if ins.startswith("v_pk_"):
+        return "pk_f32"
+    if ins.startswith("ds_"):
+        return "lds"
+    if ins.startswith(("global_load", "buffer_load", "scratch_load")):
+        return "gload"
+    if ins.startswith(("global_store", "global_atomic", "buffer_store", "scratch_store")):
+        return "gstore"
+    if ins.startswith("flat_"):
+        return "flat"
+    if ins in ("s_waitcnt", "s_barrier", "s_setprio"):
+        return "wait_sync"
+    if ins == "s_nop":
+        return "s_nop"
+    if ins.startswith(("v_readlane", "v_writelane", "v_readfirstlane")):
+        return "lane"
+    if ins.startswith(("v_add_co", "v_addc", "v_sub_co", "v_subb", "v_lshl_add_u64", "v_lshlrev_b64", "v_mad_u64", "v_mad_i64")):
+        return "valu_addr64"
+    if ins.startswith("v_"):
+        return "valu_other"
+    if ins.startswith(("s_cbranch", "s_branch", "s_swappc", "s_setpc", "s_endpgm")):
+        return "branch"
+    if "saveexec" in ins or re.search(r"\bexec\b", ops):
+        return "exec"
+    return "salu_other"
+
+
+def kernel_body(txt, mangled):
+    m = re.search(r"^" + re.escape(mangled) + r":.*$", txt, re.M)
+    end = txt.index(".Lfunc_end", m.end())
+    return txt[m.end():end].split("\n")
+
+
+def tile_loop(lines):
+    """-> (first, last) line indices of the backward-branch span holding the most v_pk_ instructions (innermost on a tie)"""
+    label_at = {}
+    for i, ln in enumerate(lines):
+        m = re.match(r"^(\.LBB\d+_\d+):", ln)
+        if m:
+            label_at[m.group(1)] = i
+    pk = [0]
+    for ln in lines:
+        pk.append(pk[-1] + (ln.strip().startswith("v_pk_")))
+    best = None
+    for i, ln in enumerate(lines):
+        m = re.match(r"^\s+s_c?branch\S*\s+(\.LBB\d+_\d+)", ln)
+        if m and label_at.get(m.group(1), i + 1) <= i:
+            j = label_at[m.group(1)]
+            key = (pk[i + 1] - pk[j], -(i - j))
+            if best is None or key > best[0]:
+                best = (key, j, i)
+    if best is None:
+        sys.exit("no loop in this kernel")
+    return best[1], best[2]
+
+
+def parse_blocks(sel):
+    out = set()
+    for part in sel.split(","):
+        a, _, b = part.partition("-")
+        out.update(range(int(a), int(b or a) + 1))
+    return out
+
+
+def loop_report(path, want, blocks):
+    txt = open(path, errors="replace").read()
+    names = list(parse(path))
+    dm = demangle(names)
+    hits = [k for k in names if want in dm[k]]
+    if len(hits) != 1:
+        sys.exit(f"{want!r} matches {len(hits)} kernels of {os.path.basename(path)}: " + ", ".join(re.sub(r"\(.*", "", dm[k]) for k in hits[:8]))
+    lines = kernel_body(txt, hits[0])
+    lo, hi = tile_loop(lines)
+    # the loop's blocks: the header and every block the compiler marks "in Loop: Header=<it>" (some are laid out behind the
+    # backward branch), blocks of loops nested in it included
+    hm = re.search(r"Header=(BB\d+_\d+) ", lines[lo])       # (the branch target may be the latch, laid out before the header)
+    hdr = hm.group(1) if hm else re.match(r"^\.L(BB\d+_\d+):", lines[lo]).group(1)
+    rows, cur, detail = [], None, {}
+    for k, ln in enumerate(lines):
+        m = re.match(r"^(\.LBB\d+_\d+):|^; %bb\.(\d+):", ln)
+        if m:
+            inside = k == lo or ("Header=" + hdr + " ") in ln or ln.startswith(".L" + hdr + ":") or (lo <= k <= hi and "Header=" in ln)
+            cur = [m.group(1) or "%bb." + m.group(2), dict.fromkeys(CLASSES, 0)] if inside else None
+            if inside:
+                rows.append(cur)
+            continue
+        t = ln.split(";")[0].strip()
+        if not t or t.startswith(".") or cur is None:
+            continue
+        ins, _, ops = t.partition(" ")
+        c = classify(ins, ops)
+        cur[1][c] += 1
+        if blocks is None or len(rows) - 1 in blocks:
+            detail[ins] = detail.get(ins, 0) + 1
+    print(re.sub(r"\(.*", "", dm[hits[0]]).replace("void rr::", ""), "- tile loop,", len(rows), "basic blocks")
+    print(f"{'#':>3s} {'block':12s} " + " ".join(f"{c:>11s}" for c in CLASSES) + f" {'total':>6s}")
+    tot = dict.fromkeys(CLASSES, 0)
+    for i, (lab, h) in enumerate(rows):
+        if blocks is not None and i not in blocks:
+            continue
+        print(f"{i:3d} {lab:12s} " + " ".join(f"{h[c]:11d}" for c in CLASSES) + f" {sum(h.values()):6d}")
+        for c in CLASSES:
+            tot[c] += h[c]
+    print(f"{'':3s} {'sum':12s} " + " ".join(f"{tot[c]:11d}" for c in CLASSES) + f" {sum(tot.values()):6d}")
+    print("by mnemonic: " + ", ".join(f"{k} {v}" for k, v in sorted(detail.items(), key=lambda kv: (-kv[1], kv[0]))))
+
+
 def demangle(names):
-    try:
-        p = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-cxxfilt"], input="\n".join(names), capture_output=True, text=True)
-        return dict(zip(names, p.stdout.split("\n")))
-    except Exception:
-        return {n: n for n in names}
+    for tool in ("/opt/rocm/lib/llvm/bin/llvm-cxxfilt", "llvm-cxxfilt", "c++filt"):
+        try:
+            p = subprocess.run([tool], input="\n".join(names), capture_output=True, text=True)
+            return dict(zip(names, p.stdout.split("\n")))
+        except Exception:
+            continue
+    return {n: n for n in names}
 
 
 def main():
@@ -66,10 +186,20 @@ def main():
     ap.add_argument("--build", default="/tmp/rr_kres")
     ap.add_argument("--diff", default=None)
     ap.add_argument("--extra", default="", help="extra compiler flags, e.g. -DRR_POLY_NB=2")
+    ap.add_argument("--loop", default=None, help="demangled kernel name (substring): histogram of its tile loop")
+    ap.add_argument("--blocks", default=None, help="with --loop: sum only these basic blocks, e.g. 0-3,7")
+    ap.add_argument("--no-build", action="store_true", help="use the assembly already in --build DIR")
     ap.add_argument("files", nargs="*")
     a = ap.parse_args()
     files = [os.path.abspath(f) for f in a.files] or sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.startswith("kernels_") and f.endswith(".hip"))
-    build(files, a.build, a.extra.split())
+    if not a.no_build:
+        build(files, a.build, a.extra.split())
+    if a.loop:
+        for f in files:
+            sp = os.path.join(a.build, os.path.basename(f).replace(".hip", ".s"))
+            if any(a.loop in v for v in demangle(list(parse(sp))).values()):
+                return loop_report(sp, a.loop, parse_blocks(a.blocks) if a.blocks else None)
+        sys.exit(f"no kernel named like {a.loop!r}")
     bad = 0
     for f in files:
         sname = os.path.basename(f).replace(".hip", ".s")
