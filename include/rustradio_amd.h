@@ -593,6 +593,14 @@ int rr_debug_fft_stamps(unsigned long long *out32);
  * FftFilter work() on a device window is ONE launch (round 6; the reference's one work() = one pass over the window,
  * src/fft_filter.rs:289-355). */
 unsigned long long rr_debug_kernel_launches(void);
+/* Introspection for tests: the kernel family of the handle's most recent EMITTING work() call, for the blocks that pick
+ * their kernel per call by the size of the window (the fused FM chains, FftFilter / FirFilter -> FftFilter, Hilbert ->
+ * FirFilter, FirFilter<Complex>).  A static string, one of "poly" (decimate-first tiles), "half" (half-size inverse), "alt" (plain 4096-point
+ * tile of a long filter), "split" (8192 / 16384-point split tile), "full" (plain tile), "prune" (pruned inverse),
+ * "direct" (direct form), "two-stage" (two kernels through a work buffer), "deci" (tiles with a decimating store).
+ * "" for a block without such a choice, for a handle that has not emitted yet and for NULL.  The result of work() does
+ * not depend on the family beyond f32 rounding; tests use it to prove that a schedule of windows really switched. */
+const char *rr_debug_last_kernel(const rr_block *b);
 
 /* ---- per-block knobs / introspection ------------------------------------------- */
 /* FftFilter: reference fft_size and nsamples (src/fft_filter.rs:261-262) and the

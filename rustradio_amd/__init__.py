@@ -243,6 +243,11 @@ class Block:
         if lib().rr_block_sync(self._h) != 0:
             raise RuntimeError(last_error())
 
+    def last_kernel(self) -> str:
+        """rr_debug_last_kernel: the kernel family of the most recent emitting work() call ("" for a block without a per-call
+        choice or before the first output) — introspection for tests"""
+        return lib().rr_debug_last_kernel(self._h).decode()
+
     def set_profiling(self, on: bool) -> None:
         lib().rr_block_set_profiling(self._h, int(on))
 

@@ -23,6 +23,7 @@ SYMBOLS = [
     "rr_block_work", "rr_block_work_dev", "rr_block_eof", "rr_block_name", "rr_block_tag_rule", "rr_block_in_elem_size",
     "rr_block_out_elem_size", "rr_block_sync", "rr_fftfilter_dims", "rr_fir_fft_tile", "rr_fir_set_rotator_mode",
     "rr_block_set_profiling", "rr_block_profile", "rr_debug_fft_stamps", "rr_debug_kernel_launches",
+    "rr_debug_last_kernel",
     "rr_host_register", "rr_host_unregister", "rr_host_window_in_place",
     "rr_dstream_create", "rr_dstream_destroy", "rr_dstream_capacity", "rr_dstream_is_double_mapped", "rr_dstream_read_buf", "rr_dstream_write_buf",
     "rr_dstream_consume", "rr_dstream_produce", "rr_dstream_close", "rr_dstream_closed", "rr_dstream_wait", "rr_dstream_id", "rr_dstream_copy_in", "rr_dstream_copy_out", "rr_dstream_copy", "rr_block_work_streams",
@@ -124,6 +125,7 @@ def lib():
     L.rr_fir_set_rotator_mode.argtypes = [vp, i32]; L.rr_fir_set_rotator_mode.restype = i32
     L.rr_debug_fft_stamps.argtypes = [vp]; L.rr_debug_fft_stamps.restype = i32
     L.rr_debug_kernel_launches.argtypes = []; L.rr_debug_kernel_launches.restype = C.c_ulonglong
+    L.rr_debug_last_kernel.argtypes = [vp]; L.rr_debug_last_kernel.restype = C.c_char_p
     pvp = C.POINTER(vp)
     L.rr_host_register.argtypes = [vp, sz]; L.rr_host_register.restype = i32
     L.rr_host_window_in_place.argtypes = [vp, sz]; L.rr_host_window_in_place.restype = i32

@@ -387,6 +387,7 @@ int rr_block_profile(rr_block* b, double* total_ms, size_t* launches, int reset)
 }
 
 unsigned long long rr_debug_kernel_launches(void) { return rr::g_kernel_launches.load(std::memory_order_relaxed); }
+const char* rr_debug_last_kernel(const rr_block* b) { return b && b->b ? b->b->last_kernel : ""; }
 
 /* measurement builds (make ABLATE=1): phase time stamps of one FftFilter tile; 0 in product builds */
 int rr_debug_fft_stamps(unsigned long long* out16) {

@@ -446,11 +446,13 @@ int FirC32::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, s
         // (beyond ~320 taps the direct form's LDS tile stops fitting and it collapses: never there)
         small_direct = !fftk || (L <= 320 && t_direct <= t_tiles && fir_direct_has_tile(pl, sizeof(cf), sizeof(cf)));
     }
-    if (use_poly) launch_fir_poly(src, static_cast<cf*>(out), (long)out_n, (int)L, (int)d, poly->d_tw.p, poly->d_h.p, s, nanfix());
-    else if (small_direct) launch_fir_c32(pl, d_tp.p, d_rev.p, src, static_cast<cf*>(out), (long)out_n, s, nanfix());
-    else if (half_ok) launch_fftfilt_half(src, static_cast<cf*>(out), (long)out_n, (int)L, (int)d, d_htw.p, d_htw_half.p, d_hhpos.p, s, nanfix());
-    else if (use_prune) launch_fftfilt_prune_c32(prune->log2f, src, static_cast<cf*>(out), (long)out_n, (int)L, prune->d_tw.p, prune->d_h2.p, prune->d_twb.p, s, (int)prune_sub, nanfix());
+    // (last_kernel: the family of this call, for rr_debug_last_kernel)
+    if (use_poly) last_kernel = "poly", launch_fir_poly(src, static_cast<cf*>(out), (long)out_n, (int)L, (int)d, poly->d_tw.p, poly->d_h.p, s, nanfix());
+    else if (small_direct) last_kernel = "direct", launch_fir_c32(pl, d_tp.p, d_rev.p, src, static_cast<cf*>(out), (long)out_n, s, nanfix());
+    else if (half_ok) last_kernel = "half", launch_fftfilt_half(src, static_cast<cf*>(out), (long)out_n, (int)L, (int)d, d_htw.p, d_htw_half.p, d_hhpos.p, s, nanfix());
+    else if (use_prune) last_kernel = "prune", launch_fftfilt_prune_c32(prune->log2f, src, static_cast<cf*>(out), (long)out_n, (int)L, prune->d_tw.p, prune->d_h2.p, prune->d_twb.p, s, (int)prune_sub, nanfix());
     else if (fftk && d > 1 && fftk->big) {
+        last_kernel = "two-stage";
         // full-rate overlap-save frames into a scratch buffer, chunk by chunk, then out[m] = y[m d] (the resampler's index
         // pick with I = 1: a strided copy).  A window position o0 d of the input starts chunk o0.
         const size_t chunk = std::max<size_t>(1, ((size_t)1 << 22) / d);
@@ -462,10 +464,10 @@ int FirC32::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, s
             launch_resample(dec_tmp.p, static_cast<cf*>(out) + o0, sizeof(cf), 0, nullptr, (long)m, 1, (long)d, 0, s);
         }
     }
-    else if (fftk && d > 1 && fftk->nsub) launch_fftfilt_split_deci(fftk->nsub, src, static_cast<cf*>(out), (long)out_n, (int)L, (int)d, fftk->d_tw4096.p, fftk->d_hs.p, fftk->d_wk.p, s, nanfix());
-    else if (fftk && d > 1) launch_fftfilt_deci(fftk->log2f, src, static_cast<cf*>(out), (long)out_n, (int)L, (int)d, fftk->d_tw.p, fftk->d_hpos.p, s, nanfix());
-    else if (fftk) fftk->filter(src, static_cast<cf*>(out), (long)out_n, s);
-    else launch_fir_c32(pl, d_tp.p, d_rev.p, src, static_cast<cf*>(out), (long)out_n, s, nanfix());
+    else if (fftk && d > 1 && fftk->nsub) last_kernel = "deci", launch_fftfilt_split_deci(fftk->nsub, src, static_cast<cf*>(out), (long)out_n, (int)L, (int)d, fftk->d_tw4096.p, fftk->d_hs.p, fftk->d_wk.p, s, nanfix());
+    else if (fftk && d > 1) last_kernel = "deci", launch_fftfilt_deci(fftk->log2f, src, static_cast<cf*>(out), (long)out_n, (int)L, (int)d, fftk->d_tw.p, fftk->d_hpos.p, s, nanfix());
+    else if (fftk) fftk->filter(src, static_cast<cf*>(out), (long)out_n, s), last_kernel = fftk->last_kernel;
+    else last_kernel = "direct", launch_fir_c32(pl, d_tp.p, d_rev.p, src, static_cast<cf*>(out), (long)out_n, s, nanfix());
     prof_end(s);
     rotate_output(static_cast<cf*>(out), out_n, s);                  // fir.rs:531
     *consumed = n; *produced = out_n;
@@ -705,8 +707,12 @@ int HilbertFir::work_dev(const void* in, size_t in_len, void* out, size_t out_ca
     }
     // (the hn samples before the new window become the next call's history: written by the tile kernel itself)
     const CarryOut carry{hist[cur ^ 1].p, (long)n, (long)hn};
-    if (use_prune) launch_fftfilt_prune_real(prune->log2f, src, static_cast<cf*>(out), (long)out_n, plG.L, prune->d_tw.p, prune->d_h2.p, prune->d_h2b.p, prune->d_twb.p, s, carry, (int)prune_sub, nanfixG());
+    if (use_prune) {
+        last_kernel = "prune";
+        launch_fftfilt_prune_real(prune->log2f, src, static_cast<cf*>(out), (long)out_n, plG.L, prune->d_tw.p, prune->d_h2.p, prune->d_h2b.p, prune->d_twb.p, s, carry, (int)prune_sub, nanfixG());
+    }
     else if (two_stage && (n >= 16384 || !fir_direct_has_tile(plG, sizeof(float), sizeof(cf)))) {
+        last_kernel = "two-stage";
         // a[k] = (iv[k + hn/2], sum_j rev_h[j] iv[k + j]) over the virtual stream iv = hist ++ window (hilbert.rs:113-116), then
         // y[m] = sum_k rev[k] a[m d + k]: outputs [m0, m1) take a[m0 d, m1 d + L - 1).  In chunks, so that the analytic buffer
         // stays at 128 MB whatever the window.
@@ -728,7 +734,10 @@ int HilbertFir::work_dev(const void* in, size_t in_len, void* out, size_t out_ca
             if (p2 != m1 - m0) throw Error("HilbertFir: the FirFilter stage disagrees on the output count");
         }
     }
-    else launch_fir_f32c(plG, d_tpG.p, d_revG.p, src, static_cast<cf*>(out), (long)out_n, s, nanfixG());
+    else {
+        last_kernel = "direct";
+        launch_fir_f32c(plG, d_tpG.p, d_revG.p, src, static_cast<cf*>(out), (long)out_n, s, nanfixG());
+    }
     prof_end(s);
     fir->rotate_output(static_cast<cf*>(out), out_n, s);
     if (!use_prune) launch_carry(src, carry, s);
@@ -1171,7 +1180,7 @@ bool FftFilter::filter(VSrc<cf> src, cf* out, long n_out, hipStream_t s, CarryOu
         return false;
     }
     const bool use_alt = nsub && alt_log2f && alt_wins(n_out);
-    if (nsub && !use_alt) { launch_fftfilt_split(nsub, src, out, n_out, (int)L, d_tw4096.p, d_hs.p, d_wk.p, s, carry, nanfix); return false; }
+    if (nsub && !use_alt) { last_kernel = "split"; launch_fftfilt_split(nsub, src, out, n_out, (int)L, d_tw4096.p, d_hs.p, d_wk.p, s, carry, nanfix); return false; }
     NanFix fx = nanfix;
     const bool rb = rb_ok && ref_blocks && rb_in_kernel && n_out > 0;
     if (rb) {
@@ -1183,8 +1192,8 @@ bool FftFilter::filter(VSrc<cf> src, cf* out, long n_out, hipStream_t s, CarryOu
         fx.rb_work = d_rb_work.p; fx.rb_recs = d_rb_recs.p; fx.rb_cap = cap; fx.rb_S = (long)nsamples; fx.rb_hist = (long)hist;
         fx.rb_front = (int)front; fx.rb_seq = seq; fx.rb_tail = d_tail.p;
     }
-    if (use_alt) launch_fftfilt_os(alt_log2f, src, out, n_out, (int)L, d_tw_alt.p, d_hpos_alt.p, s, carry, fx);
-    else launch_fftfilt_os(log2f, src, out, n_out, (int)L, d_tw.p, d_hpos.p, s, carry, fx);
+    if (use_alt) { last_kernel = "alt"; launch_fftfilt_os(alt_log2f, src, out, n_out, (int)L, d_tw_alt.p, d_hpos_alt.p, s, carry, fx); }
+    else { last_kernel = "full"; launch_fftfilt_os(log2f, src, out, n_out, (int)L, d_tw.p, d_hpos.p, s, carry, fx); }
     return rb;
 }
 
@@ -1444,32 +1453,43 @@ int FmChain::work_blocks(const void* in, size_t in_len, float* out, size_t, size
         const bool use_alt = f->nsub && f->alt_log2f && window_aware && f->alt_wins((long)n_y, true) &&
                              (int64_t)((D + I - 1) / I) < (int64_t)(((size_t)1 << f->alt_log2f) - f->L + 1);
         prof_begin(s);
+        // (last_kernel: the family of this call, for rr_debug_last_kernel)
         if (use_poly && packed)
+            last_kernel = "poly",
             launch_fm_chain_poly_iq8(src8, out, (int)f->L, poly->d_tw.p, poly->d_h.p, a, last_r[cur_lr].p, last_r[cur_lr ^ 1].p, s);
         else if (use_poly)
+            last_kernel = "poly",
             launch_fm_chain_poly(src, out, (int)f->L, poly->d_tw.p, poly->d_h.p, a, last_r[cur_lr].p, last_r[cur_lr ^ 1].p, s);
         else if (use_alt && packed)        // long filter, window of too few split tiles: the plain 4096-point chain tile (see FftFilter)
+            last_kernel = "alt",
             launch_fm_chain_iq8(f->alt_log2f, src8, out, (int)f->L, f->d_tw_alt.p, f->d_hpos_alt.p, a,
                                 last_r[cur_lr].p, last_r[cur_lr ^ 1].p, s);
         else if (use_alt)
+            last_kernel = "alt",
             launch_fm_chain(f->alt_log2f, src, out, (int)f->L, f->d_tw_alt.p, f->d_hpos_alt.p, a,
                             last_r[cur_lr].p, last_r[cur_lr ^ 1].p, s);
         else if (f->nsub && packed)
+            last_kernel = "split",
             launch_fm_chain_split_iq8(f->nsub, src8, out, (int)f->L, f->d_tw4096.p, f->d_hs.p, f->d_wk.p, a,
                                       last_r[cur_lr].p, last_r[cur_lr ^ 1].p, s);
         else if (f->nsub)
+            last_kernel = "split",
             launch_fm_chain_split(f->nsub, src, out, (int)f->L, f->d_tw4096.p, f->d_hs.p, f->d_wk.p, a,
                                   last_r[cur_lr].p, last_r[cur_lr ^ 1].p, s);
         else if (use_half && packed)
+            last_kernel = "half",
             launch_fm_chain_half_iq8(src8, out, (int)f->L, f->d_tw.p, d_tw_half.p, f->d_hpos.p, a,
                                      last_r[cur_lr].p, last_r[cur_lr ^ 1].p, s);
         else if (use_half)
+            last_kernel = "half",
             launch_fm_chain_half(src, out, (int)f->L, f->d_tw.p, d_tw_half.p, f->d_hpos.p, a,
                                  last_r[cur_lr].p, last_r[cur_lr ^ 1].p, s);
         else if (packed)
+            last_kernel = "full",
             launch_fm_chain_iq8(f->log2f, src8, out, (int)f->L, f->d_tw.p, f->d_hpos.p, a,
                                 last_r[cur_lr].p, last_r[cur_lr ^ 1].p, s);
         else
+            last_kernel = "full",
             launch_fm_chain(f->log2f, src, out, (int)f->L, f->d_tw.p, f->d_hpos.p, a,
                             last_r[cur_lr].p, last_r[cur_lr ^ 1].p, s);
         prof_end(s);

@@ -24,6 +24,8 @@ struct Block {
     int device = 0;
     hipStream_t stream = nullptr;         // private stream: host-window work() and setup copies
     hipStream_t last_stream = nullptr;    // stream of the most recent work call (what sync() waits for)
+    // blocks that pick their kernel per call: the family of the most recent emitting call (rr_debug_last_kernel; "" otherwise)
+    const char* last_kernel = "";
     DevBuf<unsigned char> st_in, st_out;   // staging for host-window work() (pageable windows)
     std::unique_ptr<HostStage> hstage_;    // ... and the pinned chunks their bytes cross the bus in (stage.hpp), made on first use
     HostStage& hstage() { if (!hstage_) hstage_.reset(new HostStage()); return *hstage_; }
