@@ -326,6 +326,67 @@ rr_block *rr_bit_decoder_create(int flags, unsigned long long mask, unsigned lon
  * sample of the largest window seen.  RR_ERR for a handle without a correlator stage. */
 int rr_bit_tags(rr_block *b, size_t *pos, unsigned char *diffs, size_t cap, size_t *total);
 
+/* Wpcr::new(src) / WpcrBuilder::samp_rate (src/wpcr.rs:84-128): whole-packet clock recovery, the symbol clock in front of the
+ * bit-level blocks above (examples/ax25-1200-wpcr.rs, ax25-9600-wpcr.rs, g3ruh.rs).  A PDU-form block like rr_fft_process, not a
+ * stream block: rr_block_work on the handle is an error.  samp_rate is NaN when not set.  One call takes a BATCH of disjoint
+ * bursts inside one f32 sample buffer; per burst x[0 .. n), N = n - 1, with its own `mid` (the reference hard-wires 0.0, :138):
+ *   1. n < 4: dropped (the reference's None, :131-133).
+ *   2. s[i] = x[i] > mid (NaN: 0); d[i] = (s[i] - s[i+1])^2, i < N: 0 / 1 and finite whatever the samples are (:141-149).
+ *   3. X = DFT_N(d), forward, unnormalised, bins k < N / 2; mag[k] = sqrt(re^2 + im^2) in f32 (:153-156, :222).
+ *   4. find_best_bin (:217-239): thresh = 0.8f max(mag[2 .. N/2)); bin = the first k >= 2 with k + 1 < N / 2, mag[k] > thresh
+ *      and mag[k] > mag[k+1]; none (every N / 2 <= 3, every burst without a crossing, a NaN mid): dropped.
+ *   5. f = (float)bin / (float)n (:165; symbols per sample, < 0.5); t = 0.5f + atan2f(im, re) / (float)(2 pi);
+ *      p0 = t > 0.5f ? t : t + 1.0f, in (0.5, 1.5] (:166-169).
+ *   6. Symbols.  The reference runs `if phase >= 1 { phase -= 1; push(x[i]) }; phase += f` per sample in f32 (:180-186).  This
+ *      block evaluates the same clock WITHOUT the accumulator's drift: with P(i) = p0 + i f in exact arithmetic on the two f32
+ *      values (64-bit integers on the device), sample i is taken iff floor(P(i)) > floor(P(i-1)) (sample 0 iff p0 >= 1) and
+ *      becomes symbol floor(P(i)) - 1; nsyms = floor(P(n-1)); the `phase` tag is fl32(P(n) - nsyms).  NOT bit-equal to the
+ *      reference: its f32 phase is off the exact one by at most i 2^-24 after i additions, so its picks differ from this
+ *      block's only where P(i) or P(i-1) lies within (i + 1) 2^-24 of an integer (there it takes the neighbouring sample), and
+ *      its phase tag differs by at most n 2^-24.  The same stance as rr_vco_create and the scan blocks: closer to the exact
+ *      recurrence than the reference.
+ *   7. A symbol is x[i] - mid, one f32 rounding: what Midpointer (:75-78) would have put into the burst, and x > mid is what
+ *      Wpcr would have seen behind it — a caller that computes Midpointer's offset passes it as `mid` instead of rewriting
+ *      the burst.  mid == NULL means 0 for every burst: the symbols are the samples bit for bit (NaN and +-Inf included).
+ *   8. Tags (:187-194): sps = f, phase as above, frequency = f * samp_rate in f32 (NaN without a sample rate).
+ * Accuracy of the spectrum the decision is taken on.  With C = the number of crossings of the burst and X the exact DFT,
+ *   |X_gpu[k] - X[k]| <= C (pi 2^-23 + e_phasor) + depth 2^-24 C,   e_phasor = pi 2^-23 + 2 e_sincos + 3 2^-24, e_sincos = 2^-21,
+ *   depth = 20, about 3.1e-6 C:
+ * j k mod N is reduced exactly in integers and a phase is rounded to f32 ONCE (2 r / N in [0, 2), error 2^-23, times pi);
+ * e_sincos bounds sincospif's error on (cos, sin) as a vector.  One bin in four takes its phasors from sincospif directly; the
+ * other three multiply them by a second such phasor (the step of 256, 512 or 768 bins) in f32, which doubles the error of one
+ * and adds 3 2^-24 for the product: that is e_phasor.  The terms are summed in f32 in groups of 16 and the groups in f64 (whose
+ * own error is below 2^-34 C), so `depth` counts 15 additions, the cast of the f64 sum and the four roundings of
+ * norm_sqr().sqrt().  The bound does not depend on N.  p0 follows within bound / |X[bin]| / (2 pi) + 3 2^-24, modulo 1.  Whatever the input (pure noise included),
+ * `bin` is find_best_bin applied to the block's OWN f32 magnitudes (rr_debug_wpcr_spectrum), and the symbols, nsyms and phase
+ * are exactly those of step 6 run from the REPORTED phase0 and sps. */
+typedef struct {
+    int ok;                 /* 0: the reference's None (the other fields are 0) */
+    unsigned bin;
+    float sps, phase0;      /* f and p0 of step 5 */
+    float phase, frequency; /* the tag values of step 8 */
+    size_t nsyms;
+} rr_wpcr_result;
+rr_block *rr_wpcr_create(float samp_rate);
+/* Device pointers d_samples (n_total f32) and d_syms (n_total f32, not overlapping d_samples); enqueued on hip_stream (used as
+ * given, like rr_block_work_dev) and returns without waiting for the kernels.  starts, lens and mid (NULL: 0) are HOST arrays
+ * of nbursts entries, read before the call returns (not const-qualified only so that every binding's type map has them).
+ * Burst b is d_samples[starts[b] .. starts[b] + lens[b]); its symbols are written to d_syms[starts[b] ..), the same geometry as
+ * the input (nsyms <= n / 2 + 1 < n always fits: no offsets to scan, no capacity to run out of); the rest of d_syms is left
+ * alone.  The ranges must be ascending, disjoint and inside n_total, else RR_ERR with rr_last_error "bursts overlap" /
+ * "burst outside the buffer"; lens[b] may be anything up to the stream capacity in samples (512,000), longer: RR_ERR ("burst
+ * longer than 512000 samples").  An error launches nothing.  nbursts == 0 launches nothing.  Four kernel launches per call,
+ * whatever the number and the lengths of the bursts. */
+int rr_wpcr_process_dev(rr_block *b, const void *d_samples, size_t n_total, size_t *starts, size_t *lens, const float *mid,
+                        size_t nbursts, void *d_syms, void *hip_stream);
+/* The same with host pointers: copies the samples down, runs, copies the symbols back and waits.  syms (n_total f32) receives
+ * burst b's symbols at syms[starts[b] ..) and zeros everywhere else between the first burst's start and the last burst's end. */
+int rr_wpcr_process(rr_block *b, const float *samples, size_t n_total, size_t *starts, size_t *lens, const float *mid,
+                    size_t nbursts, float *syms);
+/* One record per burst of the most recent process call, in burst order.  Waits for that call (as rr_burst_edges does), writes
+ * the first min(*total, cap) records; *total = the call's nbursts; res == NULL with cap == 0 only counts. */
+int rr_wpcr_results(rr_block *b, rr_wpcr_result *res, size_t cap, size_t *total);
+
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)
  * as wired in examples/ax25-1200-rx.rs:238-247: f32 in, Complex out, ONE decimating FIR with the composite
@@ -601,6 +662,10 @@ unsigned long long rr_debug_kernel_launches(void);
  * "" for a block without such a choice, for a handle that has not emitted yet and for NULL.  The result of work() does
  * not depend on the family beyond f32 rounding; tests use it to prove that a schedule of windows really switched. */
 const char *rr_debug_last_kernel(const rr_block *b);
+/* Introspection for tests: the f32 magnitudes mag[0 .. N / 2) that rr_wpcr's decision for burst `burst` of the most recent
+ * process call was taken on (the device keeps them anyway).  Waits for that call; writes the first min(*nbins, cap) of them,
+ * *nbins = N / 2 (0 for a burst shorter than 2 samples). */
+int rr_debug_wpcr_spectrum(rr_block *b, size_t burst, float *mag, size_t cap, size_t *nbins);
 
 /* ---- per-block knobs / introspection ------------------------------------------- */
 /* FftFilter: reference fft_size and nsamples (src/fft_filter.rs:261-262) and the

@@ -71,6 +71,10 @@ unsafe extern "C" {
     fn rr_correlate_access_code_tag_create(code: u64, code_len: c_uint, allowed_diffs: usize) -> *mut RrBlock;
     #[allow(dead_code)]
     fn rr_bit_decoder_create(flags: c_int, mask: u64, seed: u64, len: c_uint, code: u64, code_len: c_uint, allowed_diffs: usize) -> *mut RrBlock;
+    // (declared for completeness: Wpcr is a message block — NCReadStream<Vec<Float>> in, NCWriteStream<Vec<Float>> out with the
+    //  sps / phase / frequency tags — and its typed block needs rr_wpcr_process and rr_wpcr_results too; not written yet)
+    #[allow(dead_code)]
+    fn rr_wpcr_create(samp_rate: f32) -> *mut RrBlock;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;

@@ -13,6 +13,7 @@ what the reference would pass to `consume()`/`produce()`.
     QuadratureDemod      src/quadrature_demod.rs:32-114
     RtlSdrDecode         src/rtlsdr_decode.rs:9-47
     Hilbert              src/hilbert.rs:22-129
+    Wpcr                 src/wpcr.rs:84-239      (message form: a batch of bursts per call)
     low_pass / low_pass_complex / hilbert_taps / make_window   src/fir.rs:594-680, src/window.rs
 
 All sample arithmetic runs in HIP kernels on the GPU; nothing here computes samples.
@@ -660,6 +661,92 @@ class BitDecoder(_TagBlock):
         packed, n = pack_code(code) if code is not None else (0, 0)
         super().__init__(lib().rr_bit_decoder_create(flags, int(mask), int(seed), int(length), packed, n, int(allowed_diffs)),
                          np.float32, np.uint8)
+
+
+WPCR_MAX_LEN = 512_000      # samples of one burst: the reference's stream capacity in f32
+# rr_wpcr_result
+WPCR_RESULT = np.dtype([("ok", np.int32), ("bin", np.uint32), ("sps", np.float32), ("phase0", np.float32), ("phase", np.float32),
+                        ("frequency", np.float32), ("nsyms", np.uint64)], align=True)
+
+
+class Wpcr(Block):
+    """Wpcr::builder(src)[.samp_rate(s)] (src/wpcr.rs:84-239): whole-packet clock recovery over a batch of bursts, the PDU form
+    (rr_wpcr_create; not a stream block: work() raises).  The symbols are picked by the drift-free clock p0 + i * sps; see
+    include/rustradio_amd.h for where that differs from the reference's f32 accumulator."""
+
+    def __init__(self, samp_rate=None):
+        super().__init__(lib().rr_wpcr_create(float("nan") if samp_rate is None else float(samp_rate)), np.float32, np.float32)
+        self.samp_rate = samp_rate
+        self._lens = None           # of the most recent call (spectrum() sizes its buffer by them)
+
+    def _desc(self, starts, lens, mids):
+        st = np.ascontiguousarray(starts, np.uintp)
+        ln = np.ascontiguousarray(lens, np.uintp)
+        if st.ndim != 1 or st.shape != ln.shape:
+            raise ValueError("starts and lens must be two sequences of one length")
+        md = None if mids is None else np.ascontiguousarray(mids, np.float32)
+        if md is not None and md.shape != st.shape:
+            raise ValueError("mids must have one entry per burst")
+        return st, ln, md
+
+    def process_dev(self, d_samples: int, n_total: int, starts, lens, mids, d_syms: int, stream: int = 0) -> None:
+        """rr_wpcr_process_dev: burst b is d_samples[starts[b] : starts[b] + lens[b]] (raw device pointers to n_total f32 each);
+        its symbols go to d_syms[starts[b] :].  Asynchronous on `stream`; results() waits."""
+        st, ln, md = self._desc(starts, lens, mids)
+        if lib().rr_wpcr_process_dev(self._h, C.c_void_p(d_samples), n_total, _ptr(st), _ptr(ln), None if md is None else _ptr(md),
+                                     len(st), C.c_void_p(d_syms), C.c_void_p(stream)) != 0:
+            raise RuntimeError(last_error())
+        self._lens = ln
+
+    def process_buffer(self, samples: np.ndarray, starts, lens, mids=None) -> np.ndarray:
+        """rr_wpcr_process on host arrays -> syms, the same geometry as `samples`"""
+        x = np.ascontiguousarray(samples, np.float32)
+        st, ln, md = self._desc(starts, lens, mids)
+        syms = np.zeros(max(len(x), 1), np.float32)
+        if lib().rr_wpcr_process(self._h, _ptr(x), len(x), _ptr(st), _ptr(ln), None if md is None else _ptr(md), len(st),
+                                 _ptr(syms)) != 0:
+            raise RuntimeError(last_error())
+        self._lens = ln
+        return syms[:len(x)]
+
+    def results(self) -> np.ndarray:
+        """one WPCR_RESULT record per burst of the most recent process call (rr_wpcr_results; waits for it)"""
+        total = C.c_size_t(0)
+        if lib().rr_wpcr_results(self._h, None, 0, C.byref(total)) != 0:
+            raise RuntimeError(last_error())
+        res = np.zeros(max(total.value, 1), WPCR_RESULT)
+        if total.value and lib().rr_wpcr_results(self._h, _ptr(res), total.value, C.byref(total)) != 0:
+            raise RuntimeError(last_error())
+        return res[:total.value]
+
+    def tags(self, r) -> dict:
+        """the tags Wpcr pushes with a packet (wpcr.rs:187-194) from one result record"""
+        t = {"sps": r["sps"], "phase": r["phase"]}
+        if self.samp_rate is not None:
+            t["frequency"] = r["frequency"]
+        return t
+
+    def process(self, bursts, mids=None) -> list:
+        """what Wpcr::work does to each popped Vec<Float>, for a list of bursts in one call -> per burst (symbols, tags) or
+        None (the reference pushes nothing)"""
+        arrs = [np.ascontiguousarray(b, np.float32).ravel() for b in bursts]
+        lens = np.array([len(a) for a in arrs], np.uintp)
+        starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uintp) if len(arrs) else np.zeros(0, np.uintp)
+        x = np.concatenate(arrs) if arrs else np.zeros(0, np.float32)
+        syms = self.process_buffer(x, starts, lens, mids)
+        out = []
+        for s, r in zip(starts, self.results()):
+            out.append((syms[int(s):int(s) + int(r["nsyms"])].copy(), self.tags(r)) if r["ok"] else None)
+        return out
+
+    def spectrum(self, burst: int) -> np.ndarray:
+        """rr_debug_wpcr_spectrum: the f32 magnitudes mag[0 : N // 2] the decision for `burst` of the most recent call was taken on"""
+        n = C.c_size_t(0)
+        known = self._lens is not None and 0 <= burst < len(self._lens)
+        mag = np.zeros(max((int(self._lens[burst]) - 1) // 2, 1) if known else 1, np.float32)
+        if lib().rr_debug_wpcr_spectrum(self._h, burst, _ptr(mag), len(mag), C.byref(n)) != 0:
+            raise RuntimeError(last_error())
+        return mag[:n.value]
 
 
 def FmChainU8(taps, interp: int, deci: int, gain: float = 1.0, mode: int = ATAN2_EXACT) -> Block:

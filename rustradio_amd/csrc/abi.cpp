@@ -1,4 +1,5 @@
 // abi.cpp — the extern "C" surface declared in include/rustradio_amd.h.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -261,6 +262,55 @@ int rr_bit_tags(rr_block* b, size_t* pos, unsigned char* diffs, size_t cap, size
         const std::vector<unsigned long long>& e = d->fetch_tags();
         *total = e.size();
         for (size_t j = 0; j < e.size() && j < cap; j++) { pos[j] = (size_t)(e[j] >> 8); diffs[j] = (unsigned char)(e[j] & 0xff); }
+    });
+}
+rr_block* rr_wpcr_create(float samp_rate) {
+    return make_block([&] { return new rr::Wpcr(samp_rate); });
+}
+static rr::Wpcr* as_wpcr(rr_block* b, const char* what) {
+    auto* w = b ? dynamic_cast<rr::Wpcr*>(b->b.get()) : nullptr;
+    if (!w) rr::set_last_error(std::string(what) + ": not a wpcr handle");
+    return w;
+}
+int rr_wpcr_process_dev(rr_block* b, const void* d_samples, size_t n_total, size_t* starts, size_t* lens, const float* mid,
+                        size_t nbursts, void* d_syms, void* hip_stream) {
+    auto* w = as_wpcr(b, "rr_wpcr_process_dev");
+    if (!w) return RR_ERR;
+    if (nbursts && (!d_samples || !d_syms || !starts || !lens)) { rr::set_last_error("rr_wpcr_process_dev: null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(w->device));
+        hipStream_t s = static_cast<hipStream_t>(hip_stream);      // used as given (see rr_block_work_dev)
+        w->last_stream = s;
+        w->process_dev(static_cast<const float*>(d_samples), n_total, starts, lens, mid, nbursts, static_cast<float*>(d_syms), s);
+    });
+}
+int rr_wpcr_process(rr_block* b, const float* samples, size_t n_total, size_t* starts, size_t* lens, const float* mid, size_t nbursts,
+                    float* syms) {
+    auto* w = as_wpcr(b, "rr_wpcr_process");
+    if (!w) return RR_ERR;
+    if (nbursts && (!samples || !syms || !starts || !lens)) { rr::set_last_error("rr_wpcr_process: null argument"); return RR_ERR; }
+    return guarded([&] { w->process_host(samples, n_total, starts, lens, mid, nbursts, syms); });
+}
+int rr_wpcr_results(rr_block* b, rr_wpcr_result* res, size_t cap, size_t* total) {
+    auto* w = as_wpcr(b, "rr_wpcr_results");
+    if (!w) return RR_ERR;
+    if (!total || (cap && !res)) { rr::set_last_error("rr_wpcr_results: null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(w->device));
+        const std::vector<rr::WpcrResult>& r = w->fetch_results();
+        *total = r.size();
+        if (const size_t k = std::min(cap, r.size())) std::memcpy(res, r.data(), k * sizeof(rr_wpcr_result));   // (the same layout: blocks.cpp)
+    });
+}
+int rr_debug_wpcr_spectrum(rr_block* b, size_t burst, float* mag, size_t cap, size_t* nbins) {
+    auto* w = as_wpcr(b, "rr_debug_wpcr_spectrum");
+    if (!w) return RR_ERR;
+    if (!nbins || (cap && !mag)) { rr::set_last_error("rr_debug_wpcr_spectrum: null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(w->device));
+        const std::vector<float> m = w->fetch_spectrum(burst);
+        *nbins = m.size();
+        if (const size_t k = std::min(cap, m.size())) std::memcpy(mag, m.data(), k * sizeof(float));
     });
 }
 rr_block* rr_rtlsdr_decode_create(void) {

@@ -2414,6 +2414,106 @@ const std::vector<unsigned long long>& BitDecoder::fetch_tags() {
     return tags;
 }
 
+// ---- Wpcr (wpcr.rs:105-239; kernels_wpcr.hip) ---------------------------------------------------------------------------------------
+static_assert(sizeof(WpcrResult) == sizeof(rr_wpcr_result) && offsetof(WpcrResult, nsyms) == offsetof(rr_wpcr_result, nsyms) &&
+              offsetof(WpcrResult, frequency) == offsetof(rr_wpcr_result, frequency), "WpcrResult is rr_wpcr_result");
+Wpcr::Wpcr(float rate) : Block("Wpcr", 4, 4), samp_rate(rate) {}
+int Wpcr::work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) {
+    throw Error("Wpcr takes whole bursts: rr_wpcr_process / rr_wpcr_process_dev");
+}
+void Wpcr::check(size_t n_total, const size_t* st, const size_t* ln, size_t nbursts) {
+    if (nbursts && (!st || !ln)) throw Error("null burst descriptors");
+    size_t end = 0;
+    for (size_t b = 0; b < nbursts; b++) {
+        if (st[b] < end) throw Error("bursts overlap");
+        if (st[b] > n_total || ln[b] > n_total - st[b]) throw Error("burst outside the buffer");
+        if (ln[b] > MAX_LEN) throw Error("burst longer than 512000 samples");
+        end = st[b] + ln[b];
+    }
+}
+void Wpcr::process_dev(const float* d_x, size_t n_total, const size_t* st, const size_t* ln, const float* mid, size_t nbursts,
+                       float* d_syms, hipStream_t s) {
+    check(n_total, st, ln, nbursts);
+    if (nbursts > 0x3fffffff) throw Error("too many bursts");
+    starts.assign(st, st + nbursts);
+    lens.assign(ln, ln + nbursts);
+    results.clear();
+    fetched = true;
+    if (!nbursts) return;
+    // the records, then the burst of every sample tile, then of every bin tile
+    size_t nst = 0, nbt = 0;
+    for (size_t b = 0; b < nbursts; b++) {
+        nst += (ln[b] + WPCR_T - 1) / WPCR_T;
+        nbt += ln[b] ? ((ln[b] - 1) / 2 + WPCR_BT - 1) / WPCR_BT : 0;
+    }
+    if (nst > 0x7fffffff || nbt > 0x7fffffff) throw Error("too many tiles");
+    const size_t maps_at = nbursts * sizeof(WpcrBurst), bytes = maps_at + (nst + nbt) * sizeof(int);
+    hdesc.resize(bytes);
+    WpcrBurst* hb = reinterpret_cast<WpcrBurst*>(hdesc.data());
+    int* smap = reinterpret_cast<int*>(hdesc.data() + maps_at);
+    int* bmap = smap + nst;
+    size_t si = 0, bi = 0;
+    for (size_t b = 0; b < nbursts; b++) {
+        hb[b].start = (long)st[b];
+        hb[b].n = (int)ln[b];
+        hb[b].mid = mid ? mid[b] : 0.0f;
+        hb[b].stile0 = (int)si;
+        hb[b].btile0 = (int)bi;
+        const size_t ns = (ln[b] + WPCR_T - 1) / WPCR_T, nb = ln[b] ? ((ln[b] - 1) / 2 + WPCR_BT - 1) / WPCR_BT : 0;
+        for (size_t t = 0; t < ns; t++) smap[si++] = (int)b;
+        for (size_t t = 0; t < nb; t++) bmap[bi++] = (int)b;
+    }
+    desc.reserve(bytes);
+    list.reserve(n_total);
+    mag.reserve(n_total);
+    reim.reserve(n_total);
+    tilecnt.reserve(std::max<size_t>(nst, 1));
+    res.reserve(nbursts);
+    hstage().h2d(desc.p, hdesc.data(), bytes, s);                // (through the block's pinned chunks: hdesc is free on return)
+    const WpcrBurst* db = reinterpret_cast<const WpcrBurst*>(desc.p);
+    const int* dsmap = reinterpret_cast<const int*>(desc.p + maps_at);
+    prof_begin(s);
+    launch_wpcr(d_x, db, (long)nbursts, dsmap, (long)nst, dsmap + nst, (long)nbt, mid != nullptr, samp_rate, list.p, tilecnt.p, mag.p,
+                reim.p, res.p, d_syms, s);
+    prof_end(s);
+    fetched = false;
+}
+void Wpcr::process_host(const float* x, size_t n_total, const size_t* st, const size_t* ln, const float* mid, size_t nbursts,
+                        float* syms) {
+    RR_HIP(hipSetDevice(device));
+    last_stream = stream;
+    check(n_total, st, ln, nbursts);
+    h_in.reserve(std::max<size_t>(n_total, 1));
+    h_out.reserve(std::max<size_t>(n_total, 1));
+    // only the span of the bursts crosses the bus, in both directions
+    const size_t lo = nbursts ? st[0] : 0, hi = nbursts ? st[nbursts - 1] + ln[nbursts - 1] : 0;
+    if (hi > lo) {
+        hstage().h2d(h_in.p + lo, x + lo, (hi - lo) * sizeof(float), stream);
+        RR_HIP(hipMemsetAsync(h_out.p + lo, 0, (hi - lo) * sizeof(float), stream));
+    }
+    process_dev(h_in.p, n_total, st, ln, mid, nbursts, h_out.p, stream);
+    if (hi > lo) hstage().d2h(syms + lo, h_out.p + lo, (hi - lo) * sizeof(float), stream);
+    RR_HIP(hipStreamSynchronize(stream));
+    hstage().quiesced();
+}
+const std::vector<WpcrResult>& Wpcr::fetch_results() {
+    sync();
+    if (hstage_) hstage_->quiesced();
+    if (!fetched) {
+        results.resize(starts.size());
+        if (!results.empty()) stage_download_sync(results.data(), res.p, results.size() * sizeof(WpcrResult), stream);
+        fetched = true;
+    }
+    return results;
+}
+std::vector<float> Wpcr::fetch_spectrum(size_t burst) {
+    sync();
+    if (burst >= starts.size()) throw Error("rr_debug_wpcr_spectrum: no such burst in the most recent call");
+    std::vector<float> m(lens[burst] ? (lens[burst] - 1) / 2 : 0);
+    if (!m.empty()) stage_download_sync(m.data(), mag.p + starts[burst], m.size() * sizeof(float), stream);
+    return m;
+}
+
 // ---- RtlSdrDecode (rtlsdr_decode.rs:9-47) ----------------------------------------------------------------------
 RtlSdrDecode::RtlSdrDecode() : Block("RtlSdrDecode", 1, 8) {}
 int RtlSdrDecode::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed,

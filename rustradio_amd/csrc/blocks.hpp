@@ -620,6 +620,34 @@ struct BitDecoder : Block {
 // nullptr, or what is wrong with the parameters (said before any device is touched)
 const char* bits_check(int flags, unsigned long long seed, unsigned len, unsigned code_len);
 
+// Wpcr (wpcr.rs:105-239) in PDU form over a batch of disjoint bursts of one f32 buffer (kernels_wpcr.hip): no stream protocol
+// (work_dev is an error), no state between calls.  The scratch buffers are as long as the largest sample buffer so far and a
+// burst owns the range of each that its samples have in the input; the host keeps only the geometry of the latest call.
+struct Wpcr : Block {
+    static constexpr size_t MAX_LEN = 512000;     // the reference's stream capacity in f32 samples (stream.rs:105)
+    float samp_rate;                              // NaN: not set
+    DevBuf<unsigned> list, tilecnt;               // crossing positions (burst-owned slots); crossings of every sample tile
+    DevBuf<float> mag, reim;                      // |X[k]| and Re X / Im X of every burst's bins
+    DevBuf<unsigned char> desc;                   // this call's WpcrBurst records and the two tile -> burst maps
+    DevBuf<WpcrResult> res;
+    DevBuf<float> h_in, h_out;                    // process(): the host buffers' device copies
+    std::vector<unsigned char> hdesc;
+    std::vector<size_t> starts, lens;             // the latest call's geometry
+    bool fetched = true;                          // `results` holds the latest call's records
+    std::vector<WpcrResult> results;
+    explicit Wpcr(float samp_rate);
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+    // throws "bursts overlap" / "burst outside the buffer" / "burst longer than 512000 samples"; the process calls run it before
+    // anything is enqueued
+    static void check(size_t n_total, const size_t* st, const size_t* ln, size_t nbursts);
+    void process_dev(const float* d_x, size_t n_total, const size_t* st, const size_t* ln, const float* mid, size_t nbursts,
+                     float* d_syms, hipStream_t s);
+    void process_host(const float* x, size_t n_total, const size_t* st, const size_t* ln, const float* mid, size_t nbursts,
+                      float* syms);
+    const std::vector<WpcrResult>& fetch_results();          // waits for the latest call
+    std::vector<float> fetch_spectrum(size_t burst);         // ... and downloads mag[0 .. N / 2) of one of its bursts
+};
+
 // RtlSdrDecode (rtlsdr_decode.rs:9-47): stateless u8 pair -> Complex conversion.
 struct RtlSdrDecode : Block {
     RtlSdrDecode();

@@ -312,6 +312,33 @@ void launch_bits_tag_offsets(const unsigned* tilecnt, long ntiles, unsigned long
 void launch_bits_tag_gather(const unsigned* tilecnt, const unsigned long long* offs, const unsigned long long* list, long ntiles,
                             unsigned long long* out, hipStream_t s);
 
+// ---- kernels_wpcr.hip: Wpcr (wpcr.rs:105-239) over a batch of disjoint bursts of one f32 buffer, four launches ------------------
+// Burst b is x[start .. start + n); its scratch lives at the SAME offsets of buffers as long as x: list (the crossing
+// positions, tile t's at list[start + t WPCR_T ..)), mag (|X[k]| at mag[start + k], k < (n - 1) / 2), reim (Re X at
+// reim[start + k], Im X behind them) and its symbols at syms[start ..).  smap / bmap: the burst of every sample tile (WPCR_T
+// samples, ceil(n / WPCR_T) per burst) / bin tile (WPCR_BT bins, ceil(((n - 1) / 2) / WPCR_BT) per burst), tiles in burst order;
+// stile0 / btile0: a burst's first tile in them.  tilecnt: one counter per sample tile.  res: one record per burst, laid out as
+// rr_wpcr_result.  has_mid == false: mid is 0 in every record and the symbols are the samples' own bits.  nbursts == 0
+// launches nothing.
+constexpr int WPCR_T = 2048;                  // samples of one tile
+constexpr int WPCR_CH = 1024;                 // crossings of one LDS chunk of the transform
+constexpr int WPCR_BT = 1024;                 // bins of one tile
+struct WpcrBurst {
+    long start;
+    int n;
+    float mid;
+    int stile0, btile0;
+};
+struct WpcrResult {
+    int ok;
+    unsigned bin;
+    float sps, phase0, phase, frequency;
+    unsigned long long nsyms;
+};
+void launch_wpcr(const float* x, const WpcrBurst* bursts, long nbursts, const int* smap, long nstiles, const int* bmap, long nbtiles,
+                 bool has_mid, float samp_rate, unsigned* list, unsigned* tilecnt, float* mag, float* reim, WpcrResult* res,
+                 float* syms, hipStream_t s);
+
 // ---- head fix of the fused FirFilter -> FftFilter blocks (stream start only, a few hundred samples) ----------------
 // z[m] = sum_k t1[k] V[voff + m + L1 - 1 - k], m < n: the front FirFilter's first outputs (fir.rs:166-177) from the virtual stream
 void launch_head_z(VSrc<cf> V, long voff, const cf* t1, int L1, cf* z, long n, hipStream_t s);

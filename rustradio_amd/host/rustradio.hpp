@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstring>
 #include <condition_variable>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -755,6 +756,43 @@ public:
         return out;
     }
     size_t size() const { return size_; }
+};
+
+// ---- Wpcr (src/wpcr.rs:84-239): the message (PDU) form; process_one() is what work() does to each popped Vec<Float> -------------
+// (rr_wpcr_create / rr_wpcr_process / rr_wpcr_results).  process() takes a batch of bursts in ONE call; `mids`, when given, holds
+// Midpointer's offset per burst (wpcr.rs:75-78) instead of a rewritten burst.  The symbols are picked by the drift-free clock of
+// include/rustradio_amd.h, not by the reference's f32 accumulator.
+class Wpcr {
+    detail::Handle h_;
+    std::optional<Float> samp_rate_;
+public:
+    using Packet = std::pair<std::vector<Float>, std::vector<Tag>>;
+    explicit Wpcr(std::optional<Float> samp_rate = std::nullopt)                                   // WpcrBuilder::samp_rate (:91-96)
+        : h_(rr_wpcr_create(samp_rate ? *samp_rate : std::numeric_limits<Float>::quiet_NaN())), samp_rate_(samp_rate) {}
+    std::vector<std::optional<Packet>> process(const std::vector<std::vector<Float>>& bursts, const std::vector<Float>* mids = nullptr) {
+        if (mids && mids->size() != bursts.size()) throw Error("Wpcr: one mid per burst");
+        std::vector<size_t> starts(bursts.size()), lens(bursts.size());
+        size_t total = 0;
+        for (size_t b = 0; b < bursts.size(); b++) { starts[b] = total; lens[b] = bursts[b].size(); total += lens[b]; }
+        std::vector<Float> x(total + 1), syms(total + 1);
+        for (size_t b = 0; b < bursts.size(); b++) std::copy(bursts[b].begin(), bursts[b].end(), x.begin() + (long)starts[b]);
+        if (rr_wpcr_process(h_.h, x.data(), total, starts.data(), lens.data(), mids ? mids->data() : nullptr, bursts.size(), syms.data()) != 0)
+            throw Error(rr_last_error());
+        std::vector<rr_wpcr_result> res(bursts.size() + 1);
+        size_t n = 0;
+        if (rr_wpcr_results(h_.h, res.data(), bursts.size(), &n) != 0) throw Error(rr_last_error());
+        if (n != bursts.size()) throw Error("Wpcr: result count");
+        std::vector<std::optional<Packet>> out(bursts.size());
+        for (size_t b = 0; b < bursts.size(); b++) {
+            const rr_wpcr_result& r = res[b];
+            if (!r.ok) continue;                                                                  // None (:159-162): nothing is pushed
+            std::vector<Tag> tags{Tag(0, "sps", r.sps), Tag(0, "phase", r.phase)};                // :187-190
+            if (samp_rate_) tags.emplace_back(0, "frequency", r.frequency);                       // :191-194
+            out[b] = Packet(std::vector<Float>(syms.begin() + (long)starts[b], syms.begin() + (long)(starts[b] + r.nsyms)), std::move(tags));
+        }
+        return out;
+    }
+    std::optional<Packet> process_one(const std::vector<Float>& samples) { return process({samples})[0]; }   // :130-197
 };
 
 // ---- #[rustradio(sync)] blocks: MultiplyConst (src/multiply_const.rs), FastFM (src/quadrature_demod.rs:144-165) ----------
