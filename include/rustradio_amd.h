@@ -387,6 +387,69 @@ int rr_wpcr_process(rr_block *b, const float *samples, size_t n_total, size_t *s
  * the first min(*total, cap) records; *total = the call's nbursts; res == NULL with cap == 0 only counts. */
 int rr_wpcr_results(rr_block *b, rr_wpcr_result *res, size_t cap, size_t *total);
 
+/* BurstTagger::new(data, trigger, threshold, tag) (src/burst_tagger.rs:37-85) -> StreamToPdu::new(_, tag, max_size, tail)
+ * (src/stream_to_pdu.rs:88-280) -> optionally Midpointer (src/wpcr.rs:44-82) behind one handle: the middle of the burst
+ * receivers (examples/ax25-9600-wpcr.rs:103-139, ax25-1200-wpcr.rs, g3ruh.rs:216-219) between rr_burst_detector / rr_quaddemod
+ * and rr_wpcr.  f32 data and an f32 trigger in, one window of both per push; a PDU-forming block like rr_wpcr: rr_block_work on
+ * the handle is an error.
+ *   Edges.  cur(i) = trigger[i] > threshold (a NaN sample is not above; a NaN threshold gives no edges); an edge lies where
+ *     cur(i) != cur(i-1), cur(-1) being the previous push's last value and false at the start of the stream: what
+ *     rr_burst_detector reports.  Edges alternate strictly and the first one rises.
+ *   Bursts.  The PDUs of a stream are exactly those StreamToPdu pushes when fed BurstTagger's tags, whatever the split of the
+ *     stream into pushes.  With the rising edges r_j, their falling edges f_j, L = f_j - r_j and free = 0 at the start: a rising
+ *     edge with r_j < free is ignored together with its falling edge; an accepted one with L + tail <= max_size yields the PDU
+ *     [r_j, f_j + tail) and sets free = f_j + tail; any other accepted one yields nothing and sets free = r_j + max_size + 1.
+ *     A PDU is reported by the push that brings its last sample (and its falling edge); a burst still open is carried.
+ *   Arena.  The PDUs completed by a push lie ascending and disjoint in ONE device buffer (rr_pdu_arena_dev), a burst begun in an
+ *     earlier push whole: the geometry rr_wpcr_process_dev takes.  The block owns the carry (at most max_size samples, the two
+ *     arenas of alternate pushes); the caller keeps no old windows.
+ *   Midpointer (flags & RR_PDU_MIDPOINT), for all PDUs of the push at once: mean = fl32(S / len) with S summed in f64 (a
+ *     deviation: the reference sums in f32 in order; this is closer to the exact mean); nlow = the samples with !(x > mean);
+ *     in the total order of f32::total_cmp, low = the element of rank nlow / 2 and high = the element of rank
+ *     nlow + (len - nlow) / 2 (the reference's two medians: without a NaN the !(x > mean) side is a prefix of the sorted burst);
+ *     mid = low + (high - low) / 2.0f in f32.  ok = 0 (the reference pushes nothing) when the mean is NaN — then nlow = len —
+ *     or nlow is 0 or len; mid is 0 then.  The samples are not rewritten: rr_wpcr subtracts mid itself.
+ * NULL + rr_last_error: "max_size beyond 512000 samples" (a deviation: the reference has no limit, but Wpcr takes no longer
+ * burst), "unknown stream_to_pdu flags"; both are said before any device is touched. */
+enum { RR_PDU_MIDPOINT = 1 };
+typedef struct {
+    size_t start, len;            /* the burst is arena[start .. start + len) */
+    unsigned long long stream_pos;/* absolute position of its first sample in the data stream */
+    int ok;                       /* 0: Midpointer pushes nothing for this burst (NaN mean, or one side empty) */
+    float mean, mid;              /* Midpointer's mean and offset; 0 without RR_PDU_MIDPOINT */
+    size_t nlow;                  /* samples with !(x > mean) */
+} rr_pdu_record;
+rr_block *rr_stream_to_pdu_create(float threshold, size_t max_size, size_t tail, int flags);
+/* One window: n samples of data and of trigger (device pointers), n <= 1,024,000 (longer: RR_ERR).  Enqueued on hip_stream
+ * (used as given) and returns without waiting; 5 + ceil(log2(n / 2 + 1)) small launches whatever the trigger holds, one more
+ * with RR_PDU_MIDPOINT.  n == 0 launches nothing, reports no PDUs and leaves the state alone. */
+int rr_stream_to_pdu_push_dev(rr_block *b, const void *d_data, const void *d_trigger, size_t n, void *hip_stream);
+/* The same with host pointers: copies both down, runs and waits. */
+int rr_stream_to_pdu_push(rr_block *b, const float *data, const float *trigger, size_t n);
+/* The PDUs the most recent push completed, ascending.  Waits for it, writes the first min(*total, cap) records; rec == NULL with
+ * cap == 0 only counts (the contract of rr_wpcr_results). */
+int rr_pdu_records(rr_block *b, rr_pdu_record *rec, size_t cap, size_t *total);
+/* The edges of the most recent push, ascending: pos[j] window-relative, val[j] = cur (1: rising) — the contract of
+ * rr_burst_edges, and the same list when fed rr_burst_detector's output and threshold. */
+int rr_pdu_edges(rr_block *b, size_t *pos, unsigned char *val, size_t cap, size_t *total);
+/* The arena of the most recent push (device memory, *n_total f32: max_size + n); valid until the next push.  NULL, *n_total = 0
+ * before the first push and after a push of no samples. */
+const void *rr_pdu_arena_dev(rr_block *b, size_t *n_total);
+/* The samples of PDU idx of the most recent push, the first min(len, cap) of them, to the host. */
+int rr_pdu_fetch(rr_block *b, size_t idx, float *out, size_t cap);
+/* Midpointer -> Wpcr over the PDUs of the most recent push of `pdus`: waits for that push, takes its records with ok != 0 (all of
+ * them without RR_PDU_MIDPOINT) and calls rr_wpcr_process_dev on the arena with their `mid` (NULL without RR_PDU_MIDPOINT).
+ * d_syms holds the arena's n_total floats.  rr_wpcr_results then has one record per such PDU, in order. */
+int rr_wpcr_process_pdus(rr_block *wpcr, rr_block *pdus, void *d_syms, void *hip_stream);
+/* PduToStream (src/pdu_to_stream.rs:57-101) over the most recent process call of `wpcr`: the symbols of every burst with ok
+ * and nsyms > 0, in burst order, back to back in d_out (device, out_cap f32), by ONE gather launch on hip_stream (the offsets
+ * come from the host's copy of the results; the call waits for them).  *produced = symbols written; pdu_start[j] / pdu_len[j]
+ * (the first min(*npdus, cap) of them; NULL with cap == 0: none) = where packed PDU j begins in d_out and how long it is —
+ * the positions of PduToStream's `start` / `end` tags, the latter carrying U64(len).  out_cap too small: RR_ERR ("output
+ * shorter than the packed symbols"), nothing launched. */
+int rr_wpcr_pack_dev(rr_block *wpcr, const void *d_syms, void *d_out, size_t out_cap, size_t *produced,
+                     size_t *pdu_start, size_t *pdu_len, size_t cap, size_t *npdus, void *hip_stream);
+
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)
  * as wired in examples/ax25-1200-rx.rs:238-247: f32 in, Complex out, ONE decimating FIR with the composite
@@ -666,6 +729,10 @@ const char *rr_debug_last_kernel(const rr_block *b);
  * process call was taken on (the device keeps them anyway).  Waits for that call; writes the first min(*nbins, cap) of them,
  * *nbins = N / 2 (0 for a burst shorter than 2 samples). */
 int rr_debug_wpcr_spectrum(rr_block *b, size_t burst, float *mag, size_t cap, size_t *nbins);
+/* Introspection for tests: the two elements Midpointer's offset of PDU idx of the most recent push was made of — `low`, the
+ * element of rank nlow / 2, and `high`, the element of rank nlow + (len - nlow) / 2 (both 0 for a PDU with ok == 0).  Waits for
+ * that push.  RR_ERR for a handle without RR_PDU_MIDPOINT and for an idx beyond the push's PDUs. */
+int rr_debug_pdu_ranks(rr_block *b, size_t idx, float *low, float *high);
 
 /* ---- per-block knobs / introspection ------------------------------------------- */
 /* FftFilter: reference fft_size and nsamples (src/fft_filter.rs:261-262) and the

@@ -75,6 +75,11 @@ unsafe extern "C" {
     //  sps / phase / frequency tags — and its typed block needs rr_wpcr_process and rr_wpcr_results too; not written yet)
     #[allow(dead_code)]
     fn rr_wpcr_create(samp_rate: f32) -> *mut RrBlock;
+    // (declared for completeness: BurstTagger -> StreamToPdu -> Midpointer behind one handle takes two ReadStream<Float> and feeds an
+    //  NCWriteStream<Vec<Float>>; its typed block needs rr_stream_to_pdu_push, rr_pdu_records (a struct outside this file's FFI
+    //  map) and rr_pdu_fetch too; not written yet)
+    #[allow(dead_code)]
+    fn rr_stream_to_pdu_create(threshold: f32, max_size: usize, tail: usize, flags: c_int) -> *mut RrBlock;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;

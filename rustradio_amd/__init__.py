@@ -14,6 +14,7 @@ what the reference would pass to `consume()`/`produce()`.
     RtlSdrDecode         src/rtlsdr_decode.rs:9-47
     Hilbert              src/hilbert.rs:22-129
     Wpcr                 src/wpcr.rs:84-239      (message form: a batch of bursts per call)
+    StreamToPdu          src/burst_tagger.rs:68-85, src/stream_to_pdu.rs:198-275, src/wpcr.rs:44-82 (BurstTagger -> StreamToPdu -> Midpointer)
     low_pass / low_pass_complex / hilbert_taps / make_window   src/fir.rs:594-680, src/window.rs
 
 All sample arithmetic runs in HIP kernels on the GPU; nothing here computes samples.
@@ -739,6 +740,25 @@ class Wpcr(Block):
             out.append((syms[int(s):int(s) + int(r["nsyms"])].copy(), self.tags(r)) if r["ok"] else None)
         return out
 
+    def process_pdus(self, pdus: "StreamToPdu", d_syms: int, stream: int = 0) -> None:
+        """rr_wpcr_process_pdus: Midpointer -> Wpcr over the PDUs of the most recent push of `pdus`, on its arena; d_syms is a raw
+        device pointer to as many f32 as the arena holds.  results() then has one record per PDU with ok != 0."""
+        if lib().rr_wpcr_process_pdus(self._h, pdus._h, C.c_void_p(d_syms), C.c_void_p(stream)) != 0:
+            raise RuntimeError(last_error())
+        self._lens = None
+
+    def pack(self, d_syms: int, d_out: int, out_cap: int, stream: int = 0):
+        """rr_wpcr_pack_dev: PduToStream over the most recent process call -> (produced, pdu_start: uint64[], pdu_len: uint64[]):
+        the symbols of every burst with ok and nsyms > 0 back to back in d_out (raw device pointers), and where each begins"""
+        produced, npdus = C.c_size_t(0), C.c_size_t(0)
+        cap = len(self.results())
+        st = np.zeros(max(cap, 1), np.uintp)
+        ln = np.zeros(max(cap, 1), np.uintp)
+        if lib().rr_wpcr_pack_dev(self._h, C.c_void_p(d_syms), C.c_void_p(d_out), out_cap, C.byref(produced), _ptr(st), _ptr(ln), cap,
+                                  C.byref(npdus), C.c_void_p(stream)) != 0:
+            raise RuntimeError(last_error())
+        return produced.value, st[:npdus.value].astype(np.uint64), ln[:npdus.value].astype(np.uint64)
+
     def spectrum(self, burst: int) -> np.ndarray:
         """rr_debug_wpcr_spectrum: the f32 magnitudes mag[0 : N // 2] the decision for `burst` of the most recent call was taken on"""
         n = C.c_size_t(0)
@@ -747,6 +767,82 @@ class Wpcr(Block):
         if lib().rr_debug_wpcr_spectrum(self._h, burst, _ptr(mag), len(mag), C.byref(n)) != 0:
             raise RuntimeError(last_error())
         return mag[:n.value]
+
+
+PDU_MIDPOINT = 1            # RR_PDU_MIDPOINT
+PDU_MAX_WINDOW = 1_024_000  # samples of one push: the f32 stream capacity
+# rr_pdu_record
+PDU_RECORD = np.dtype([("start", np.uint64), ("len", np.uint64), ("stream_pos", np.uint64), ("ok", np.int32), ("mean", np.float32),
+                       ("mid", np.float32), ("nlow", np.uint64)], align=True)
+
+
+class StreamToPdu(Block):
+    """BurstTagger(threshold) -> StreamToPdu(max_size, tail) -> [Midpointer] behind one handle (rr_stream_to_pdu_create; not a
+    stream block: work() raises): f32 data and an f32 trigger in, one window of both per push; the PDUs a push completes lie in
+    one device arena, a burst begun in an earlier push whole.  See include/rustradio_amd.h for the rules."""
+
+    def __init__(self, threshold: float, max_size: int, tail: int, flags: int = 0):
+        super().__init__(lib().rr_stream_to_pdu_create(float(threshold), int(max_size), int(tail), int(flags)), np.float32, np.float32)
+        self.flags = flags
+
+    def push_dev(self, d_data: int, d_trigger: int, n: int, stream: int = 0) -> None:
+        """rr_stream_to_pdu_push_dev: raw device pointers to n f32 each; asynchronous on `stream`; records() waits"""
+        if lib().rr_stream_to_pdu_push_dev(self._h, C.c_void_p(d_data), C.c_void_p(d_trigger), n, C.c_void_p(stream)) != 0:
+            raise RuntimeError(last_error())
+
+    def push(self, data: np.ndarray, trigger: np.ndarray) -> np.ndarray:
+        """rr_stream_to_pdu_push on host arrays of one length -> records()"""
+        x = np.ascontiguousarray(data, np.float32).ravel()
+        t = np.ascontiguousarray(trigger, np.float32).ravel()
+        if x.shape != t.shape:
+            raise ValueError("data and trigger must have one length")
+        if lib().rr_stream_to_pdu_push(self._h, _ptr(x) if len(x) else None, _ptr(t) if len(t) else None, len(x)) != 0:
+            raise RuntimeError(last_error())
+        return self.records()
+
+    def records(self) -> np.ndarray:
+        """one PDU_RECORD per PDU the most recent push completed, ascending (rr_pdu_records; waits for it)"""
+        total = C.c_size_t(0)
+        if lib().rr_pdu_records(self._h, None, 0, C.byref(total)) != 0:
+            raise RuntimeError(last_error())
+        rec = np.zeros(max(total.value, 1), PDU_RECORD)
+        if total.value and lib().rr_pdu_records(self._h, _ptr(rec), total.value, C.byref(total)) != 0:
+            raise RuntimeError(last_error())
+        return rec[:total.value]
+
+    def edges(self):
+        """-> (pos: uint64[], val: bool[]) of the most recent push, ascending, window-relative (rr_pdu_edges)"""
+        total = C.c_size_t(0)
+        if lib().rr_pdu_edges(self._h, None, None, 0, C.byref(total)) != 0:
+            raise RuntimeError(last_error())
+        pos = np.zeros(max(total.value, 1), np.uint64)
+        val = np.zeros(max(total.value, 1), np.uint8)
+        if total.value and lib().rr_pdu_edges(self._h, _ptr(pos), _ptr(val), total.value, C.byref(total)) != 0:
+            raise RuntimeError(last_error())
+        return pos[:total.value], val[:total.value].astype(bool)
+
+    def arena_dev(self):
+        """-> (raw device pointer or None, n_total) of the most recent push's arena (rr_pdu_arena_dev); valid until the next push"""
+        n = C.c_size_t(0)
+        p = lib().rr_pdu_arena_dev(self._h, C.byref(n))
+        return p, n.value
+
+    def pdu(self, i: int, rec=None) -> np.ndarray:
+        """the samples of PDU i of the most recent push (rr_pdu_fetch)"""
+        r = self.records() if rec is None else rec
+        if not 0 <= i < len(r):
+            raise IndexError("no such PDU in the most recent push")
+        out = np.zeros(max(int(r[i]["len"]), 1), np.float32)
+        if lib().rr_pdu_fetch(self._h, i, _ptr(out), int(r[i]["len"])) != 0:
+            raise RuntimeError(last_error())
+        return out[:int(r[i]["len"])]
+
+    def ranks(self, i: int):
+        """rr_debug_pdu_ranks: (low, high), the two elements Midpointer's offset of PDU i of the most recent push was made of"""
+        lh = np.zeros(2, np.float32)
+        if lib().rr_debug_pdu_ranks(self._h, i, C.c_void_p(lh.ctypes.data), C.c_void_p(lh.ctypes.data + 4)) != 0:
+            raise RuntimeError(last_error())
+        return lh[0], lh[1]
 
 
 def FmChainU8(taps, interp: int, deci: int, gain: float = 1.0, mode: int = ATAN2_EXACT) -> Block:

@@ -10,6 +10,7 @@
 
 #include "blocks.hpp"
 #include "dstream.hpp"
+#include "pdu_host.hpp"
 #include "taps.hpp"
 
 struct rr_block {
@@ -311,6 +312,105 @@ int rr_debug_wpcr_spectrum(rr_block* b, size_t burst, float* mag, size_t cap, si
         const std::vector<float> m = w->fetch_spectrum(burst);
         *nbins = m.size();
         if (const size_t k = std::min(cap, m.size())) std::memcpy(mag, m.data(), k * sizeof(float));
+    });
+}
+rr_block* rr_stream_to_pdu_create(float threshold, size_t max_size, size_t tail, int flags) {
+    if (const char* e = rr::pdu_check(max_size, flags)) { rr::set_last_error(e); return nullptr; }     // before any device is touched
+    return make_block([&] { return new rr::StreamToPdu(threshold, max_size, tail, flags); });
+}
+static rr::StreamToPdu* as_pdu(rr_block* b, const char* what) {
+    auto* p = b ? dynamic_cast<rr::StreamToPdu*>(b->b.get()) : nullptr;
+    if (!p) rr::set_last_error(std::string(what) + ": not a stream_to_pdu handle");
+    return p;
+}
+int rr_stream_to_pdu_push_dev(rr_block* b, const void* d_data, const void* d_trigger, size_t n, void* hip_stream) {
+    auto* p = as_pdu(b, "rr_stream_to_pdu_push_dev");
+    if (!p) return RR_ERR;
+    if (n && (!d_data || !d_trigger)) { rr::set_last_error("rr_stream_to_pdu_push_dev: null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(p->device));
+        hipStream_t s = static_cast<hipStream_t>(hip_stream);      // used as given (see rr_block_work_dev)
+        p->last_stream = s;
+        p->push_dev(static_cast<const float*>(d_data), static_cast<const float*>(d_trigger), n, s);
+    });
+}
+int rr_stream_to_pdu_push(rr_block* b, const float* data, const float* trigger, size_t n) {
+    auto* p = as_pdu(b, "rr_stream_to_pdu_push");
+    if (!p) return RR_ERR;
+    if (n && (!data || !trigger)) { rr::set_last_error("rr_stream_to_pdu_push: null argument"); return RR_ERR; }
+    return guarded([&] { p->push_host(data, trigger, n); });
+}
+int rr_pdu_records(rr_block* b, rr_pdu_record* rec, size_t cap, size_t* total) {
+    auto* p = as_pdu(b, "rr_pdu_records");
+    if (!p) return RR_ERR;
+    if (!total || (cap && !rec)) { rr::set_last_error("rr_pdu_records: null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(p->device));
+        rr::pdu_copy_out(p->fetch_records(), rec, cap, total);
+    });
+}
+int rr_pdu_edges(rr_block* b, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
+    auto* p = as_pdu(b, "rr_pdu_edges");
+    if (!p) return RR_ERR;
+    if (!total || (cap && (!pos || !val))) { rr::set_last_error("rr_pdu_edges: null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(p->device));
+        const std::vector<unsigned>& e = p->fetch_edges();
+        *total = e.size();
+        for (size_t j = 0; j < e.size() && j < cap; j++) { pos[j] = (size_t)(e[j] >> 1); val[j] = (unsigned char)(e[j] & 1u); }
+    });
+}
+const void* rr_pdu_arena_dev(rr_block* b, size_t* n_total) {
+    auto* p = as_pdu(b, "rr_pdu_arena_dev");
+    if (n_total) *n_total = p ? p->n_total : 0;
+    return p ? p->arena_dev() : nullptr;
+}
+int rr_pdu_fetch(rr_block* b, size_t idx, float* out, size_t cap) {
+    auto* p = as_pdu(b, "rr_pdu_fetch");
+    if (!p) return RR_ERR;
+    if (cap && !out) { rr::set_last_error("rr_pdu_fetch: null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(p->device));
+        p->fetch_pdu(idx, out, cap);
+    });
+}
+int rr_debug_pdu_ranks(rr_block* b, size_t idx, float* low, float* high) {
+    auto* p = as_pdu(b, "rr_debug_pdu_ranks");
+    if (!p) return RR_ERR;
+    if (!low || !high) { rr::set_last_error("rr_debug_pdu_ranks: null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(p->device));
+        p->fetch_ranks(idx, low, high);
+    });
+}
+int rr_wpcr_process_pdus(rr_block* wpcr, rr_block* pdus, void* d_syms, void* hip_stream) {
+    auto* w = as_wpcr(wpcr, "rr_wpcr_process_pdus");
+    auto* p = as_pdu(pdus, "rr_wpcr_process_pdus");
+    if (!w || !p) return RR_ERR;
+    return guarded([&] {
+        RR_HIP(hipSetDevice(p->device));
+        if (w->device != p->device) throw rr::Error("rr_wpcr_process_pdus: the two handles live on different devices");
+        std::vector<size_t> starts, lens;
+        std::vector<float> mids;
+        if (const char* e = rr::pdu_select(p->fetch_records(), p->midpoint, p->n_total, rr::Wpcr::MAX_LEN, starts, lens, mids))
+            throw rr::Error(e);
+        if (!starts.empty() && !d_syms) throw rr::Error("rr_wpcr_process_pdus: null argument");
+        hipStream_t s = static_cast<hipStream_t>(hip_stream);
+        w->last_stream = s;
+        w->process_dev(p->arena_dev(), p->n_total, starts.data(), lens.data(), p->midpoint ? mids.data() : nullptr, starts.size(),
+                       static_cast<float*>(d_syms), s);
+    });
+}
+int rr_wpcr_pack_dev(rr_block* wpcr, const void* d_syms, void* d_out, size_t out_cap, size_t* produced, size_t* pdu_start,
+                     size_t* pdu_len, size_t cap, size_t* npdus, void* hip_stream) {
+    auto* w = as_wpcr(wpcr, "rr_wpcr_pack_dev");
+    if (!w) return RR_ERR;
+    if (!produced || !npdus) { rr::set_last_error("rr_wpcr_pack_dev: null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(w->device));
+        hipStream_t s = static_cast<hipStream_t>(hip_stream);
+        w->pack_dev(static_cast<const float*>(d_syms), static_cast<float*>(d_out), out_cap, produced, pdu_start, pdu_len, cap, npdus, s);
+        w->last_stream = s;
     });
 }
 rr_block* rr_rtlsdr_decode_create(void) {

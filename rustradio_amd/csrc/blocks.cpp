@@ -16,6 +16,7 @@
 #include <cstring>
 #include <unistd.h>
 
+#include "pdu_host.hpp"
 #include "stage.hpp"
 #include "taps.hpp"
 
@@ -2512,6 +2513,141 @@ std::vector<float> Wpcr::fetch_spectrum(size_t burst) {
     std::vector<float> m(lens[burst] ? (lens[burst] - 1) / 2 : 0);
     if (!m.empty()) stage_download_sync(m.data(), mag.p + starts[burst], m.size() * sizeof(float), stream);
     return m;
+}
+
+// ---- StreamToPdu (burst_tagger.rs:68-85, stream_to_pdu.rs:198-275, wpcr.rs:62-78; kernels_pdu.hip) -------------------------------------
+static_assert(sizeof(PduRec) == sizeof(rr_pdu_record) && offsetof(PduRec, nlow) == offsetof(rr_pdu_record, nlow) &&
+              offsetof(PduRec, mid) == offsetof(rr_pdu_record, mid) && offsetof(PduRec, stream_pos) == offsetof(rr_pdu_record, stream_pos),
+              "PduRec is rr_pdu_record");
+StreamToPdu::StreamToPdu(float threshold, size_t max_sz, size_t tl, int flags)
+    : Block("BurstTagger>StreamToPdu>Midpointer", 4, 4), thr(threshold), max_size(max_sz),
+      tail(std::min(tl, max_sz + 1)),          // (a tail beyond max_size files nothing, like max_size + 1: no sum below overflows)
+      midpoint((flags & RR_PDU_MIDPOINT) != 0) {
+    if (const char* e = pdu_check(max_sz, flags)) throw Error(e);
+    PduState init{};
+    init.free = 0;                             // Unsync, last_state false (stream_to_pdu.rs:102, burst_tagger.rs:62)
+    init.open_r = init.open_f = PDU_NONE;
+    st[0].upload(&init, 1, stream);
+    st[1].upload(&init, 1, stream);
+    etotal.reserve(1);
+    count.reserve(1);
+    root.reserve(1);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+int StreamToPdu::work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) {
+    throw Error("StreamToPdu forms PDUs: rr_stream_to_pdu_push / rr_stream_to_pdu_push_dev");
+}
+void StreamToPdu::push_dev(const float* d_data, const float* d_trig, size_t n, hipStream_t s) {
+    if (n > MAX_WINDOW) throw Error("window longer than 1024000 samples");
+    records.clear();
+    edgelist.clear();
+    fetched = efetched = true;                 // a push that moves nothing has no PDUs and no edges and leaves every state alone
+    last_n = n;
+    n_total = 0;
+    if (!n) return;
+    const int a = acur ^ 1;
+    const size_t ntiles = (n + PDU_T - 1) / PDU_T, nr = n / 2 + 2;
+    arena[a].reserve(max_size + n);
+    tilecnt.reserve(ntiles);
+    offs.reserve(ntiles);
+    edges.reserve(n);
+    jmp[0].reserve(nr);
+    jmp[1].reserve(nr);
+    mark.reserve(nr);
+    recs.reserve(nr);
+    if (midpoint) ranks.reserve(2 * nr);
+    PduArgs g{};
+    g.data = d_data; g.trig = d_trig; g.n = (long)n; g.thr = thr;
+    g.max_size = max_size; g.tail = tail; g.w0 = w0; g.C = (long)max_size;
+    g.prev_arena = arena[acur].p;              // (nullptr before the first push: nothing is open then)
+    g.n_prev = (long)n_prev;
+    g.arena = arena[a].p;
+    g.st_in = st[cur].p; g.st_out = st[cur ^ 1].p;
+    g.tilecnt = tilecnt.p; g.offs = offs.p; g.etotal = etotal.p; g.edges = edges.p;
+    g.jmp0 = jmp[0].p; g.jmp1 = jmp[1].p; g.mark = mark.p; g.root = root.p;
+    g.recs = recs.p; g.rec_cap = (long)nr; g.count = count.p; g.ranks = ranks.p; g.midpoint = midpoint;
+    prof_begin(s);
+    launch_pdu(g, s);
+    prof_end(s);
+    acur = a;
+    cur ^= 1;
+    n_prev = n;
+    n_total = max_size + n;
+    w0 += n;
+    fetched = efetched = false;
+}
+void StreamToPdu::push_host(const float* data, const float* trig, size_t n) {
+    RR_HIP(hipSetDevice(device));
+    last_stream = stream;
+    if (n > MAX_WINDOW) throw Error("window longer than 1024000 samples");
+    if (n) {
+        h_data.reserve(n);
+        h_trig.reserve(n);
+        hstage().h2d(h_data.p, data, n * sizeof(float), stream);
+        hstage().h2d(h_trig.p, trig, n * sizeof(float), stream);
+    }
+    push_dev(h_data.p, h_trig.p, n, stream);
+    RR_HIP(hipStreamSynchronize(stream));
+    hstage().quiesced();
+}
+const std::vector<rr_pdu_record>& StreamToPdu::fetch_records() {
+    sync();
+    if (hstage_) hstage_->quiesced();
+    if (!fetched) {
+        unsigned long long k = 0;
+        stage_download_sync(&k, count.p, sizeof k, stream);
+        if (const char* e = pdu_count_check(k, recs.cap)) throw Error(e);
+        records.resize((size_t)k);
+        if (k) stage_download_sync(records.data(), recs.p, (size_t)k * sizeof(rr_pdu_record), stream);
+        pdu_sort(records, slots);              // the device appends in no order
+        fetched = true;
+    }
+    return records;
+}
+const std::vector<unsigned>& StreamToPdu::fetch_edges() {
+    sync();
+    if (hstage_) hstage_->quiesced();
+    if (!efetched) {
+        unsigned long long k = 0;
+        stage_download_sync(&k, etotal.p, sizeof k, stream);
+        if (k > last_n) throw Error("stream_to_pdu: edge count beyond the window");
+        edgelist.resize((size_t)k);
+        if (k) stage_download_sync(edgelist.data(), edges.p, (size_t)k * sizeof(unsigned), stream);
+        efetched = true;
+    }
+    return edgelist;
+}
+void StreamToPdu::fetch_pdu(size_t idx, float* out, size_t cap) {
+    const std::vector<rr_pdu_record>& r = fetch_records();
+    if (idx >= r.size()) throw Error("rr_pdu_fetch: no such PDU in the most recent push");
+    if (r[idx].start > n_total || r[idx].len > n_total - r[idx].start) throw Error("stream_to_pdu: record outside the arena");
+    if (const size_t k = std::min(cap, r[idx].len)) stage_download_sync(out, arena[acur].p + r[idx].start, k * sizeof(float), stream);
+}
+void StreamToPdu::fetch_ranks(size_t idx, float* low, float* high) {
+    const std::vector<rr_pdu_record>& r = fetch_records();
+    if (!midpoint) throw Error("rr_debug_pdu_ranks: the handle runs no Midpointer");
+    if (idx >= r.size() || idx >= slots.size()) throw Error("rr_debug_pdu_ranks: no such PDU in the most recent push");
+    float lh[2] = {0.0f, 0.0f};
+    stage_download_sync(lh, ranks.p + 2 * slots[idx], sizeof lh, stream);
+    *low = lh[0];
+    *high = lh[1];
+}
+void Wpcr::pack_dev(const float* d_syms, float* d_out, size_t out_cap, size_t* produced, size_t* pdu_start, size_t* pdu_len, size_t cap,
+                    size_t* npdus, hipStream_t s) {
+    const std::vector<WpcrResult>& r = fetch_results();
+    static_assert(sizeof(WpcrResult) == sizeof(rr_wpcr_result), "WpcrResult is rr_wpcr_result");
+    std::vector<rr_wpcr_result> res(r.size());
+    if (!r.empty()) std::memcpy(res.data(), r.data(), r.size() * sizeof(rr_wpcr_result));
+    size_t k = 0;
+    const size_t total = pdu_pack_plan(res, starts, hpack, pdu_start, pdu_len, cap, &k);
+    if (total > out_cap) throw Error("output shorter than the packed symbols");
+    *produced = total;
+    *npdus = k;
+    if (!total) return;
+    if (!d_syms || !d_out) throw Error("rr_wpcr_pack_dev: null argument");
+    pack_desc.reserve(hpack.size());
+    hstage().h2d(pack_desc.p, hpack.data(), hpack.size() * sizeof(long), s);
+    launch_pdu_pack(d_syms, pack_desc.p, (long)(hpack.size() / 3), (long)total, d_out, s);
 }
 
 // ---- RtlSdrDecode (rtlsdr_decode.rs:9-47) ----------------------------------------------------------------------

@@ -646,6 +646,47 @@ struct Wpcr : Block {
                       float* syms);
     const std::vector<WpcrResult>& fetch_results();          // waits for the latest call
     std::vector<float> fetch_spectrum(size_t burst);         // ... and downloads mag[0 .. N / 2) of one of its bursts
+    // PduToStream over the latest call (rr_wpcr_pack_dev): waits for its results, then one gather launch on s
+    DevBuf<long> pack_desc;
+    std::vector<long> hpack;
+    void pack_dev(const float* d_syms, float* d_out, size_t out_cap, size_t* produced, size_t* pdu_start, size_t* pdu_len, size_t cap,
+                  size_t* npdus, hipStream_t s);
+};
+
+// BurstTagger -> StreamToPdu -> [Midpointer] over windows of an f32 data / trigger stream pair (kernels_pdu.hip): no stream
+// protocol (work_dev is an error).  The state between pushes (PduState) stays on the device; the two arenas alternate, and the
+// one of the previous push holds the samples of a burst that is still open, so they are the carry as well.
+struct StreamToPdu : Block {
+    static constexpr size_t MAX_WINDOW = 1024000;         // the f32 stream capacity in samples (stream.rs:105)
+    float thr;
+    size_t max_size, tail;
+    bool midpoint;
+    DevBuf<PduState> st[2];
+    int cur = 0;
+    DevBuf<float> arena[2];
+    int acur = 0;                                 // the arena of the most recent push that moved samples
+    size_t n_prev = 0, n_total = 0;               // its window; its length (0: no such push yet, or the latest push was empty)
+    unsigned long long w0 = 0;                    // samples of the stream so far
+    DevBuf<unsigned> tilecnt, edges, jmp[2], mark;
+    DevBuf<unsigned long long> offs, etotal, count;
+    DevBuf<PduRoot> root;
+    DevBuf<PduRec> recs;
+    DevBuf<float> ranks;                          // Midpointer's low and high per record slot (rr_debug_pdu_ranks)
+    DevBuf<float> h_data, h_trig;                 // push(): the host windows' device copies
+    size_t last_n = 0;                            // the most recent push's window
+    bool fetched = true, efetched = true;         // `records` / `edgelist` hold the most recent push's
+    std::vector<rr_pdu_record> records;           // ... ascending
+    std::vector<size_t> slots;                    // record i's place in the device's (unordered) list
+    std::vector<unsigned> edgelist;               // (pos << 1) | cur, ascending
+    StreamToPdu(float threshold, size_t max_size, size_t tail, int flags);
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+    void push_dev(const float* d_data, const float* d_trig, size_t n, hipStream_t s);
+    void push_host(const float* data, const float* trig, size_t n);
+    const std::vector<rr_pdu_record>& fetch_records();      // waits for the most recent push
+    const std::vector<unsigned>& fetch_edges();
+    const float* arena_dev() const { return n_total ? arena[acur].p : nullptr; }
+    void fetch_pdu(size_t idx, float* out, size_t cap);
+    void fetch_ranks(size_t idx, float* low, float* high);  // the two elements Midpointer's offset of PDU idx was made of
 };
 
 // RtlSdrDecode (rtlsdr_decode.rs:9-47): stateless u8 pair -> Complex conversion.

@@ -339,6 +339,64 @@ void launch_wpcr(const float* x, const WpcrBurst* bursts, long nbursts, const in
                  bool has_mid, float samp_rate, unsigned* list, unsigned* tilecnt, float* mag, float* reim, WpcrResult* res,
                  float* syms, hipStream_t s);
 
+// ---- kernels_pdu.hip: BurstTagger -> StreamToPdu -> Midpointer over one window of a data / trigger stream pair ------------------
+// All positions in the state are ABSOLUTE stream positions; w0 is the window's first.  The arena of a push is the virtual stream
+// "open burst ++ window": arena[C + i] = data[i], i < n, and the samples of a burst still open from earlier pushes in front of
+// it, ending at arena[C) (C = max_size: an open burst never holds more).  They are taken from the PREVIOUS push's arena
+// (prev_arena, whose window was n_prev samples), so the two arenas are the block's double-buffered carry.
+// edges: (pos << 1) | cur, ascending, *etotal of them (at most n).  jmp0 / jmp1 / mark: n / 2 + 2 entries each.  recs: n / 2 + 2
+// records, appended in no order; *count of them (zeroed by the launcher).  n == 0 launches nothing.
+constexpr int PDU_T = 2048;                   // samples of one tile
+constexpr unsigned long long PDU_NONE = ~0ull;
+struct PduState {
+    unsigned long long free;                  // the first position at which a rising edge is taken again
+    unsigned long long open_r, open_f;        // the accepted burst that has not been filed yet: its rising edge and, once seen, its
+                                              // falling edge (PDU_NONE otherwise)
+    int last, pad;                            // cur(-1)
+};
+struct PduRoot {                              // what the carried state and the window's first edge decide (k_pdu_next)
+    unsigned long long free;                  // `free` in front of the window's first rising edge
+    unsigned long long open_r, open_f;        // the carried burst after the window's first edge has been seen
+    long j0;                                  // the first accepted rising edge of the window (R: none)
+    long R;                                   // rising edges of the window
+};
+struct PduRec {                               // rr_pdu_record
+    unsigned long long start, len, stream_pos;
+    int ok;
+    float mean, mid;
+    unsigned long long nlow;
+};
+struct PduArgs {
+    const float* data;
+    const float* trig;
+    long n;
+    float thr;
+    unsigned long long max_size, tail, w0;
+    long C;
+    const float* prev_arena;
+    long n_prev;
+    float* arena;
+    const PduState* st_in;
+    PduState* st_out;
+    unsigned* tilecnt;
+    unsigned long long* offs;
+    unsigned long long* etotal;
+    unsigned* edges;
+    unsigned* jmp0;
+    unsigned* jmp1;
+    unsigned* mark;
+    PduRoot* root;
+    PduRec* recs;
+    long rec_cap;
+    unsigned long long* count;
+    float* ranks;                             // with midpoint: low and high of record slot k at [2 k], [2 k + 1] (0 when ok == 0)
+    bool midpoint;
+};
+void launch_pdu(const PduArgs& a, hipStream_t s);
+// PduToStream over a batch: out[dst[b] + i] = syms[src[b] + i], i < len[b]; desc holds nb (src, dst, len) triples ascending in
+// dst without gaps, total = their lengths' sum.  One launch; total == 0 launches nothing.
+void launch_pdu_pack(const float* syms, const long* desc, long nb, long total, float* out, hipStream_t s);
+
 // ---- head fix of the fused FirFilter -> FftFilter blocks (stream start only, a few hundred samples) ----------------
 // z[m] = sum_k t1[k] V[voff + m + L1 - 1 - k], m < n: the front FirFilter's first outputs (fir.rs:166-177) from the virtual stream
 void launch_head_z(VSrc<cf> V, long voff, const cf* t1, int L1, cf* z, long n, hipStream_t s);

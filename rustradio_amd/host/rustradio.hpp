@@ -795,6 +795,57 @@ public:
     std::optional<Packet> process_one(const std::vector<Float>& samples) { return process({samples})[0]; }   // :130-197
 };
 
+// ---- BurstTagger -> StreamToPdu -> [Midpointer] (src/burst_tagger.rs:68-85, src/stream_to_pdu.rs:198-275, src/wpcr.rs:44-82) -----------
+// (rr_stream_to_pdu_create / rr_stream_to_pdu_push / rr_pdu_records / rr_pdu_fetch).  push() takes one window of the data stream
+// and of the trigger stream and returns what StreamToPdu's output would receive for it: the PDUs this window completes, a burst
+// begun in an earlier window whole.  With `midpoint` a Pdu also carries Midpointer's offset (`mid` empty: Midpointer pushes
+// nothing for it); centred() is the Vec<Float> Midpointer would push.  The block keeps the open burst: no window is kept here.
+class StreamToPdu {
+    detail::Handle h_;
+    bool midpoint_;
+public:
+    struct Pdu {
+        unsigned long long stream_pos;                // absolute position of the first sample in the data stream
+        std::vector<Float> samples;
+        std::optional<Float> mid;                     // Midpointer's offset (wpcr.rs:75)
+        std::vector<Float> centred() const {          // wpcr.rs:77-78
+            std::vector<Float> v(samples);
+            if (mid) for (auto& t : v) t -= *mid;
+            return v;
+        }
+    };
+    StreamToPdu(Float threshold, size_t max_size, size_t tail, bool midpoint = false)
+        : h_(rr_stream_to_pdu_create(threshold, max_size, tail, midpoint ? RR_PDU_MIDPOINT : 0)), midpoint_(midpoint) {}
+    rr_block* handle() const { return h_.h; }
+    std::vector<Pdu> push(const std::vector<Float>& data, const std::vector<Float>& trigger) {
+        if (data.size() != trigger.size()) throw Error("StreamToPdu: data and trigger must have one length");
+        if (rr_stream_to_pdu_push(h_.h, data.data(), trigger.data(), data.size()) != 0) throw Error(rr_last_error());
+        size_t n = 0;
+        if (rr_pdu_records(h_.h, nullptr, 0, &n) != 0) throw Error(rr_last_error());
+        std::vector<rr_pdu_record> rec(n + 1);
+        if (n && rr_pdu_records(h_.h, rec.data(), n, &n) != 0) throw Error(rr_last_error());
+        std::vector<Pdu> out(n);
+        for (size_t i = 0; i < n; i++) {
+            out[i].stream_pos = rec[i].stream_pos;
+            out[i].samples.resize(rec[i].len);
+            if (rr_pdu_fetch(h_.h, i, out[i].samples.data(), rec[i].len) != 0) throw Error(rr_last_error());
+            if (midpoint_ && rec[i].ok) out[i].mid = rec[i].mid;
+        }
+        return out;
+    }
+    // the tags BurstTagger pushed in the most recent window: (window-relative position, value)
+    std::vector<std::pair<size_t, bool>> edges() {
+        size_t n = 0;
+        if (rr_pdu_edges(h_.h, nullptr, nullptr, 0, &n) != 0) throw Error(rr_last_error());
+        std::vector<size_t> pos(n + 1);
+        std::vector<unsigned char> val(n + 1);
+        if (n && rr_pdu_edges(h_.h, pos.data(), val.data(), n, &n) != 0) throw Error(rr_last_error());
+        std::vector<std::pair<size_t, bool>> out(n);
+        for (size_t i = 0; i < n; i++) out[i] = {pos[i], val[i] != 0};
+        return out;
+    }
+};
+
 // ---- #[rustradio(sync)] blocks: MultiplyConst (src/multiply_const.rs), FastFM (src/quadrature_demod.rs:144-165) ----------
 // work() per rustradio_macros_code/src/lib.rs:458-515; a tag at position pos < n passes through at pos.
 template <class In, class Out> class SyncBlock : public Block {
