@@ -450,6 +450,67 @@ int rr_wpcr_process_pdus(rr_block *wpcr, rr_block *pdus, void *d_syms, void *hip
 int rr_wpcr_pack_dev(rr_block *wpcr, const void *d_syms, void *d_out, size_t out_cap, size_t *produced,
                      size_t *pdu_start, size_t *pdu_len, size_t cap, size_t *npdus, void *hip_stream);
 
+/* The bit-level blocks of the packet TRANSMITTERS (examples/g3ruh.rs:250-267, examples/bell202.rs:160-176), the mirror image of
+ * the sync blocks above: u8 in, u8 out, #[rustradio(sync)]: n = min(in_len, out_cap) samples per call, tags RR_TAGS_FORWARD, 1.
+ * Exact in integers: bit-identical to the reference whatever the split of the stream into calls; the state between calls stays
+ * on the device.  Only the lowest bit of an input byte is read.  Three small launches per call.
+ *
+ * NrziEncode::new(src) (src/nrzi.rs:52-69): out[n] = out[n-1] ^ (in[n] == 0), out[-1] = 0 at the start of the stream. */
+rr_block *rr_nrzi_encode_create(void);
+/* Scrambler::g3ruh(src) (src/descrambler.rs:41-47, 95-123): with s[n] = in[n] ^ s[n-12] ^ s[n-17] and every s before the stream
+ * 0, out[n] = s[n-17].  So the first 17 outputs of a stream are 0, n input bits give n output bits, and the last 17 bits stay in
+ * the register until more input comes (the reference's behaviour, kept). */
+rr_block *rr_scrambler_g3ruh_create(void);
+
+/* FcsAdder (src/hdlc_framer.rs:28-42) -> HdlcFramer (hdlc_encode, src/hdlc_framer.rs:60-86) -> PduToStream<u8>
+ * (src/pdu_to_stream.rs:57-101) -> [Scrambler::g3ruh] -> [NrziEncode] -> [Map(bit ? hi : lo)] behind one handle: everything of the
+ * transmit chains in front of RationalResampler, in the order of examples/g3ruh.rs.  (RationalResampler copies samples and never
+ * filters, src/rational_resampler.rs:183-197, so the Map commutes with it: the f32 levels at the bit rate are what rr_fm_tx
+ * takes.)  A PDU-form block like rr_wpcr: rr_block_work on the handle is an error.  One push takes a BATCH of packets inside one
+ * byte buffer and frames them in array order; every stage is bit-identical to the reference's block:
+ *   FcsAdder (RR_FRAME_FCS): CRC-16/X.25 (calc_crc, src/hdlc_deframer.rs:309-315) appended low byte first; rec.fcs holds it
+ *     (0 without the flag).
+ *   HdlcFramer: 20 flags 01111110, the bytes LSB first with a 0 stuffed behind every fifth consecutive 1, 20 flags.  The count
+ *     of ones starts at 0 for every packet and is reset by a stuffed bit; five ones that end the packet are still followed by
+ *     their 0; an empty packet without FCS is 320 bits of flags.  rec.stuffed = the stuffed bits.
+ *   PduToStream: the frames lie back to back in d_out; rec.start / rec.len are the positions of its `start` tag and of the
+ *     U64(len) it carries.  The sum of the lengths is *produced.
+ *   Scrambler::g3ruh (RR_FRAME_G3RUH), then NrziEncode (RR_FRAME_NRZI), both as the sync blocks above over the concatenated
+ *     stream: the register and the level are carried from push to push, so the output of a stream of packets is the same
+ *     whatever its split into pushes.
+ *   Map (RR_FRAME_SYMBOLS): d_out is f32 and out = bit ? hi : lo; without the flag d_out is u8 and lo / hi are ignored.
+ * NULL + rr_last_error: "unknown hdlc framer flags", said before any device is touched. */
+enum { RR_FRAME_FCS = 1, RR_FRAME_G3RUH = 2, RR_FRAME_NRZI = 4, RR_FRAME_SYMBOLS = 8 };
+typedef struct {
+    size_t start, len;      /* the frame is d_out[start .. start + len) */
+    unsigned stuffed;       /* stuffed bits of the frame: len = 320 + 8 L + stuffed, L = the packet's bytes (+ 2 with the FCS) */
+    unsigned short fcs;     /* the FCS FcsAdder appended; 0 without RR_FRAME_FCS */
+} rr_frame_record;
+rr_block *rr_hdlc_framer_create(int flags, float lo, float hi);
+/* The elements a push of these packets can produce at most: the sum of 320 + 8 L + floor(8 L / 5), L = lens[p] (+ 2 with the
+ * FCS); an all-ones payload reaches it.  (size_t)-1 where that overflows; 0 for a handle that is no framer. */
+size_t rr_hdlc_framer_bound(const rr_block *b, const size_t *lens, size_t npackets);
+/* Packet p is d_bytes[starts[p] .. starts[p] + lens[p]) of the device buffer d_bytes (n_bytes u8); starts and lens are HOST
+ * arrays in the convention of rr_wpcr_process_dev, read before the call returns.  The ranges must lie inside n_bytes ("packet
+ * outside the buffer") but may overlap or repeat: the input is only read.  d_out (device, out_cap elements, u8 or f32 by
+ * RR_FRAME_SYMBOLS) must hold rr_hdlc_framer_bound elements, else RR_ERR ("output shorter than the framed bits can be"); a bound
+ * above 2^30 elements is RR_ERR too.  Every refusal is made before any device is touched and launches nothing.  Elements of
+ * d_out at and beyond the produced ones are never written.  Enqueued on hip_stream (used as given) and returns without
+ * waiting: 3 launches for the framer, 2 more with RR_FRAME_FCS, 3 more with RR_FRAME_G3RUH or RR_FRAME_NRZI and 1 more with
+ * RR_FRAME_SYMBOLS alone — whatever the packets hold.  npackets == 0 launches nothing and leaves the state alone. */
+int rr_hdlc_framer_push_dev(rr_block *b, const void *d_bytes, size_t n_bytes, size_t *starts, size_t *lens, size_t npackets,
+                            void *d_out, size_t out_cap, void *hip_stream);
+/* The same with host pointers: copies the bytes down, runs, waits and copies the *produced elements of the push back. */
+int rr_hdlc_framer_push(rr_block *b, const unsigned char *bytes, size_t n_bytes, size_t *starts, size_t *lens, size_t npackets,
+                        void *out, size_t out_cap, size_t *produced);
+/* One record per packet of the most recent push, in packet order, and the elements it produced.  Waits for that push, writes the
+ * first min(*total, cap) records; rec == NULL with cap == 0 only counts (the contract of rr_wpcr_results).  The host buffers
+ * behind it are sized from the packet count, and what the device counted is checked against the bound before it is used. */
+int rr_hdlc_framer_records(rr_block *b, rr_frame_record *rec, size_t cap, size_t *total, size_t *produced);
+/* *tile_bits = the payload bits of one tile of the stuffing scan, which is also the tile of the line coder (tests aim at the
+ * seams with it). */
+int rr_hdlc_framer_dims(const rr_block *b, size_t *tile_bits);
+
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)
  * as wired in examples/ax25-1200-rx.rs:238-247: f32 in, Complex out, ONE decimating FIR with the composite

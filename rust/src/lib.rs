@@ -80,6 +80,18 @@ unsafe extern "C" {
     //  map) and rr_pdu_fetch too; not written yet)
     #[allow(dead_code)]
     fn rr_stream_to_pdu_create(threshold: f32, max_size: usize, tail: usize, flags: c_int) -> *mut RrBlock;
+    fn rr_nrzi_encode_create() -> *mut RrBlock;
+    fn rr_scrambler_g3ruh_create() -> *mut RrBlock;
+    // (declared for completeness: FcsAdder -> HdlcFramer -> PduToStream behind one handle takes an NCReadStream<Vec<u8>> and feeds a
+    //  WriteStream<u8> or <Float> with the `start` tags; its typed block needs rr_hdlc_framer_bound and rr_hdlc_framer_records (types
+    //  outside this file's FFI map) too; not written yet)
+    #[allow(dead_code)]
+    fn rr_hdlc_framer_create(flags: c_int, lo: f32, hi: f32) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_hdlc_framer_push_dev(b: *mut RrBlock, d_bytes: *const c_void, n_bytes: usize, starts: *mut usize, lens: *mut usize,
+                               npackets: usize, d_out: *mut c_void, out_cap: usize, hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_hdlc_framer_dims(b: *const RrBlock, tile_bits: *mut usize) -> c_int;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;
@@ -401,6 +413,16 @@ impl GpuMap<u8, Complex> {
     /// `RtlSdrDecode::new(src)` (src/rtlsdr_decode.rs:9-47)
     pub fn rtlsdr_decode(src: ReadStream<u8>) -> Result<(Self, ReadStream<Complex>)> {
         Self::wrap(unsafe { rr_rtlsdr_decode_create() }, "GpuRtlSdrDecode", false, src)
+    }
+}
+impl GpuMap<u8, u8> {
+    /// `NrziEncode::new(src)` (src/nrzi.rs:52-69); a sync block: tags pass through position for position
+    pub fn nrzi_encode(src: ReadStream<u8>) -> Result<(Self, ReadStream<u8>)> {
+        Self::wrap(unsafe { rr_nrzi_encode_create() }, "GpuNrziEncode", true, src)
+    }
+    /// `Scrambler::g3ruh(src)` (src/descrambler.rs:95-123)
+    pub fn scrambler_g3ruh(src: ReadStream<u8>) -> Result<(Self, ReadStream<u8>)> {
+        Self::wrap(unsafe { rr_scrambler_g3ruh_create() }, "GpuScrambler", true, src)
     }
 }
 impl GpuMap<Float, Float> {

@@ -664,6 +664,97 @@ class BitDecoder(_TagBlock):
                          np.float32, np.uint8)
 
 
+def NrziEncode() -> Block:
+    """NrziEncode::new(src) (src/nrzi.rs:52-69): u8 in, out[n] = out[n-1] ^ (in[n] == 0), out[-1] = 0."""
+    return Block(lib().rr_nrzi_encode_create(), np.uint8, np.uint8)
+
+
+class Scrambler(Block):
+    """Scrambler (src/descrambler.rs:95-123): u8 in, u8 out; only the G3RUH form exists in the reference."""
+
+    def __init__(self):
+        super().__init__(lib().rr_scrambler_g3ruh_create(), np.uint8, np.uint8)
+
+    @classmethod
+    def g3ruh(cls):
+        """Scrambler::g3ruh (src/descrambler.rs:106-118): s[n] = in[n] ^ s[n-12] ^ s[n-17], out[n] = s[n-17]"""
+        return cls()
+
+
+FRAME_FCS, FRAME_G3RUH, FRAME_NRZI, FRAME_SYMBOLS = 1, 2, 4, 8      # RR_FRAME_*
+# rr_frame_record
+FRAME_RECORD = np.dtype([("start", np.uint64), ("len", np.uint64), ("stuffed", np.uint32), ("fcs", np.uint16)], align=True)
+
+
+class HdlcFramer(Block):
+    """FcsAdder -> HdlcFramer -> PduToStream<u8> -> [Scrambler::g3ruh] -> [NrziEncode] -> [Map(bit ? hi : lo)] behind one handle
+    (rr_hdlc_framer_create; src/hdlc_framer.rs, examples/g3ruh.rs:250-267; not a stream block: work() raises): a batch of
+    packets in, their line bits (u8) or levels (f32, with FRAME_SYMBOLS) out, back to back.  See include/rustradio_amd.h."""
+
+    def __init__(self, flags: int = 0, lo: float = -1.0, hi: float = 1.0):
+        super().__init__(lib().rr_hdlc_framer_create(int(flags), float(lo), float(hi)), np.uint8,
+                         np.float32 if int(flags) & FRAME_SYMBOLS else np.uint8)
+        self.flags = int(flags)
+
+    @property
+    def tile_bits(self) -> int:
+        """rr_hdlc_framer_dims"""
+        t = C.c_size_t(0)
+        if lib().rr_hdlc_framer_dims(self._h, C.byref(t)) != 0:
+            raise RuntimeError(last_error())
+        return t.value
+
+    @staticmethod
+    def _desc(starts, lens):
+        st = np.ascontiguousarray(starts, np.uintp)
+        ln = np.ascontiguousarray(lens, np.uintp)
+        if st.ndim != 1 or st.shape != ln.shape:
+            raise ValueError("starts and lens must be two sequences of one length")
+        return st, ln
+
+    def bound(self, lens) -> int:
+        """rr_hdlc_framer_bound: the elements a push of packets of these lengths produces at most"""
+        ln = np.ascontiguousarray(lens, np.uintp)
+        return lib().rr_hdlc_framer_bound(self._h, _ptr(ln) if len(ln) else None, len(ln))
+
+    def push_dev(self, d_bytes: int, n_bytes: int, starts, lens, d_out: int, out_cap: int, stream: int = 0) -> None:
+        """rr_hdlc_framer_push_dev: packet p is d_bytes[starts[p] : starts[p] + lens[p]] (raw device pointers); asynchronous on
+        `stream`; records() waits"""
+        st, ln = self._desc(starts, lens)
+        if lib().rr_hdlc_framer_push_dev(self._h, C.c_void_p(d_bytes), n_bytes, _ptr(st) if len(st) else None,
+                                         _ptr(ln) if len(ln) else None, len(st), C.c_void_p(d_out), out_cap, C.c_void_p(stream)) != 0:
+            raise RuntimeError(last_error())
+
+    def push_buffer(self, data, starts, lens) -> np.ndarray:
+        """rr_hdlc_framer_push on a host byte buffer -> the elements the push produced"""
+        x = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else data, np.uint8).ravel()
+        st, ln = self._desc(starts, lens)
+        cap = self.bound(ln)
+        out = np.zeros(max(cap, 1), self.out_dtype)
+        produced = C.c_size_t(0)
+        if lib().rr_hdlc_framer_push(self._h, _ptr(x) if len(x) else None, len(x), _ptr(st) if len(st) else None,
+                                     _ptr(ln) if len(ln) else None, len(st), _ptr(out), cap, C.byref(produced)) != 0:
+            raise RuntimeError(last_error())
+        return out[:produced.value]
+
+    def push(self, packets) -> np.ndarray:
+        """what the chain does to each popped Vec<u8>, for a list of packets in one call -> their frames back to back"""
+        pk = [bytes(p) for p in packets]
+        lens = np.array([len(p) for p in pk], np.uintp)
+        starts = (np.cumsum(lens) - lens).astype(np.uintp)
+        return self.push_buffer(b"".join(pk), starts, lens)
+
+    def records(self):
+        """-> (FRAME_RECORD per packet of the most recent push, the elements it produced) (rr_hdlc_framer_records; waits)"""
+        total, produced = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_hdlc_framer_records(self._h, None, 0, C.byref(total), C.byref(produced)) != 0:
+            raise RuntimeError(last_error())
+        rec = np.zeros(max(total.value, 1), FRAME_RECORD)
+        if total.value and lib().rr_hdlc_framer_records(self._h, _ptr(rec), total.value, C.byref(total), C.byref(produced)) != 0:
+            raise RuntimeError(last_error())
+        return rec[:total.value], produced.value
+
+
 WPCR_MAX_LEN = 512_000      # samples of one burst: the reference's stream capacity in f32
 # rr_wpcr_result
 WPCR_RESULT = np.dtype([("ok", np.int32), ("bin", np.uint32), ("sps", np.float32), ("phase0", np.float32), ("phase", np.float32),

@@ -10,6 +10,8 @@
 
 #include "blocks.hpp"
 #include "dstream.hpp"
+#include "frame_core.hpp"
+#include "frame_host.hpp"
 #include "pdu_host.hpp"
 #include "taps.hpp"
 
@@ -412,6 +414,67 @@ int rr_wpcr_pack_dev(rr_block* wpcr, const void* d_syms, void* d_out, size_t out
         w->pack_dev(static_cast<const float*>(d_syms), static_cast<float*>(d_out), out_cap, produced, pdu_start, pdu_len, cap, npdus, s);
         w->last_stream = s;
     });
+}
+rr_block* rr_nrzi_encode_create(void) {
+    return make_block([&] { return new rr::LineCoder("NrziEncode", rr::LINE_NRZI); }, RR_TAGS_FORWARD, 1);
+}
+rr_block* rr_scrambler_g3ruh_create(void) {
+    return make_block([&] { return new rr::LineCoder("Scrambler", rr::LINE_SCR); }, RR_TAGS_FORWARD, 1);
+}
+rr_block* rr_hdlc_framer_create(int flags, float lo, float hi) {
+    if (const char* e = rr::frame_check_flags(flags)) { rr::set_build_opts(nullptr); rr::set_last_error(e); return nullptr; }   // before any device is touched
+    return make_block([&] { return new rr::HdlcFramer(flags, lo, hi); });
+}
+static rr::HdlcFramer* as_framer(const rr_block* b, const char* what) {
+    auto* f = b ? dynamic_cast<rr::HdlcFramer*>(b->b.get()) : nullptr;
+    if (!f) rr::set_last_error(std::string(what) + ": not an hdlc framer handle");
+    return f;
+}
+size_t rr_hdlc_framer_bound(const rr_block* b, const size_t* lens, size_t npackets) {
+    auto* f = as_framer(b, "rr_hdlc_framer_bound");
+    if (!f || (npackets && !lens)) return 0;
+    return rr::frame_bound(f->flags, lens, npackets);
+}
+int rr_hdlc_framer_push_dev(rr_block* b, const void* d_bytes, size_t n_bytes, size_t* starts, size_t* lens, size_t npackets,
+                            void* d_out, size_t out_cap, void* hip_stream) {
+    auto* f = as_framer(b, "rr_hdlc_framer_push_dev");
+    if (!f) return RR_ERR;
+    size_t bound = 0;                                  // every refusal before any device is touched
+    if (const char* e = rr::frame_check_push(f->flags, n_bytes, starts, lens, npackets, out_cap, &bound)) { rr::set_last_error(e); return RR_ERR; }
+    if (npackets && (!d_out || (n_bytes && !d_bytes))) { rr::set_last_error("rr_hdlc_framer_push_dev: null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(f->device));
+        hipStream_t s = static_cast<hipStream_t>(hip_stream);      // used as given (see rr_block_work_dev)
+        f->last_stream = s;
+        f->push_dev(static_cast<const unsigned char*>(d_bytes), n_bytes, starts, lens, npackets, d_out, out_cap, s);
+    });
+}
+int rr_hdlc_framer_push(rr_block* b, const unsigned char* bytes, size_t n_bytes, size_t* starts, size_t* lens, size_t npackets,
+                        void* out, size_t out_cap, size_t* produced) {
+    auto* f = as_framer(b, "rr_hdlc_framer_push");
+    if (!f) return RR_ERR;
+    if (!produced) { rr::set_last_error("rr_hdlc_framer_push: null argument"); return RR_ERR; }
+    size_t bound = 0;
+    if (const char* e = rr::frame_check_push(f->flags, n_bytes, starts, lens, npackets, out_cap, &bound)) { rr::set_last_error(e); return RR_ERR; }
+    if (npackets && (!out || (n_bytes && !bytes))) { rr::set_last_error("rr_hdlc_framer_push: null argument"); return RR_ERR; }
+    return guarded([&] { f->push_host(bytes, n_bytes, starts, lens, npackets, out, out_cap, produced); });
+}
+int rr_hdlc_framer_records(rr_block* b, rr_frame_record* rec, size_t cap, size_t* total, size_t* produced) {
+    auto* f = as_framer(b, "rr_hdlc_framer_records");
+    if (!f) return RR_ERR;
+    if (!total || !produced || (cap && !rec)) { rr::set_last_error("rr_hdlc_framer_records: null argument"); return RR_ERR; }
+    return guarded([&] {
+        RR_HIP(hipSetDevice(f->device));
+        rr::frame_copy_out(f->fetch_records(), rec, cap, total);
+        *produced = f->produced;
+    });
+}
+int rr_hdlc_framer_dims(const rr_block* b, size_t* tile_bits) {
+    auto* f = as_framer(b, "rr_hdlc_framer_dims");
+    if (!f || !tile_bits) { if (f) rr::set_last_error("rr_hdlc_framer_dims: null argument"); return RR_ERR; }
+    static_assert(rr::FRAME_T == rr::LINE_T, "one tile length for the stuffing scan and the line coder");
+    *tile_bits = rr::FRAME_T;
+    return 0;
 }
 rr_block* rr_rtlsdr_decode_create(void) {
     return make_block([&] { return new rr::RtlSdrDecode(); });

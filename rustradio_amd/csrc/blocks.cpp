@@ -16,6 +16,8 @@
 #include <cstring>
 #include <unistd.h>
 
+#include "frame_core.hpp"
+#include "frame_host.hpp"
 #include "pdu_host.hpp"
 #include "stage.hpp"
 #include "taps.hpp"
@@ -2648,6 +2650,135 @@ void Wpcr::pack_dev(const float* d_syms, float* d_out, size_t out_cap, size_t* p
     pack_desc.reserve(hpack.size());
     hstage().h2d(pack_desc.p, hpack.data(), hpack.size() * sizeof(long), s);
     launch_pdu_pack(d_syms, pack_desc.p, (long)(hpack.size() / 3), (long)total, d_out, s);
+}
+
+// ---- Scrambler::g3ruh, NrziEncode and the HDLC framer (descrambler.rs:41-47, nrzi.rs:52-69, hdlc_framer.rs; kernels_frame.hip) ----------
+void LineState::init(int m, hipStream_t s) {
+    mode = m;
+    if (!mode) return;
+    std::vector<unsigned> h(LINE_NP * LINE_NS);
+    line_build_powers(mode, h.data());
+    pw.upload(h.data(), h.size(), s);
+    const unsigned zero = 0;                         // Lfsr::g3ruh's seed 0 (descrambler.rs:31), NrziEncode's out 0 (nrzi.rs:59-60)
+    st[0].upload(&zero, 1, s);
+    st[1].upload(&zero, 1, s);
+}
+void LineState::run(const unsigned char* in, void* out, bool out_f32, float lo, float hi, size_t max_n, const unsigned long long* n_dev,
+                    hipStream_t s) {
+    if (!max_n) return;
+    const size_t ntiles = (max_n + LINE_T - 1) / LINE_T;
+    LineArgs a{};
+    a.in = in; a.out = out; a.out_f32 = out_f32 ? 1 : 0; a.lo = lo; a.hi = hi;
+    a.max_n = (long)max_n; a.n_dev = n_dev; a.mode = mode;
+    if (mode) {
+        z.reserve(ntiles);
+        carry.reserve(ntiles);
+        a.pw = pw.p; a.st_in = st[cur].p; a.st_out = st[cur ^ 1].p; a.z = z.p; a.carry = carry.p;
+    }
+    launch_line(a, s);
+    if (mode) cur ^= 1;
+}
+LineCoder::LineCoder(const char* nm, int mode) : Block(nm, 1, 1) {
+    line.init(mode, stream);
+    zero_copy_in = false;                            // (a tile is read twice: a page-locked host window is copied down first)
+    RR_HIP(hipStreamSynchronize(stream));
+}
+int LineCoder::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed, size_t* produced, size_t* need,
+                        hipStream_t s) {
+    size_t n = 0;
+    const int rc = sync_counts(in_len, out_cap, &n, need);
+    if (n) {
+        prof_begin(s);
+        line.run(static_cast<const unsigned char*>(in), out, false, 0.0f, 0.0f, n, nullptr, s);
+        prof_end(s);
+    }
+    *consumed = *produced = n;
+    return rc;
+}
+
+static_assert(sizeof(StuffSum) == 4 * sizeof(unsigned), "FrameArgs::sums: four words per tile");
+HdlcFramer::HdlcFramer(int fl, float l, float h)
+    : Block("FcsAdder>HdlcFramer>PduToStream", 1, fl & RR_FRAME_SYMBOLS ? 4 : 1), flags(fl), lo(l), hi(h) {
+    if (const char* e = frame_check_flags(fl)) throw Error(e);
+    line.init((fl & RR_FRAME_G3RUH ? LINE_SCR : 0) | (fl & RR_FRAME_NRZI ? LINE_NRZI : 0), stream);
+    total.reserve(1);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+int HdlcFramer::work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) {
+    throw Error("HdlcFramer takes whole packets: rr_hdlc_framer_push / rr_hdlc_framer_push_dev");
+}
+void HdlcFramer::push_dev(const unsigned char* d_bytes, size_t n_bytes, const size_t* st, const size_t* ln, size_t npackets, void* d_out,
+                          size_t out_cap, hipStream_t s) {
+    size_t bnd = 0;
+    if (const char* e = frame_check_push(flags, n_bytes, st, ln, npackets, out_cap, &bnd)) throw Error(e);
+    if (npackets && !d_out) throw Error("null output");
+    if (npackets && n_bytes && !d_bytes) throw Error("null input");
+    lens.assign(ln, ln + npackets);
+    bound = bnd;
+    records.clear();
+    produced = 0;
+    fetched = true;                                  // a push of no packets has no records and leaves every state alone
+    if (!npackets) return;
+    FramePlan pl;
+    frame_plan(flags, st, ln, npackets, FRAME_CH, pl);
+    const bool fcs = (flags & RR_FRAME_FCS) != 0, coded = line.mode != 0 || (flags & RR_FRAME_SYMBOLS) != 0;
+    FrameArgs a{};
+    a.P = (long)npackets;
+    a.nbytes = (long)pl.nbytes;
+    a.ntiles = (long)std::max<size_t>(1, (8 * pl.nbytes + FRAME_T - 1) / FRAME_T);
+    a.nchunks = (long)pl.nchunks;
+    a.fcs = fcs ? 1 : 0;
+    desc.reserve(pl.words.size());
+    if (fcs) { part.reserve(std::max<size_t>(pl.nchunks, 1)); crc.reserve(npackets); }
+    lb.reserve(std::max<size_t>(pl.nbytes, 1));
+    sums.reserve(4 * (size_t)a.ntiles);
+    tin.reserve(2 * (size_t)a.ntiles);
+    cb.reserve(npackets + 1);
+    if (coded) pre.reserve(bnd);
+    hstage().h2d(desc.p, pl.words.data(), pl.words.size() * sizeof(unsigned long long), s);      // (pl is free on return)
+    a.bytes = d_bytes;
+    a.starts = desc.p; a.pb = desc.p + npackets; a.cpre = desc.p + 2 * npackets + 1;
+    a.part = part.p; a.crc = crc.p; a.lb = lb.p; a.sums = sums.p; a.tin = tin.p; a.cb = cb.p; a.total = total.p;
+    a.pre = coded ? pre.p : static_cast<unsigned char*>(d_out);
+    a.cap = (long)bnd;
+    prof_begin(s);
+    launch_frame(a, s);
+    if (coded) line.run(pre.p, d_out, (flags & RR_FRAME_SYMBOLS) != 0, lo, hi, bnd, total.p, s);
+    prof_end(s);
+    fetched = false;
+}
+void HdlcFramer::push_host(const unsigned char* bytes, size_t n_bytes, const size_t* st, const size_t* ln, size_t npackets, void* out,
+                           size_t out_cap, size_t* prod) {
+    RR_HIP(hipSetDevice(device));
+    last_stream = stream;
+    size_t bnd = 0;
+    if (const char* e = frame_check_push(flags, n_bytes, st, ln, npackets, out_cap, &bnd)) throw Error(e);
+    *prod = 0;
+    if (!npackets) { push_dev(nullptr, n_bytes, st, ln, 0, nullptr, out_cap, stream); return; }
+    h_in.reserve(std::max<size_t>(n_bytes, 1));
+    h_out.reserve(std::max<size_t>(bnd * out_es, 1));
+    if (n_bytes) hstage().h2d(h_in.p, bytes, n_bytes, stream);
+    push_dev(h_in.p, n_bytes, st, ln, npackets, h_out.p, bnd, stream);
+    fetch_records();                                 // waits; `produced` is checked against the bound in there
+    if (produced) hstage().d2h(out, h_out.p, produced * out_es, stream);
+    RR_HIP(hipStreamSynchronize(stream));
+    hstage().quiesced();
+    *prod = produced;
+}
+const std::vector<rr_frame_record>& HdlcFramer::fetch_records() {
+    sync();
+    if (hstage_) hstage_->quiesced();
+    if (!fetched) {
+        const size_t P = lens.size();
+        std::vector<unsigned> hcb(P + 1), hcrc(flags & RR_FRAME_FCS ? P : 0);
+        unsigned long long tot = 0;
+        stage_download_sync(hcb.data(), cb.p, hcb.size() * sizeof(unsigned), stream);
+        if (!hcrc.empty()) stage_download_sync(hcrc.data(), crc.p, hcrc.size() * sizeof(unsigned), stream);
+        stage_download_sync(&tot, total.p, sizeof tot, stream);
+        if (const char* e = frame_records(flags, lens, hcb, hcrc, tot, bound, records, &produced)) throw Error(e);
+        fetched = true;
+    }
+    return records;
 }
 
 // ---- RtlSdrDecode (rtlsdr_decode.rs:9-47) ----------------------------------------------------------------------

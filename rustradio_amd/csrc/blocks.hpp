@@ -689,6 +689,51 @@ struct StreamToPdu : Block {
     void fetch_ranks(size_t idx, float* low, float* high);  // the two elements Midpointer's offset of PDU idx was made of
 };
 
+// Scrambler::g3ruh (descrambler.rs:41-47, 95-123) and NrziEncode (nrzi.rs:52-69) as one affine system over GF(2)
+// (kernels_frame.hip, frame_core.hpp): what LineCoder (the two sync blocks) and HdlcFramer share.  The state word stays on the
+// device between calls; mode 0 has none.
+struct LineState {
+    int mode = 0;                             // LINE_SCR | LINE_NRZI
+    DevBuf<unsigned> pw;                      // the LINE_NP powers of the tile matrix
+    DevBuf<unsigned> st[2];                   // [cur]: what the stream so far left behind
+    int cur = 0;
+    DevBuf<unsigned> z, carry;                // one word per tile of the largest call so far
+    void init(int mode, hipStream_t s);
+    // n = *n_dev when given (at most max_n), else max_n
+    void run(const unsigned char* in, void* out, bool out_f32, float lo, float hi, size_t max_n, const unsigned long long* n_dev,
+             hipStream_t s);
+};
+struct LineCoder : Block {
+    LineState line;
+    LineCoder(const char* nm, int mode);
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+};
+
+// FcsAdder -> HdlcFramer -> PduToStream<u8> -> [Scrambler::g3ruh] -> [NrziEncode] -> [Map] in PDU form over a batch of packets of
+// one byte buffer (kernels_frame.hip): no stream protocol (work_dev is an error).  The host keeps the geometry of the latest
+// push; what it reads back (frame_host.hpp) is sized from that geometry.
+struct HdlcFramer : Block {
+    int flags;
+    float lo, hi;
+    LineState line;
+    DevBuf<unsigned long long> desc, total;   // this push's starts / pb / cpre; the framed bits it made
+    DevBuf<unsigned> part, crc, sums, tin, cb;
+    DevBuf<unsigned char> lb, pre;            // the packets' bytes with their FCS; the framed bits in front of the line coder
+    DevBuf<unsigned char> h_in, h_out;        // push_host(): the host buffers' device copies
+    std::vector<size_t> lens;                 // the latest push's geometry
+    size_t bound = 0;
+    bool fetched = true;                      // `records` / `produced` hold the latest push's
+    std::vector<rr_frame_record> records;
+    size_t produced = 0;
+    HdlcFramer(int flags, float lo, float hi);
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
+    void push_dev(const unsigned char* d_bytes, size_t n_bytes, const size_t* starts, const size_t* lens, size_t npackets, void* d_out,
+                  size_t out_cap, hipStream_t s);
+    void push_host(const unsigned char* bytes, size_t n_bytes, const size_t* starts, const size_t* lens, size_t npackets, void* out,
+                   size_t out_cap, size_t* produced);
+    const std::vector<rr_frame_record>& fetch_records();      // waits for the latest push
+};
+
 // RtlSdrDecode (rtlsdr_decode.rs:9-47): stateless u8 pair -> Complex conversion.
 struct RtlSdrDecode : Block {
     RtlSdrDecode();

@@ -397,6 +397,55 @@ void launch_pdu(const PduArgs& a, hipStream_t s);
 // dst without gaps, total = their lengths' sum.  One launch; total == 0 launches nothing.
 void launch_pdu_pack(const float* syms, const long* desc, long nb, long total, float* out, hipStream_t s);
 
+// ---- kernels_frame.hip: FcsAdder -> HdlcFramer -> PduToStream<u8> over a batch of packets, then Scrambler::g3ruh -> NrziEncode ->
+//      Map over the stream they make (frame_core.hpp holds the arithmetic) -----------------------------------------------------------
+// Packet p is bytes[starts[p] ..) followed by its two FCS bytes when fcs != 0; pb[p] = the bytes of the packets before it with
+// their FCS bytes (pb[P] = nbytes), cpre[p] = the CRC chunks (FRAME_CH payload bytes each) before it.  The payload bits of all
+// packets, back to back, are cut into tiles of FRAME_T bits: ntiles = max(1, ceil(8 nbytes / FRAME_T)).  pre gets the framed
+// bits, one u8 each; cb[b], b <= P: the stuffed bits before packet b's first payload bit; *total: the framed bits of the push.
+// Scratch: part (cpre[P] words), crc (P), lb (nbytes), sums (ntiles StuffSums = 4 words each), tin (2 ntiles).  P == 0 launches
+// nothing.  The launches depend on P, nbytes and fcs alone.
+constexpr int FRAME_T = 4096;                 // payload bits of one tile
+constexpr int FRAME_CH = 128;                 // payload bytes of one CRC chunk
+struct FrameArgs {
+    const unsigned char* bytes;
+    const unsigned long long* starts;
+    const unsigned long long* pb;
+    const unsigned long long* cpre;
+    long P, nbytes, ntiles, nchunks;          // nchunks = cpre[P]
+    int fcs;
+    unsigned* part;
+    unsigned* crc;
+    unsigned char* lb;
+    unsigned* sums;
+    unsigned* tin;
+    unsigned* cb;
+    unsigned long long* total;
+    unsigned char* pre;
+    long cap;                                 // elements of pre: the bound of the push
+};
+void launch_frame(const FrameArgs& a, hipStream_t s);
+// The line coder over n bits, u8 in (the lowest bit of each): out = u8 bits, or with out_f32 bit ? hi : lo.  n = *n_dev when
+// n_dev is given (then at most max_n, which sizes the grid and the scratch), else max_n.  mode: LINE_SCR | LINE_NRZI
+// (frame_core.hpp); pw: the LINE_NP powers of the tile matrix for that mode.  st_in / st_out: distinct device words (the
+// block's ping-pong), the state in front of the window and behind it.  z, carry: ceil(max_n / LINE_T) words each.  Three
+// launches, or one when mode == 0 (then no state is read or written); max_n == 0 launches nothing.
+struct LineArgs {
+    const unsigned char* in;
+    void* out;
+    int out_f32;
+    float lo, hi;
+    long max_n;
+    const unsigned long long* n_dev;
+    int mode;
+    const unsigned* pw;
+    const unsigned* st_in;
+    unsigned* st_out;
+    unsigned* z;
+    unsigned* carry;
+};
+void launch_line(const LineArgs& a, hipStream_t s);
+
 // ---- head fix of the fused FirFilter -> FftFilter blocks (stream start only, a few hundred samples) ----------------
 // z[m] = sum_k t1[k] V[voff + m + L1 - 1 - k], m < n: the front FirFilter's first outputs (fir.rs:166-177) from the virtual stream
 void launch_head_z(VSrc<cf> V, long voff, const cf* t1, int L1, cf* z, long n, hipStream_t s);

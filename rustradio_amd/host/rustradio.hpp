@@ -37,6 +37,7 @@
 #include <thread>
 #include <tuple>
 #include <utility>
+#include <type_traits>
 #include <variant>
 #include <vector>
 
@@ -795,6 +796,51 @@ public:
     std::optional<Packet> process_one(const std::vector<Float>& samples) { return process({samples})[0]; }   // :130-197
 };
 
+// ---- FcsAdder -> HdlcFramer -> PduToStream<u8> -> [Scrambler::g3ruh] -> [NrziEncode] -> [Map] (src/hdlc_framer.rs:28-86,
+// src/pdu_to_stream.rs:57-101, examples/g3ruh.rs:250-267): the message (PDU) form ---------------------------------------------------
+// (rr_hdlc_framer_create / rr_hdlc_framer_push / rr_hdlc_framer_records).  push() takes a batch of packets in ONE call and
+// returns what the stream behind PduToStream (and the line stages the flags name) receives for them: the frames back to back,
+// with a `start` tag carrying U64(len) at each frame's first element (pdu_to_stream.rs:84-92).  The scrambler's register and
+// the NRZI level stay in the block from push to push.  T = uint8_t without RR_FRAME_SYMBOLS, Float with it.
+template <class T> class HdlcFramer {
+    static_assert(std::is_same<T, uint8_t>::value || std::is_same<T, Float>::value, "bits or levels");
+    detail::Handle h_;
+public:
+    struct Frames {
+        std::vector<T> stream;
+        std::vector<rr_frame_record> records;
+        std::vector<Tag> tags;
+    };
+    explicit HdlcFramer(int flags, Float lo = -1.0f, Float hi = 1.0f)
+        : h_(rr_hdlc_framer_create(std::is_same<T, Float>::value ? flags | RR_FRAME_SYMBOLS : flags & ~RR_FRAME_SYMBOLS, lo, hi)) {}
+    Frames push(const std::vector<std::vector<uint8_t>>& packets) {
+        std::vector<size_t> starts(packets.size() + 1), lens(packets.size() + 1);
+        size_t total = 0;
+        for (size_t p = 0; p < packets.size(); p++) { starts[p] = total; lens[p] = packets[p].size(); total += lens[p]; }
+        std::vector<uint8_t> x(total + 1);
+        for (size_t p = 0; p < packets.size(); p++) std::copy(packets[p].begin(), packets[p].end(), x.begin() + (long)starts[p]);
+        const size_t cap = rr_hdlc_framer_bound(h_.h, lens.data(), packets.size());
+        Frames f;
+        f.stream.resize(cap + 1);
+        size_t produced = 0;
+        if (rr_hdlc_framer_push(h_.h, x.data(), total, starts.data(), lens.data(), packets.size(), f.stream.data(), cap, &produced) != 0)
+            throw Error(rr_last_error());
+        f.stream.resize(produced);
+        f.records.resize(packets.size() + 1);
+        size_t n = 0, again = 0;
+        if (rr_hdlc_framer_records(h_.h, f.records.data(), packets.size(), &n, &again) != 0) throw Error(rr_last_error());
+        if (n != packets.size() || again != produced) throw Error("HdlcFramer: record count");
+        f.records.resize(n);
+        for (const rr_frame_record& r : f.records) f.tags.emplace_back(r.start, "start", (uint64_t)r.len);
+        return f;
+    }
+    size_t tile_bits() const {
+        size_t t = 0;
+        if (rr_hdlc_framer_dims(h_.h, &t) != 0) throw Error(rr_last_error());
+        return t;
+    }
+};
+
 // ---- BurstTagger -> StreamToPdu -> [Midpointer] (src/burst_tagger.rs:68-85, src/stream_to_pdu.rs:198-275, src/wpcr.rs:44-82) -----------
 // (rr_stream_to_pdu_create / rr_stream_to_pdu_push / rr_pdu_records / rr_pdu_fetch).  push() takes one window of the data stream
 // and of the trigger stream and returns what StreamToPdu's output would receive for it: the PDUs this window completes, a burst
@@ -947,6 +993,23 @@ public:
     static std::pair<std::unique_ptr<NrziDecode>, ReadStream<uint8_t>> new_(ReadStream<uint8_t> src) {
         auto [w, r] = new_stream<uint8_t>();
         return {std::make_unique<NrziDecode>(rr_nrzi_decode_create(), std::move(src), std::move(w)), std::move(r)};
+    }
+};
+// NrziEncode (src/nrzi.rs:52-69) and Scrambler (src/descrambler.rs:95-123): the transmit side's sync blocks, u8 in, u8 out
+class NrziEncode : public SyncBlock<uint8_t, uint8_t> {
+public:
+    using SyncBlock<uint8_t, uint8_t>::SyncBlock;
+    static std::pair<std::unique_ptr<NrziEncode>, ReadStream<uint8_t>> new_(ReadStream<uint8_t> src) {
+        auto [w, r] = new_stream<uint8_t>();
+        return {std::make_unique<NrziEncode>(rr_nrzi_encode_create(), std::move(src), std::move(w)), std::move(r)};
+    }
+};
+class Scrambler : public SyncBlock<uint8_t, uint8_t> {
+public:
+    using SyncBlock<uint8_t, uint8_t>::SyncBlock;
+    static std::pair<std::unique_ptr<Scrambler>, ReadStream<uint8_t>> g3ruh(ReadStream<uint8_t> src) {         // :106-118
+        auto [w, r] = new_stream<uint8_t>();
+        return {std::make_unique<Scrambler>(rr_scrambler_g3ruh_create(), std::move(src), std::move(w)), std::move(r)};
     }
 };
 class Descrambler : public SyncBlock<uint8_t, uint8_t> {
