@@ -105,6 +105,17 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _fetch(fn, handle, *dtypes, tail=()):
+    """ask for the total, allocate, ask again: fn(handle, one array per dtype, capacity, &total, *tail) -> the arrays, cut to total"""
+    total = C.c_size_t(0)
+    if fn(handle, *[None] * len(dtypes), 0, C.byref(total), *tail) != 0:
+        raise RuntimeError(last_error())
+    arrs = [np.zeros(max(total.value, 1), d) for d in dtypes]
+    if total.value and fn(handle, *map(_ptr, arrs), total.value, C.byref(total), *tail) != 0:
+        raise RuntimeError(last_error())
+    return [a[:total.value] for a in arrs]
+
+
 def device_count() -> int:
     return lib().rr_device_count()
 
@@ -583,14 +594,8 @@ class BurstDetector(Block):
 
     def edges(self):
         """-> (pos: uint64[], val: bool[]) of the most recent work call, ascending, window-relative (rr_burst_edges)"""
-        total = C.c_size_t(0)
-        if lib().rr_burst_edges(self._h, None, None, 0, C.byref(total)) != 0:
-            raise RuntimeError(last_error())
-        pos = np.zeros(max(total.value, 1), np.uint64)
-        val = np.zeros(max(total.value, 1), np.uint8)
-        if total.value and lib().rr_burst_edges(self._h, _ptr(pos), _ptr(val), total.value, C.byref(total)) != 0:
-            raise RuntimeError(last_error())
-        return pos[:total.value], val[:total.value].astype(bool)
+        pos, val = _fetch(lib().rr_burst_edges, self._h, np.uint64, np.uint8)
+        return pos, val.astype(bool)
 
 
 BITS_INVERT, BITS_NRZI, BITS_DESCRAMBLE = 1, 2, 4      # RR_BITS_*
@@ -610,14 +615,7 @@ class _TagBlock(Block):
 
     def tags(self):
         """-> (pos: uint64[], diffs: uint8[]) of the most recent work call, ascending, window-relative (rr_bit_tags)"""
-        total = C.c_size_t(0)
-        if lib().rr_bit_tags(self._h, None, None, 0, C.byref(total)) != 0:
-            raise RuntimeError(last_error())
-        pos = np.zeros(max(total.value, 1), np.uint64)
-        diffs = np.zeros(max(total.value, 1), np.uint8)
-        if total.value and lib().rr_bit_tags(self._h, _ptr(pos), _ptr(diffs), total.value, C.byref(total)) != 0:
-            raise RuntimeError(last_error())
-        return pos[:total.value], diffs[:total.value]
+        return tuple(_fetch(lib().rr_bit_tags, self._h, np.uint64, np.uint8))
 
 
 def BinarySlicer() -> Block:
@@ -746,13 +744,9 @@ class HdlcFramer(Block):
 
     def records(self):
         """-> (FRAME_RECORD per packet of the most recent push, the elements it produced) (rr_hdlc_framer_records; waits)"""
-        total, produced = C.c_size_t(0), C.c_size_t(0)
-        if lib().rr_hdlc_framer_records(self._h, None, 0, C.byref(total), C.byref(produced)) != 0:
-            raise RuntimeError(last_error())
-        rec = np.zeros(max(total.value, 1), FRAME_RECORD)
-        if total.value and lib().rr_hdlc_framer_records(self._h, _ptr(rec), total.value, C.byref(total), C.byref(produced)) != 0:
-            raise RuntimeError(last_error())
-        return rec[:total.value], produced.value
+        produced = C.c_size_t(0)
+        rec, = _fetch(lib().rr_hdlc_framer_records, self._h, FRAME_RECORD, tail=(C.byref(produced),))
+        return rec, produced.value
 
 
 WPCR_MAX_LEN = 512_000      # samples of one burst: the reference's stream capacity in f32
@@ -803,13 +797,7 @@ class Wpcr(Block):
 
     def results(self) -> np.ndarray:
         """one WPCR_RESULT record per burst of the most recent process call (rr_wpcr_results; waits for it)"""
-        total = C.c_size_t(0)
-        if lib().rr_wpcr_results(self._h, None, 0, C.byref(total)) != 0:
-            raise RuntimeError(last_error())
-        res = np.zeros(max(total.value, 1), WPCR_RESULT)
-        if total.value and lib().rr_wpcr_results(self._h, _ptr(res), total.value, C.byref(total)) != 0:
-            raise RuntimeError(last_error())
-        return res[:total.value]
+        return _fetch(lib().rr_wpcr_results, self._h, WPCR_RESULT)[0]
 
     def tags(self, r) -> dict:
         """the tags Wpcr pushes with a packet (wpcr.rs:187-194) from one result record"""
@@ -893,24 +881,12 @@ class StreamToPdu(Block):
 
     def records(self) -> np.ndarray:
         """one PDU_RECORD per PDU the most recent push completed, ascending (rr_pdu_records; waits for it)"""
-        total = C.c_size_t(0)
-        if lib().rr_pdu_records(self._h, None, 0, C.byref(total)) != 0:
-            raise RuntimeError(last_error())
-        rec = np.zeros(max(total.value, 1), PDU_RECORD)
-        if total.value and lib().rr_pdu_records(self._h, _ptr(rec), total.value, C.byref(total)) != 0:
-            raise RuntimeError(last_error())
-        return rec[:total.value]
+        return _fetch(lib().rr_pdu_records, self._h, PDU_RECORD)[0]
 
     def edges(self):
         """-> (pos: uint64[], val: bool[]) of the most recent push, ascending, window-relative (rr_pdu_edges)"""
-        total = C.c_size_t(0)
-        if lib().rr_pdu_edges(self._h, None, None, 0, C.byref(total)) != 0:
-            raise RuntimeError(last_error())
-        pos = np.zeros(max(total.value, 1), np.uint64)
-        val = np.zeros(max(total.value, 1), np.uint8)
-        if total.value and lib().rr_pdu_edges(self._h, _ptr(pos), _ptr(val), total.value, C.byref(total)) != 0:
-            raise RuntimeError(last_error())
-        return pos[:total.value], val[:total.value].astype(bool)
+        pos, val = _fetch(lib().rr_pdu_edges, self._h, np.uint64, np.uint8)
+        return pos, val.astype(bool)
 
     def arena_dev(self):
         """-> (raw device pointer or None, n_total) of the most recent push's arena (rr_pdu_arena_dev); valid until the next push"""

@@ -65,6 +65,31 @@ template <class F> static int guarded(F&& f) {
     try { f(); return 0; }
     catch (const std::exception& e) { rr::set_last_error(e.what()); return RR_ERR; } catch (...) { rr::set_last_error("non-standard exception"); return RR_ERR; }
 }
+// f on the handle's device; with the caller's stream, used as given (see rr_block_work_dev) and what sync() then waits for
+template <class B, class F> static int on_device(B* h, F&& f) {
+    return guarded([&] { RR_HIP(hipSetDevice(h->device)); f(); });
+}
+template <class B, class F> static int on_device(B* h, void* hip_stream, F&& f) {
+    return on_device(h, [&] { hipStream_t s = static_cast<hipStream_t>(hip_stream); h->last_stream = s; f(s); });
+}
+// the block of kind T behind a handle, or nullptr and "<what>: <not_a>" (also said when the caller's `args_ok` is false)
+template <class T> static T* as(const rr_block* b, const char* what, const char* not_a, bool args_ok = true) {
+    auto* p = b && args_ok ? dynamic_cast<T*>(b->b.get()) : nullptr;
+    if (!p) rr::set_last_error(std::string(what) + ": " + not_a);
+    return p;
+}
+static const char NOT_WPCR[] = "not a wpcr handle", NOT_PDU[] = "not a stream_to_pdu handle", NOT_FRAMER[] = "not an hdlc framer handle";
+// a fetched list of (pos << shift) | val entries into the caller's two arrays
+template <class E> static void unpack(const std::vector<E>& e, unsigned shift, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
+    *total = e.size();
+    for (size_t j = 0; j < e.size() && j < cap; j++) { pos[j] = (size_t)(e[j] >> shift); val[j] = (unsigned char)(e[j] & ((E(1) << shift) - 1)); }
+}
+// a create call that refuses before any device is touched: it ends the pending overrides like any other (OptsScope)
+static rr_block* refuse_create(const char* msg) {
+    rr::OptsScope scope;
+    rr::set_last_error(msg);
+    return nullptr;
+}
 
 extern "C" {
 
@@ -202,38 +227,24 @@ rr_block* rr_complex_to_mag2_create(void) {
     return make_block([&] { return new rr::ComplexToMag2(); }, RR_TAGS_FORWARD, 1);
 }
 // single_pole_iir_filter.rs:38-41: None unless 0 <= alpha <= 1 (NaN fails both comparisons) — said before any device is touched
-static bool iir_alpha_ok(float alpha) {
-    if (alpha >= 0.0f && alpha <= 1.0f) return true;
-    rr::set_build_opts(nullptr);
-    rr::set_last_error("alpha out of range");
-    return false;
-}
+static bool iir_alpha_ok(float alpha) { return alpha >= 0.0f && alpha <= 1.0f; }
 rr_block* rr_single_pole_iir_create(float alpha, size_t elem_size) {
-    if (!iir_alpha_ok(alpha)) return nullptr;
+    if (!iir_alpha_ok(alpha)) return refuse_create("alpha out of range");
     return make_block([&] { return new rr::SinglePoleIir(alpha, elem_size); }, RR_TAGS_FORWARD, 1);
 }
 rr_block* rr_burst_detector_create(float alpha, float threshold) {
-    if (!iir_alpha_ok(alpha)) return nullptr;
+    if (!iir_alpha_ok(alpha)) return refuse_create("alpha out of range");
     return make_block([&] { return new rr::BurstDetector(alpha, threshold); }, RR_TAGS_FORWARD, 1);
 }
 int rr_burst_edges(rr_block* b, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
-    auto* d = b ? dynamic_cast<rr::BurstDetector*>(b->b.get()) : nullptr;
-    if (!d || !total || (cap && (!pos || !val))) { rr::set_last_error("rr_burst_edges: not a burst detector handle / null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(d->device));
-        const std::vector<unsigned long long>& e = d->fetch_edges();
-        *total = e.size();
-        for (size_t j = 0; j < e.size() && j < cap; j++) { pos[j] = (size_t)(e[j] >> 1); val[j] = (unsigned char)(e[j] & 1); }
-    });
+    auto* d = as<rr::BurstDetector>(b, "rr_burst_edges", "not a burst detector handle / null argument", total && (!cap || (pos && val)));
+    if (!d) return RR_ERR;
+    return on_device(d, [&] { unpack(d->fetch_edges(), 1, pos, val, cap, total); });
 }
 // the bit-level blocks: parameter errors are said before any device is touched
 static rr_block* make_bits(const char* nm, bool f32src, int flags, unsigned long long mask, unsigned long long seed, unsigned len,
                            unsigned long long code, unsigned code_len, size_t allowed_diffs) {
-    if (const char* e = rr::bits_check(flags, seed, len, code_len)) {
-        rr::set_build_opts(nullptr);
-        rr::set_last_error(e);
-        return nullptr;
-    }
+    if (const char* e = rr::bits_check(flags, seed, len, code_len)) return refuse_create(e);
     return make_block([&] { return new rr::BitDecoder(nm, f32src, flags, mask, seed, len, code, code_len, allowed_diffs); },
                       RR_TAGS_FORWARD, 1);
 }
@@ -243,11 +254,7 @@ rr_block* rr_descrambler_create(unsigned long long mask, unsigned long long seed
     return make_bits("Descrambler", false, RR_BITS_DESCRAMBLE, mask, seed, len, 0, 0, 0);
 }
 rr_block* rr_correlate_access_code_tag_create(unsigned long long code, unsigned code_len, size_t allowed_diffs) {
-    if (code_len == 0) {                             // correlate_access_code.rs:79 (assert)
-        rr::set_build_opts(nullptr);
-        rr::set_last_error("access code must be nonempty");
-        return nullptr;
-    }
+    if (code_len == 0) return refuse_create("access code must be nonempty");     // correlate_access_code.rs:79 (assert)
     return make_bits("CorrelateAccessCodeTag", false, 0, 0, 0, 0, code, code_len, allowed_diffs);
 }
 rr_block* rr_bit_decoder_create(int flags, unsigned long long mask, unsigned long long seed, unsigned len, unsigned long long code,
@@ -255,142 +262,103 @@ rr_block* rr_bit_decoder_create(int flags, unsigned long long mask, unsigned lon
     return make_bits("BitDecoder", true, flags, mask, seed, len, code, code_len, allowed_diffs);
 }
 int rr_bit_tags(rr_block* b, size_t* pos, unsigned char* diffs, size_t cap, size_t* total) {
-    auto* d = b ? dynamic_cast<rr::BitDecoder*>(b->b.get()) : nullptr;
-    if (!d || !d->has_correlator() || !total || (cap && (!pos || !diffs))) {
-        rr::set_last_error("rr_bit_tags: not a handle with a correlator stage / null argument");
-        return RR_ERR;
-    }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(d->device));
-        const std::vector<unsigned long long>& e = d->fetch_tags();
-        *total = e.size();
-        for (size_t j = 0; j < e.size() && j < cap; j++) { pos[j] = (size_t)(e[j] >> 8); diffs[j] = (unsigned char)(e[j] & 0xff); }
-    });
+    static const char NOT_A[] = "not a handle with a correlator stage / null argument";
+    auto* d = as<rr::BitDecoder>(b, "rr_bit_tags", NOT_A, total && (!cap || (pos && diffs)));
+    if (d && !d->has_correlator()) d = as<rr::BitDecoder>(nullptr, "rr_bit_tags", NOT_A);
+    if (!d) return RR_ERR;
+    return on_device(d, [&] { unpack(d->fetch_tags(), 8, pos, diffs, cap, total); });
 }
 rr_block* rr_wpcr_create(float samp_rate) {
     return make_block([&] { return new rr::Wpcr(samp_rate); });
 }
-static rr::Wpcr* as_wpcr(rr_block* b, const char* what) {
-    auto* w = b ? dynamic_cast<rr::Wpcr*>(b->b.get()) : nullptr;
-    if (!w) rr::set_last_error(std::string(what) + ": not a wpcr handle");
-    return w;
-}
 int rr_wpcr_process_dev(rr_block* b, const void* d_samples, size_t n_total, size_t* starts, size_t* lens, const float* mid,
                         size_t nbursts, void* d_syms, void* hip_stream) {
-    auto* w = as_wpcr(b, "rr_wpcr_process_dev");
+    auto* w = as<rr::Wpcr>(b, "rr_wpcr_process_dev", NOT_WPCR);
     if (!w) return RR_ERR;
     if (nbursts && (!d_samples || !d_syms || !starts || !lens)) { rr::set_last_error("rr_wpcr_process_dev: null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(w->device));
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);      // used as given (see rr_block_work_dev)
-        w->last_stream = s;
+    return on_device(w, hip_stream, [&](hipStream_t s) {
         w->process_dev(static_cast<const float*>(d_samples), n_total, starts, lens, mid, nbursts, static_cast<float*>(d_syms), s);
     });
 }
 int rr_wpcr_process(rr_block* b, const float* samples, size_t n_total, size_t* starts, size_t* lens, const float* mid, size_t nbursts,
                     float* syms) {
-    auto* w = as_wpcr(b, "rr_wpcr_process");
+    auto* w = as<rr::Wpcr>(b, "rr_wpcr_process", NOT_WPCR);
     if (!w) return RR_ERR;
     if (nbursts && (!samples || !syms || !starts || !lens)) { rr::set_last_error("rr_wpcr_process: null argument"); return RR_ERR; }
     return guarded([&] { w->process_host(samples, n_total, starts, lens, mid, nbursts, syms); });
 }
 int rr_wpcr_results(rr_block* b, rr_wpcr_result* res, size_t cap, size_t* total) {
-    auto* w = as_wpcr(b, "rr_wpcr_results");
+    auto* w = as<rr::Wpcr>(b, "rr_wpcr_results", NOT_WPCR);
     if (!w) return RR_ERR;
     if (!total || (cap && !res)) { rr::set_last_error("rr_wpcr_results: null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(w->device));
+    return on_device(w, [&] {
         const std::vector<rr::WpcrResult>& r = w->fetch_results();
         *total = r.size();
-        if (const size_t k = std::min(cap, r.size())) std::memcpy(res, r.data(), k * sizeof(rr_wpcr_result));   // (the same layout: blocks.cpp)
+        if (const size_t k = std::min(cap, r.size())) std::memcpy(res, r.data(), k * sizeof(rr_wpcr_result));   // (the same layout: blocks_packet.cpp)
     });
 }
 int rr_debug_wpcr_spectrum(rr_block* b, size_t burst, float* mag, size_t cap, size_t* nbins) {
-    auto* w = as_wpcr(b, "rr_debug_wpcr_spectrum");
+    auto* w = as<rr::Wpcr>(b, "rr_debug_wpcr_spectrum", NOT_WPCR);
     if (!w) return RR_ERR;
     if (!nbins || (cap && !mag)) { rr::set_last_error("rr_debug_wpcr_spectrum: null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(w->device));
+    return on_device(w, [&] {
         const std::vector<float> m = w->fetch_spectrum(burst);
         *nbins = m.size();
         if (const size_t k = std::min(cap, m.size())) std::memcpy(mag, m.data(), k * sizeof(float));
     });
 }
 rr_block* rr_stream_to_pdu_create(float threshold, size_t max_size, size_t tail, int flags) {
-    if (const char* e = rr::pdu_check(max_size, flags)) { rr::set_last_error(e); return nullptr; }     // before any device is touched
+    if (const char* e = rr::pdu_check(max_size, flags)) return refuse_create(e);
     return make_block([&] { return new rr::StreamToPdu(threshold, max_size, tail, flags); });
 }
-static rr::StreamToPdu* as_pdu(rr_block* b, const char* what) {
-    auto* p = b ? dynamic_cast<rr::StreamToPdu*>(b->b.get()) : nullptr;
-    if (!p) rr::set_last_error(std::string(what) + ": not a stream_to_pdu handle");
-    return p;
-}
 int rr_stream_to_pdu_push_dev(rr_block* b, const void* d_data, const void* d_trigger, size_t n, void* hip_stream) {
-    auto* p = as_pdu(b, "rr_stream_to_pdu_push_dev");
+    auto* p = as<rr::StreamToPdu>(b, "rr_stream_to_pdu_push_dev", NOT_PDU);
     if (!p) return RR_ERR;
     if (n && (!d_data || !d_trigger)) { rr::set_last_error("rr_stream_to_pdu_push_dev: null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(p->device));
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);      // used as given (see rr_block_work_dev)
-        p->last_stream = s;
+    return on_device(p, hip_stream, [&](hipStream_t s) {
         p->push_dev(static_cast<const float*>(d_data), static_cast<const float*>(d_trigger), n, s);
     });
 }
 int rr_stream_to_pdu_push(rr_block* b, const float* data, const float* trigger, size_t n) {
-    auto* p = as_pdu(b, "rr_stream_to_pdu_push");
+    auto* p = as<rr::StreamToPdu>(b, "rr_stream_to_pdu_push", NOT_PDU);
     if (!p) return RR_ERR;
     if (n && (!data || !trigger)) { rr::set_last_error("rr_stream_to_pdu_push: null argument"); return RR_ERR; }
     return guarded([&] { p->push_host(data, trigger, n); });
 }
 int rr_pdu_records(rr_block* b, rr_pdu_record* rec, size_t cap, size_t* total) {
-    auto* p = as_pdu(b, "rr_pdu_records");
+    auto* p = as<rr::StreamToPdu>(b, "rr_pdu_records", NOT_PDU);
     if (!p) return RR_ERR;
     if (!total || (cap && !rec)) { rr::set_last_error("rr_pdu_records: null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(p->device));
-        rr::pdu_copy_out(p->fetch_records(), rec, cap, total);
-    });
+    return on_device(p, [&] { rr::pdu_copy_out(p->fetch_records(), rec, cap, total); });
 }
 int rr_pdu_edges(rr_block* b, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
-    auto* p = as_pdu(b, "rr_pdu_edges");
+    auto* p = as<rr::StreamToPdu>(b, "rr_pdu_edges", NOT_PDU);
     if (!p) return RR_ERR;
     if (!total || (cap && (!pos || !val))) { rr::set_last_error("rr_pdu_edges: null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(p->device));
-        const std::vector<unsigned>& e = p->fetch_edges();
-        *total = e.size();
-        for (size_t j = 0; j < e.size() && j < cap; j++) { pos[j] = (size_t)(e[j] >> 1); val[j] = (unsigned char)(e[j] & 1u); }
-    });
+    return on_device(p, [&] { unpack(p->fetch_edges(), 1, pos, val, cap, total); });
 }
 const void* rr_pdu_arena_dev(rr_block* b, size_t* n_total) {
-    auto* p = as_pdu(b, "rr_pdu_arena_dev");
+    auto* p = as<rr::StreamToPdu>(b, "rr_pdu_arena_dev", NOT_PDU);
     if (n_total) *n_total = p ? p->n_total : 0;
     return p ? p->arena_dev() : nullptr;
 }
 int rr_pdu_fetch(rr_block* b, size_t idx, float* out, size_t cap) {
-    auto* p = as_pdu(b, "rr_pdu_fetch");
+    auto* p = as<rr::StreamToPdu>(b, "rr_pdu_fetch", NOT_PDU);
     if (!p) return RR_ERR;
     if (cap && !out) { rr::set_last_error("rr_pdu_fetch: null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(p->device));
-        p->fetch_pdu(idx, out, cap);
-    });
+    return on_device(p, [&] { p->fetch_pdu(idx, out, cap); });
 }
 int rr_debug_pdu_ranks(rr_block* b, size_t idx, float* low, float* high) {
-    auto* p = as_pdu(b, "rr_debug_pdu_ranks");
+    auto* p = as<rr::StreamToPdu>(b, "rr_debug_pdu_ranks", NOT_PDU);
     if (!p) return RR_ERR;
     if (!low || !high) { rr::set_last_error("rr_debug_pdu_ranks: null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(p->device));
-        p->fetch_ranks(idx, low, high);
-    });
+    return on_device(p, [&] { p->fetch_ranks(idx, low, high); });
 }
 int rr_wpcr_process_pdus(rr_block* wpcr, rr_block* pdus, void* d_syms, void* hip_stream) {
-    auto* w = as_wpcr(wpcr, "rr_wpcr_process_pdus");
-    auto* p = as_pdu(pdus, "rr_wpcr_process_pdus");
+    auto* w = as<rr::Wpcr>(wpcr, "rr_wpcr_process_pdus", NOT_WPCR);
+    auto* p = as<rr::StreamToPdu>(pdus, "rr_wpcr_process_pdus", NOT_PDU);
     if (!w || !p) return RR_ERR;
-    return guarded([&] {
-        RR_HIP(hipSetDevice(p->device));
+    return on_device(p, [&] {
         if (w->device != p->device) throw rr::Error("rr_wpcr_process_pdus: the two handles live on different devices");
         std::vector<size_t> starts, lens;
         std::vector<float> mids;
@@ -405,11 +373,10 @@ int rr_wpcr_process_pdus(rr_block* wpcr, rr_block* pdus, void* d_syms, void* hip
 }
 int rr_wpcr_pack_dev(rr_block* wpcr, const void* d_syms, void* d_out, size_t out_cap, size_t* produced, size_t* pdu_start,
                      size_t* pdu_len, size_t cap, size_t* npdus, void* hip_stream) {
-    auto* w = as_wpcr(wpcr, "rr_wpcr_pack_dev");
+    auto* w = as<rr::Wpcr>(wpcr, "rr_wpcr_pack_dev", NOT_WPCR);
     if (!w) return RR_ERR;
     if (!produced || !npdus) { rr::set_last_error("rr_wpcr_pack_dev: null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(w->device));
+    return on_device(w, [&] {
         hipStream_t s = static_cast<hipStream_t>(hip_stream);
         w->pack_dev(static_cast<const float*>(d_syms), static_cast<float*>(d_out), out_cap, produced, pdu_start, pdu_len, cap, npdus, s);
         w->last_stream = s;
@@ -422,36 +389,28 @@ rr_block* rr_scrambler_g3ruh_create(void) {
     return make_block([&] { return new rr::LineCoder("Scrambler", rr::LINE_SCR); }, RR_TAGS_FORWARD, 1);
 }
 rr_block* rr_hdlc_framer_create(int flags, float lo, float hi) {
-    if (const char* e = rr::frame_check_flags(flags)) { rr::set_build_opts(nullptr); rr::set_last_error(e); return nullptr; }   // before any device is touched
+    if (const char* e = rr::frame_check_flags(flags)) return refuse_create(e);
     return make_block([&] { return new rr::HdlcFramer(flags, lo, hi); });
 }
-static rr::HdlcFramer* as_framer(const rr_block* b, const char* what) {
-    auto* f = b ? dynamic_cast<rr::HdlcFramer*>(b->b.get()) : nullptr;
-    if (!f) rr::set_last_error(std::string(what) + ": not an hdlc framer handle");
-    return f;
-}
 size_t rr_hdlc_framer_bound(const rr_block* b, const size_t* lens, size_t npackets) {
-    auto* f = as_framer(b, "rr_hdlc_framer_bound");
+    auto* f = as<rr::HdlcFramer>(b, "rr_hdlc_framer_bound", NOT_FRAMER);
     if (!f || (npackets && !lens)) return 0;
     return rr::frame_bound(f->flags, lens, npackets);
 }
 int rr_hdlc_framer_push_dev(rr_block* b, const void* d_bytes, size_t n_bytes, size_t* starts, size_t* lens, size_t npackets,
                             void* d_out, size_t out_cap, void* hip_stream) {
-    auto* f = as_framer(b, "rr_hdlc_framer_push_dev");
+    auto* f = as<rr::HdlcFramer>(b, "rr_hdlc_framer_push_dev", NOT_FRAMER);
     if (!f) return RR_ERR;
     size_t bound = 0;                                  // every refusal before any device is touched
     if (const char* e = rr::frame_check_push(f->flags, n_bytes, starts, lens, npackets, out_cap, &bound)) { rr::set_last_error(e); return RR_ERR; }
     if (npackets && (!d_out || (n_bytes && !d_bytes))) { rr::set_last_error("rr_hdlc_framer_push_dev: null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(f->device));
-        hipStream_t s = static_cast<hipStream_t>(hip_stream);      // used as given (see rr_block_work_dev)
-        f->last_stream = s;
+    return on_device(f, hip_stream, [&](hipStream_t s) {
         f->push_dev(static_cast<const unsigned char*>(d_bytes), n_bytes, starts, lens, npackets, d_out, out_cap, s);
     });
 }
 int rr_hdlc_framer_push(rr_block* b, const unsigned char* bytes, size_t n_bytes, size_t* starts, size_t* lens, size_t npackets,
                         void* out, size_t out_cap, size_t* produced) {
-    auto* f = as_framer(b, "rr_hdlc_framer_push");
+    auto* f = as<rr::HdlcFramer>(b, "rr_hdlc_framer_push", NOT_FRAMER);
     if (!f) return RR_ERR;
     if (!produced) { rr::set_last_error("rr_hdlc_framer_push: null argument"); return RR_ERR; }
     size_t bound = 0;
@@ -460,17 +419,16 @@ int rr_hdlc_framer_push(rr_block* b, const unsigned char* bytes, size_t n_bytes,
     return guarded([&] { f->push_host(bytes, n_bytes, starts, lens, npackets, out, out_cap, produced); });
 }
 int rr_hdlc_framer_records(rr_block* b, rr_frame_record* rec, size_t cap, size_t* total, size_t* produced) {
-    auto* f = as_framer(b, "rr_hdlc_framer_records");
+    auto* f = as<rr::HdlcFramer>(b, "rr_hdlc_framer_records", NOT_FRAMER);
     if (!f) return RR_ERR;
     if (!total || !produced || (cap && !rec)) { rr::set_last_error("rr_hdlc_framer_records: null argument"); return RR_ERR; }
-    return guarded([&] {
-        RR_HIP(hipSetDevice(f->device));
+    return on_device(f, [&] {
         rr::frame_copy_out(f->fetch_records(), rec, cap, total);
         *produced = f->produced;
     });
 }
 int rr_hdlc_framer_dims(const rr_block* b, size_t* tile_bits) {
-    auto* f = as_framer(b, "rr_hdlc_framer_dims");
+    auto* f = as<rr::HdlcFramer>(b, "rr_hdlc_framer_dims", NOT_FRAMER);
     if (!f || !tile_bits) { if (f) rr::set_last_error("rr_hdlc_framer_dims: null argument"); return RR_ERR; }
     static_assert(rr::FRAME_T == rr::LINE_T, "one tile length for the stuffing scan and the line coder");
     *tile_bits = rr::FRAME_T;

@@ -1,0 +1,537 @@
+// blocks_packet.cpp — host side of the packet-side blocks (blocks_packet.hpp): the sync blocks, the burst and bit blocks, and the
+// batch handles (Wpcr, StreamToPdu, HdlcFramer).  Citations are to the reference's src, as in blocks.cpp.
+#include "blocks_packet.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+
+#include "frame_core.hpp"
+#include "frame_host.hpp"
+#include "pdu_host.hpp"
+
+namespace rr {
+
+// ---- MultiplyConst, FastFM (sync blocks) ------------------------------------------------------------------------
+static int sync_counts(size_t in_len, size_t out_cap, size_t* n, size_t* need) {
+    *need = 1;
+    if (in_len == 0) { *n = 0; return RR_WAIT_SRC; }
+    if (out_cap == 0) { *n = 0; return RR_WAIT_DST; }
+    *n = std::min(in_len, out_cap);
+    return in_len - *n == 0 ? RR_WAIT_SRC : RR_WAIT_DST;      // the loop's next iteration
+}
+int SyncBlock::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed, size_t* produced, size_t* need,
+                        hipStream_t s) {
+    size_t n = 0;
+    const int st = sync_counts(in_len, out_cap, &n, need);
+    begin_call();
+    if (n) {
+        prof_begin(s);
+        run(in, out, n, s);
+        prof_end(s);
+    }
+    *consumed = *produced = n;
+    return st;
+}
+MultiplyConst::MultiplyConst(size_t es, float re, float im) : SyncBlock("MultiplyConst", es, es), vr(re), vi(im) {
+    if (es != 4 && es != 8) throw Error("MultiplyConst: Float or Complex only");
+}
+void MultiplyConst::run(const void* in, void* out, size_t n, hipStream_t s) {
+    if (in_es == 4) launch_mulconst_f32(static_cast<const float*>(in), static_cast<float*>(out), (long)n, vr, s);
+    else launch_mulconst_c32(static_cast<const cf*>(in), static_cast<cf*>(out), (long)n, vr, vi, s);
+}
+FastFM::FastFM() : SyncBlock("FastFM", 8, 4) {
+    hist.zero(2, stream);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void FastFM::run(const void* in, void* out, size_t n, hipStream_t s) {
+    VSrc<cf> src{hist.in(), 2, static_cast<const cf*>(in), (long)n};
+    launch_fastfm(src, static_cast<float*>(out), (long)n, s);
+    launch_vcopy_c32(src, (long)n, hist.out(), 2, s);                // q2, q1 for the next call
+    hist.flip();
+}
+
+// ---- Vco (vco.rs:9-37) and RationalResampler -> Vco (examples/fm_tx.rs:84-91) ------------------------------------------------
+VcoState::VcoState(double kk, hipStream_t s) : k(kk) {
+    phase.zero(1, s);                                // phase: 0.0 (vco.rs:18)
+    RR_HIP(hipStreamSynchronize(s));
+}
+Vco::Vco(double k) : SyncBlock("Vco", 4, 8), v(k, stream) {
+    zero_copy_in = false;                            // (the scan reads the window twice: tile sums, then the samples)
+}
+void Vco::run(const void* in, void* out, size_t n, hipStream_t s) {
+    launch_vco(static_cast<const float*>(in), static_cast<cf*>(out), (long)n, v.k, v.phase.in(), v.phase.out(), v.scratch(n), s);
+    v.phase.flip();
+}
+FmTx::FmTx(size_t interp, size_t deci, double k) : Resampler("RationalResampler>Vco", interp, deci, 4, 8), v(k, stream) {
+    zero_copy_in = false;
+}
+void FmTx::emit(const void* in, void* out, int64_t r, int64_t n_gather, int64_t c0, hipStream_t s) {
+    const int64_t n = r + n_gather;
+    if (n <= 0) return;
+    launch_fm_tx(static_cast<const float*>(in), static_cast<cf*>(out), (long)r, reinterpret_cast<const float*>(d_pending.p),
+                 (long)n_gather, (long)I, (long)D, (long)c0, v.k, v.phase.in(), v.phase.out(), v.scratch((size_t)n), s);
+    v.phase.flip();
+}
+
+// ---- ComplexToMag2, SinglePoleIirFilter and the burst detector (kernels_burst.hip) ----------------------------------------------
+ComplexToMag2::ComplexToMag2() : SyncBlock("ComplexToMag2", 8, 4) {}
+void ComplexToMag2::run(const void* in, void* out, size_t n, hipStream_t s) {
+    launch_mag2(static_cast<const cf*>(in), static_cast<float*>(out), (long)n, s);
+}
+IirState::IirState(float alpha, int nrows, hipStream_t s) : rows(nrows) {
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) throw Error("alpha out of range");          // single_pole_iir_filter.rs:38-41 (None)
+    const float one_minus = 1.0f - alpha;                                              // :42-43: the reference's two f32 fields
+    c.a = (double)alpha;
+    c.b = (double)one_minus;
+    std::vector<double> p8(IIR_PW8_N), ps(IIR_PWS_N);
+    for (int k = 0; k < IIR_PW8_N; k++) p8[k] = (double)powl((long double)c.b, (long double)(8L * k));
+    for (int k = 0; k < IIR_PWS_N; k++) ps[k] = (double)powl((long double)c.b, (long double)((long)IIR_SSPAN * k));
+    c.bT = p8[IIR_PW8_N - 1];
+    pw8.upload(p8.data(), p8.size(), s);
+    pws.upload(ps.data(), ps.size(), s);
+    c.pw8 = pw8.p;
+    c.pws = pws.p;
+    y.zero(rows, s);                                 // prev_output: 0 (:25)
+    RR_HIP(hipStreamSynchronize(s));
+}
+SinglePoleIir::SinglePoleIir(float alpha, size_t es)
+    : SyncBlock("SinglePoleIirFilter", es == 4 || es == 8 ? es : throw Error("SinglePoleIirFilter: Float or Complex only"), es),
+      st(alpha, es == 8 ? 2 : 1, stream) {
+    zero_copy_in = false;                            // (the scan reads the window twice: tile responses, then the samples)
+}
+void SinglePoleIir::run(const void* in, void* out, size_t n, hipStream_t s) {
+    if (in_es == 4)
+        launch_iir_f32(static_cast<const float*>(in), static_cast<float*>(out), (long)n, st.c, st.y.in(), st.y.out(), st.scratch(n), s);
+    else
+        launch_iir_c32(static_cast<const cf*>(in), static_cast<cf*>(out), (long)n, st.c, st.y.in(), st.y.out(), st.scratch(n), s);
+    st.y.flip();
+}
+BurstDetector::BurstDetector(float alpha, float threshold)
+    : SyncBlock("ComplexToMag2>SinglePoleIirFilter>BurstTagger", 8, 4), st(alpha, 1, stream), thr(threshold) {
+    zero_copy_in = false;
+    flag.zero(1, stream);                            // last_state: false (burst_tagger.rs:62)
+    count.zero(1, stream);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void BurstDetector::begin_call() {
+    edges.clear();
+    fetched = true;                                  // a call that moves nothing has no edges and leaves every state alone
+}
+void BurstDetector::run(const void* in, void* out, size_t n, hipStream_t s) {
+    list.reserve(n);
+    // (this call's counter was zeroed by the previous call's launch, or at construction; it zeroes the other one)
+    launch_burst_detector(static_cast<const cf*>(in), static_cast<float*>(out), (long)n, st.c, st.y.in(), st.y.out(), st.scratch(n), thr,
+                          flag.in(), flag.out(), count.out(), count.in(), list.p, s);
+    st.y.flip();
+    flag.flip();
+    count.flip();
+    fetched = false;
+}
+const std::vector<unsigned long long>& BurstDetector::fetch_edges() {
+    sync();
+    if (!fetched) {
+        fetch_counted(count.in(), list.p, list.cap, "burst detector: edge count beyond the window", edges, stream);
+        std::sort(edges.begin(), edges.end());       // the device appends in no order; the position is the high part
+        fetched = true;
+    }
+    return edges;
+}
+
+// ---- BinarySlicer, NrziDecode, Descrambler, CorrelateAccessCodeTag and their fusion (kernels_bits.hip) ---------------------------
+const char* bits_check(int flags, unsigned long long seed, unsigned len, unsigned code_len) {
+    if (flags & ~(RR_BITS_INVERT | RR_BITS_NRZI | RR_BITS_DESCRAMBLE)) return "unknown bit decoder flags";
+    if (flags & RR_BITS_DESCRAMBLE) {
+        if (len >= 64) return "descrambler length out of range";                       // descrambler.rs:22 (assert)
+        if (len < 63 && seed >> (len + 1)) return "seed wider than the register";
+    }
+    if (code_len > 64) return "access code longer than 64 bits";
+    return nullptr;
+}
+BitDecoder::BitDecoder(const char* nm, bool f32src, int flags, unsigned long long mask, unsigned long long seed, unsigned len,
+                       unsigned long long code, unsigned code_len, size_t allowed_diffs)
+    : SyncBlock(nm, f32src ? 4 : 1, 1) {
+    if (const char* e = bits_check(flags, seed, len, code_len)) throw Error(e);
+    cfg.invert = flags & RR_BITS_INVERT ? 1 : 0;
+    cfg.nrzi = flags & RR_BITS_NRZI ? 1 : 0;
+    unsigned long long init[BITS_ST_N] = {0, 0, 0, 0};                                // last: 0 (nrzi.rs:32-33); nothing seen
+    if (flags & RR_BITS_DESCRAMBLE) {
+        // shift_reg holds d[n-1-k] in bit len-k (descrambler.rs:37), so mask bit j reads d[n - delta], delta = 1 + len - j;
+        // before the stream the register is the seed: d[-1-k] = bit len-k of it
+        for (unsigned j = 0; j <= len; j++)
+            if (mask >> j & 1) cfg.dmask |= 1ull << (len - j);
+        init[BITS_ST_DHIST] = seed << (63 - len);
+    }
+    cfg.L = (int)code_len;
+    cfg.code = code_len == 64 ? code : code & ((1ull << code_len) - 1ull);
+    cfg.allowed = (unsigned)std::min<size_t>(allowed_diffs, 64);
+    st.upload(init, BITS_ST_N, stream);
+    total.reserve(1);
+    zero_copy_in = false;                            // (tiles re-read their 128 samples of history, and a misaligned window is read one
+                                                     //  sample per lane: a page-locked host window is copied down first)
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void BitDecoder::begin_call() {
+    tags.clear();
+    fetched = true;                                  // a call that moves nothing has no tags and leaves every state alone
+}
+void BitDecoder::run(const void* in, void* out, size_t n, hipStream_t s) {
+    const size_t ntiles = (n + BITS_T - 1) / BITS_T;
+    if (cfg.L) { tilecnt.reserve(ntiles); list.reserve(ntiles * BITS_T); }
+    if (in_es == 4)
+        launch_bits_f32(static_cast<const float*>(in), static_cast<unsigned char*>(out), (long)n, cfg, st.in(), st.out(), tilecnt.p,
+                        list.p, s);
+    else
+        launch_bits_u8(static_cast<const unsigned char*>(in), static_cast<unsigned char*>(out), (long)n, cfg, st.in(), st.out(),
+                       tilecnt.p, list.p, s);
+    st.flip();
+    if (cfg.L) { last_tiles = ntiles; fetched = false; }
+}
+const std::vector<unsigned long long>& BitDecoder::fetch_tags() {
+    sync();
+    if (!fetched) {
+        // the tiles' entries without the gaps between them, in two small launches; tiles and the entries of a tile are ascending
+        offs.reserve(last_tiles);
+        launch_bits_tag_offsets(tilecnt.p, (long)last_tiles, offs.p, total.p, stream);
+        const auto pack = [&](size_t nt) {
+            packed.reserve(nt);
+            launch_bits_tag_gather(tilecnt.p, offs.p, list.p, (long)last_tiles, packed.p, stream);
+            return packed.p;
+        };
+        fetch_counted_at(total.p, pack, last_tiles * (size_t)BITS_T, "bit decoder: tag count beyond the window", tags, stream);
+        fetched = true;
+    }
+    return tags;
+}
+
+// ---- Wpcr (wpcr.rs:105-239; kernels_wpcr.hip) ---------------------------------------------------------------------------------------
+static_assert(sizeof(WpcrResult) == sizeof(rr_wpcr_result) && offsetof(WpcrResult, nsyms) == offsetof(rr_wpcr_result, nsyms) &&
+              offsetof(WpcrResult, frequency) == offsetof(rr_wpcr_result, frequency), "WpcrResult is rr_wpcr_result");
+Wpcr::Wpcr(float rate)
+    : BatchBlock("Wpcr", 4, 4, "Wpcr takes whole bursts: rr_wpcr_process / rr_wpcr_process_dev"), samp_rate(rate) {}
+void Wpcr::check(size_t n_total, const size_t* st, const size_t* ln, size_t nbursts) {
+    if (nbursts && (!st || !ln)) throw Error("null burst descriptors");
+    size_t end = 0;
+    for (size_t b = 0; b < nbursts; b++) {
+        if (st[b] < end) throw Error("bursts overlap");
+        if (st[b] > n_total || ln[b] > n_total - st[b]) throw Error("burst outside the buffer");
+        if (ln[b] > MAX_LEN) throw Error("burst longer than 512000 samples");
+        end = st[b] + ln[b];
+    }
+}
+void Wpcr::process_dev(const float* d_x, size_t n_total, const size_t* st, const size_t* ln, const float* mid, size_t nbursts,
+                       float* d_syms, hipStream_t s) {
+    check(n_total, st, ln, nbursts);
+    if (nbursts > 0x3fffffff) throw Error("too many bursts");
+    starts.assign(st, st + nbursts);
+    lens.assign(ln, ln + nbursts);
+    results.clear();
+    fetched = true;
+    if (!nbursts) return;
+    // the records, then the burst of every sample tile, then of every bin tile
+    size_t nst = 0, nbt = 0;
+    for (size_t b = 0; b < nbursts; b++) {
+        nst += (ln[b] + WPCR_T - 1) / WPCR_T;
+        nbt += ln[b] ? ((ln[b] - 1) / 2 + WPCR_BT - 1) / WPCR_BT : 0;
+    }
+    if (nst > 0x7fffffff || nbt > 0x7fffffff) throw Error("too many tiles");
+    const size_t maps_at = nbursts * sizeof(WpcrBurst), bytes = maps_at + (nst + nbt) * sizeof(int);
+    hdesc.resize(bytes);
+    WpcrBurst* hb = reinterpret_cast<WpcrBurst*>(hdesc.data());
+    int* smap = reinterpret_cast<int*>(hdesc.data() + maps_at);
+    int* bmap = smap + nst;
+    size_t si = 0, bi = 0;
+    for (size_t b = 0; b < nbursts; b++) {
+        hb[b].start = (long)st[b];
+        hb[b].n = (int)ln[b];
+        hb[b].mid = mid ? mid[b] : 0.0f;
+        hb[b].stile0 = (int)si;
+        hb[b].btile0 = (int)bi;
+        const size_t ns = (ln[b] + WPCR_T - 1) / WPCR_T, nb = ln[b] ? ((ln[b] - 1) / 2 + WPCR_BT - 1) / WPCR_BT : 0;
+        for (size_t t = 0; t < ns; t++) smap[si++] = (int)b;
+        for (size_t t = 0; t < nb; t++) bmap[bi++] = (int)b;
+    }
+    desc.reserve(bytes);
+    list.reserve(n_total);
+    mag.reserve(n_total);
+    reim.reserve(n_total);
+    tilecnt.reserve(std::max<size_t>(nst, 1));
+    res.reserve(nbursts);
+    hstage().h2d(desc.p, hdesc.data(), bytes, s);                // (through the block's pinned chunks: hdesc is free on return)
+    const WpcrBurst* db = reinterpret_cast<const WpcrBurst*>(desc.p);
+    const int* dsmap = reinterpret_cast<const int*>(desc.p + maps_at);
+    prof_begin(s);
+    launch_wpcr(d_x, db, (long)nbursts, dsmap, (long)nst, dsmap + nst, (long)nbt, mid != nullptr, samp_rate, list.p, tilecnt.p, mag.p,
+                reim.p, res.p, d_syms, s);
+    prof_end(s);
+    fetched = false;
+}
+void Wpcr::process_host(const float* x, size_t n_total, const size_t* st, const size_t* ln, const float* mid, size_t nbursts,
+                        float* syms) {
+    host_call([&] {
+        check(n_total, st, ln, nbursts);
+        h_in.reserve(std::max<size_t>(n_total, 1));
+        h_out.reserve(std::max<size_t>(n_total, 1));
+        // only the span of the bursts crosses the bus, in both directions
+        const size_t lo = nbursts ? st[0] : 0, hi = nbursts ? st[nbursts - 1] + ln[nbursts - 1] : 0;
+        if (hi > lo) {
+            hstage().h2d(h_in.p + lo, x + lo, (hi - lo) * sizeof(float), stream);
+            RR_HIP(hipMemsetAsync(h_out.p + lo, 0, (hi - lo) * sizeof(float), stream));
+        }
+        process_dev(h_in.p, n_total, st, ln, mid, nbursts, h_out.p, stream);
+        if (hi > lo) hstage().d2h(syms + lo, h_out.p + lo, (hi - lo) * sizeof(float), stream);
+    });
+}
+const std::vector<WpcrResult>& Wpcr::fetch_results() {
+    settle();
+    if (!fetched) {
+        results.resize(starts.size());
+        if (!results.empty()) stage_download_sync(results.data(), res.p, results.size() * sizeof(WpcrResult), stream);
+        fetched = true;
+    }
+    return results;
+}
+std::vector<float> Wpcr::fetch_spectrum(size_t burst) {
+    sync();
+    if (burst >= starts.size()) throw Error("rr_debug_wpcr_spectrum: no such burst in the most recent call");
+    std::vector<float> m(lens[burst] ? (lens[burst] - 1) / 2 : 0);
+    if (!m.empty()) stage_download_sync(m.data(), mag.p + starts[burst], m.size() * sizeof(float), stream);
+    return m;
+}
+
+// ---- StreamToPdu (burst_tagger.rs:68-85, stream_to_pdu.rs:198-275, wpcr.rs:62-78; kernels_pdu.hip) -------------------------------------
+static_assert(sizeof(PduRec) == sizeof(rr_pdu_record) && offsetof(PduRec, nlow) == offsetof(rr_pdu_record, nlow) &&
+              offsetof(PduRec, mid) == offsetof(rr_pdu_record, mid) && offsetof(PduRec, stream_pos) == offsetof(rr_pdu_record, stream_pos),
+              "PduRec is rr_pdu_record");
+StreamToPdu::StreamToPdu(float threshold, size_t max_sz, size_t tl, int flags)
+    : BatchBlock("BurstTagger>StreamToPdu>Midpointer", 4, 4, "StreamToPdu forms PDUs: rr_stream_to_pdu_push / rr_stream_to_pdu_push_dev"),
+      thr(threshold), max_size(max_sz),
+      tail(std::min(tl, max_sz + 1)),          // (a tail beyond max_size files nothing, like max_size + 1: no sum below overflows)
+      midpoint((flags & RR_PDU_MIDPOINT) != 0) {
+    if (const char* e = pdu_check(max_sz, flags)) throw Error(e);
+    PduState init{};
+    init.free = 0;                             // Unsync, last_state false (stream_to_pdu.rs:102, burst_tagger.rs:62)
+    init.open_r = init.open_f = PDU_NONE;
+    st.upload(&init, 1, stream);
+    etotal.reserve(1);
+    count.reserve(1);
+    root.reserve(1);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void StreamToPdu::push_dev(const float* d_data, const float* d_trig, size_t n, hipStream_t s) {
+    if (n > MAX_WINDOW) throw Error("window longer than 1024000 samples");
+    records.clear();
+    edgelist.clear();
+    fetched = efetched = true;                 // a push that moves nothing has no PDUs and no edges and leaves every state alone
+    last_n = n;
+    n_total = 0;
+    if (!n) return;
+    const size_t ntiles = (n + PDU_T - 1) / PDU_T, nr = n / 2 + 2;
+    arena.reserve_out(max_size + n);
+    tilecnt.reserve(ntiles);
+    offs.reserve(ntiles);
+    edges.reserve(n);
+    jmp[0].reserve(nr);
+    jmp[1].reserve(nr);
+    mark.reserve(nr);
+    recs.reserve(nr);
+    if (midpoint) ranks.reserve(2 * nr);
+    PduArgs g{};
+    g.data = d_data; g.trig = d_trig; g.n = (long)n; g.thr = thr;
+    g.max_size = max_size; g.tail = tail; g.w0 = w0; g.C = (long)max_size;
+    g.prev_arena = arena.in();                 // (nullptr before the first push: nothing is open then)
+    g.n_prev = (long)n_prev;
+    g.arena = arena.out();
+    g.st_in = st.in(); g.st_out = st.out();
+    g.tilecnt = tilecnt.p; g.offs = offs.p; g.etotal = etotal.p; g.edges = edges.p;
+    g.jmp0 = jmp[0].p; g.jmp1 = jmp[1].p; g.mark = mark.p; g.root = root.p;
+    g.recs = recs.p; g.rec_cap = (long)nr; g.count = count.p; g.ranks = ranks.p; g.midpoint = midpoint;
+    prof_begin(s);
+    launch_pdu(g, s);
+    prof_end(s);
+    arena.flip();
+    st.flip();
+    n_prev = n;
+    n_total = max_size + n;
+    w0 += n;
+    fetched = efetched = false;
+}
+void StreamToPdu::push_host(const float* data, const float* trig, size_t n) {
+    host_call([&] {
+        if (n > MAX_WINDOW) throw Error("window longer than 1024000 samples");
+        if (n) {
+            h_data.reserve(n);
+            h_trig.reserve(n);
+            hstage().h2d(h_data.p, data, n * sizeof(float), stream);
+            hstage().h2d(h_trig.p, trig, n * sizeof(float), stream);
+        }
+        push_dev(h_data.p, h_trig.p, n, stream);
+    });
+}
+const std::vector<rr_pdu_record>& StreamToPdu::fetch_records() {
+    settle();
+    if (!fetched) {
+        fetch_counted(count.p, recs.p, recs.cap, pdu_count_check((unsigned long long)recs.cap + 1, recs.cap), records, stream);
+        pdu_sort(records, slots);              // the device appends in no order
+        fetched = true;
+    }
+    return records;
+}
+const std::vector<unsigned>& StreamToPdu::fetch_edges() {
+    settle();
+    if (!efetched) {
+        fetch_counted(etotal.p, edges.p, last_n, "stream_to_pdu: edge count beyond the window", edgelist, stream);
+        efetched = true;
+    }
+    return edgelist;
+}
+void StreamToPdu::fetch_pdu(size_t idx, float* out, size_t cap) {
+    const std::vector<rr_pdu_record>& r = fetch_records();
+    if (idx >= r.size()) throw Error("rr_pdu_fetch: no such PDU in the most recent push");
+    if (r[idx].start > n_total || r[idx].len > n_total - r[idx].start) throw Error("stream_to_pdu: record outside the arena");
+    if (const size_t k = std::min(cap, r[idx].len)) stage_download_sync(out, arena.in() + r[idx].start, k * sizeof(float), stream);
+}
+void StreamToPdu::fetch_ranks(size_t idx, float* low, float* high) {
+    const std::vector<rr_pdu_record>& r = fetch_records();
+    if (!midpoint) throw Error("rr_debug_pdu_ranks: the handle runs no Midpointer");
+    if (idx >= r.size() || idx >= slots.size()) throw Error("rr_debug_pdu_ranks: no such PDU in the most recent push");
+    float lh[2] = {0.0f, 0.0f};
+    stage_download_sync(lh, ranks.p + 2 * slots[idx], sizeof lh, stream);
+    *low = lh[0];
+    *high = lh[1];
+}
+void Wpcr::pack_dev(const float* d_syms, float* d_out, size_t out_cap, size_t* produced, size_t* pdu_start, size_t* pdu_len, size_t cap,
+                    size_t* npdus, hipStream_t s) {
+    const std::vector<WpcrResult>& r = fetch_results();
+    static_assert(sizeof(WpcrResult) == sizeof(rr_wpcr_result), "WpcrResult is rr_wpcr_result");
+    std::vector<rr_wpcr_result> res(r.size());
+    if (!r.empty()) std::memcpy(res.data(), r.data(), r.size() * sizeof(rr_wpcr_result));
+    size_t k = 0;
+    const size_t total = pdu_pack_plan(res, starts, hpack, pdu_start, pdu_len, cap, &k);
+    if (total > out_cap) throw Error("output shorter than the packed symbols");
+    *produced = total;
+    *npdus = k;
+    if (!total) return;
+    if (!d_syms || !d_out) throw Error("rr_wpcr_pack_dev: null argument");
+    pack_desc.reserve(hpack.size());
+    hstage().h2d(pack_desc.p, hpack.data(), hpack.size() * sizeof(long), s);
+    launch_pdu_pack(d_syms, pack_desc.p, (long)(hpack.size() / 3), (long)total, d_out, s);
+}
+
+// ---- Scrambler::g3ruh, NrziEncode and the HDLC framer (descrambler.rs:41-47, nrzi.rs:52-69, hdlc_framer.rs; kernels_frame.hip) ----------
+void LineState::init(int m, hipStream_t s) {
+    mode = m;
+    if (!mode) return;
+    std::vector<unsigned> h(LINE_NP * LINE_NS);
+    line_build_powers(mode, h.data());
+    pw.upload(h.data(), h.size(), s);
+    const unsigned zero = 0;                         // Lfsr::g3ruh's seed 0 (descrambler.rs:31), NrziEncode's out 0 (nrzi.rs:59-60)
+    st.upload(&zero, 1, s);
+}
+void LineState::run(const unsigned char* in, void* out, bool out_f32, float lo, float hi, size_t max_n, const unsigned long long* n_dev,
+                    hipStream_t s) {
+    if (!max_n) return;
+    const size_t ntiles = (max_n + LINE_T - 1) / LINE_T;
+    LineArgs a{};
+    a.in = in; a.out = out; a.out_f32 = out_f32 ? 1 : 0; a.lo = lo; a.hi = hi;
+    a.max_n = (long)max_n; a.n_dev = n_dev; a.mode = mode;
+    if (mode) {
+        z.reserve(ntiles);
+        carry.reserve(ntiles);
+        a.pw = pw.p; a.st_in = st.in(); a.st_out = st.out(); a.z = z.p; a.carry = carry.p;
+    }
+    launch_line(a, s);
+    if (mode) st.flip();
+}
+LineCoder::LineCoder(const char* nm, int mode) : SyncBlock(nm, 1, 1) {
+    line.init(mode, stream);
+    zero_copy_in = false;                            // (a tile is read twice: a page-locked host window is copied down first)
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void LineCoder::run(const void* in, void* out, size_t n, hipStream_t s) {
+    line.run(static_cast<const unsigned char*>(in), out, false, 0.0f, 0.0f, n, nullptr, s);
+}
+
+static_assert(sizeof(StuffSum) == 4 * sizeof(unsigned), "FrameArgs::sums: four words per tile");
+HdlcFramer::HdlcFramer(int fl, float l, float h)
+    : BatchBlock("FcsAdder>HdlcFramer>PduToStream", 1, fl & RR_FRAME_SYMBOLS ? 4 : 1,
+                 "HdlcFramer takes whole packets: rr_hdlc_framer_push / rr_hdlc_framer_push_dev"),
+      flags(fl), lo(l), hi(h) {
+    if (const char* e = frame_check_flags(fl)) throw Error(e);
+    line.init((fl & RR_FRAME_G3RUH ? LINE_SCR : 0) | (fl & RR_FRAME_NRZI ? LINE_NRZI : 0), stream);
+    total.reserve(1);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void HdlcFramer::push_dev(const unsigned char* d_bytes, size_t n_bytes, const size_t* st, const size_t* ln, size_t npackets, void* d_out,
+                          size_t out_cap, hipStream_t s) {
+    size_t bnd = 0;
+    if (const char* e = frame_check_push(flags, n_bytes, st, ln, npackets, out_cap, &bnd)) throw Error(e);
+    if (npackets && !d_out) throw Error("null output");
+    if (npackets && n_bytes && !d_bytes) throw Error("null input");
+    lens.assign(ln, ln + npackets);
+    bound = bnd;
+    records.clear();
+    produced = 0;
+    fetched = true;                                  // a push of no packets has no records and leaves every state alone
+    if (!npackets) return;
+    FramePlan pl;
+    frame_plan(flags, st, ln, npackets, FRAME_CH, pl);
+    const bool fcs = (flags & RR_FRAME_FCS) != 0, coded = line.mode != 0 || (flags & RR_FRAME_SYMBOLS) != 0;
+    FrameArgs a{};
+    a.P = (long)npackets;
+    a.nbytes = (long)pl.nbytes;
+    a.ntiles = (long)std::max<size_t>(1, (8 * pl.nbytes + FRAME_T - 1) / FRAME_T);
+    a.nchunks = (long)pl.nchunks;
+    a.fcs = fcs ? 1 : 0;
+    desc.reserve(pl.words.size());
+    if (fcs) { part.reserve(std::max<size_t>(pl.nchunks, 1)); crc.reserve(npackets); }
+    lb.reserve(std::max<size_t>(pl.nbytes, 1));
+    sums.reserve(4 * (size_t)a.ntiles);
+    tin.reserve(2 * (size_t)a.ntiles);
+    cb.reserve(npackets + 1);
+    if (coded) pre.reserve(bnd);
+    hstage().h2d(desc.p, pl.words.data(), pl.words.size() * sizeof(unsigned long long), s);      // (pl is free on return)
+    a.bytes = d_bytes;
+    a.starts = desc.p; a.pb = desc.p + npackets; a.cpre = desc.p + 2 * npackets + 1;
+    a.part = part.p; a.crc = crc.p; a.lb = lb.p; a.sums = sums.p; a.tin = tin.p; a.cb = cb.p; a.total = total.p;
+    a.pre = coded ? pre.p : static_cast<unsigned char*>(d_out);
+    a.cap = (long)bnd;
+    prof_begin(s);
+    launch_frame(a, s);
+    if (coded) line.run(pre.p, d_out, (flags & RR_FRAME_SYMBOLS) != 0, lo, hi, bnd, total.p, s);
+    prof_end(s);
+    fetched = false;
+}
+void HdlcFramer::push_host(const unsigned char* bytes, size_t n_bytes, const size_t* st, const size_t* ln, size_t npackets, void* out,
+                           size_t out_cap, size_t* prod) {
+    host_call([&] {
+        size_t bnd = 0;
+        if (const char* e = frame_check_push(flags, n_bytes, st, ln, npackets, out_cap, &bnd)) throw Error(e);
+        *prod = 0;
+        if (!npackets) { push_dev(nullptr, n_bytes, st, ln, 0, nullptr, out_cap, stream); return; }
+        h_in.reserve(std::max<size_t>(n_bytes, 1));
+        h_out.reserve(std::max<size_t>(bnd * out_es, 1));
+        if (n_bytes) hstage().h2d(h_in.p, bytes, n_bytes, stream);
+        push_dev(h_in.p, n_bytes, st, ln, npackets, h_out.p, bnd, stream);
+        fetch_records();                             // waits; `produced` is checked against the bound in there
+        if (produced) hstage().d2h(out, h_out.p, produced * out_es, stream);
+        *prod = produced;
+    });
+}
+const std::vector<rr_frame_record>& HdlcFramer::fetch_records() {
+    settle();
+    if (!fetched) {
+        const size_t P = lens.size();
+        std::vector<unsigned> hcb(P + 1), hcrc(flags & RR_FRAME_FCS ? P : 0);
+        unsigned long long tot = 0;
+        stage_download_sync(hcb.data(), cb.p, hcb.size() * sizeof(unsigned), stream);
+        if (!hcrc.empty()) stage_download_sync(hcrc.data(), crc.p, hcrc.size() * sizeof(unsigned), stream);
+        stage_download_sync(&tot, total.p, sizeof tot, stream);
+        if (const char* e = frame_records(flags, lens, hcb, hcrc, tot, bound, records, &produced)) throw Error(e);
+        fetched = true;
+    }
+    return records;
+}
+
+}  // namespace rr

@@ -1,0 +1,264 @@
+// blocks_packet.hpp — the packet-side blocks (blocks_packet.cpp) and the plumbing they share.  Part of blocks.hpp: include that.
+#pragma once
+#include "blocks.hpp"
+
+namespace rr {
+
+// What a block carries from call to call on the device, as a pair: a call reads in() and writes out(), then flip()s, so a call
+// that is still in flight on another stream never has its input overwritten.
+template <class T> struct Carried {
+    DevBuf<T> buf[2];
+    int cur = 0;
+    T* in() const { return buf[cur].p; }
+    T* out() const { return buf[cur ^ 1].p; }
+    void flip() { cur ^= 1; }
+    void reserve_out(size_t n) { buf[cur ^ 1].reserve(n); }
+    void zero(size_t n, hipStream_t s) { for (auto& b : buf) { b.reserve(n); RR_HIP(hipMemsetAsync(b.p, 0, n * sizeof(T), s)); } }
+    void upload(const T* h, size_t n, hipStream_t s) { for (auto& b : buf) b.upload(h, n, s); }
+};
+
+// The list a call left on the device, count first: refused with `msg` beyond `cap` entries.  list(k) says where the k > 0
+// entries are (BitDecoder packs them only once it knows k).
+template <class H, class F>
+void fetch_counted_at(const unsigned long long* d_count, F&& list, size_t cap, const char* msg, std::vector<H>& dst, hipStream_t s) {
+    unsigned long long k = 0;
+    stage_download_sync(&k, d_count, sizeof k, s);
+    if (k > cap) throw Error(msg);
+    dst.resize((size_t)k);
+    if (k) stage_download_sync(dst.data(), list((size_t)k), (size_t)k * sizeof(H), s);
+}
+template <class H, class D>
+void fetch_counted(const unsigned long long* d_count, const D* d_list, size_t cap, const char* msg, std::vector<H>& dst, hipStream_t s) {
+    static_assert(sizeof(D) == sizeof(H), "the device's entry is the host's");
+    fetch_counted_at(d_count, [&](size_t) { return d_list; }, cap, msg, dst, s);
+}
+
+// #[rustradio(sync)] blocks (rustradio_macros_code/src/lib.rs:458-515): map min(input, output space) samples,
+// then WaitForStream on the side that ran dry.
+struct SyncBlock : Block {
+    using Block::Block;
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) final;
+protected:
+    virtual void begin_call() {}          // every call, also one that moves nothing (the blocks that keep a per-call list drop it here)
+    virtual void run(const void* in, void* out, size_t n, hipStream_t s) = 0;     // n > 0, inside the profiling bracket
+};
+struct MultiplyConst : SyncBlock {        // multiply_const.rs:6-23, T = Float (es 4) or Complex (es 8)
+    float vr, vi;
+    MultiplyConst(size_t es, float re, float im);
+    void run(const void* in, void* out, size_t n, hipStream_t s) override;
+};
+struct FastFM : SyncBlock {           // quadrature_demod.rs:144-165; q2, q1 = the two previous samples (zeros at start)
+    Carried<cf> hist;
+    FastFM();
+    void run(const void* in, void* out, size_t n, hipStream_t s) override;
+};
+// Vco (vco.rs:9-37): Float -> Complex(sin phase, cos phase), phase += k * a in f64.  The running sum is a tiled scan
+// (kernels_tx.hip); the phase carried from call to call stays on the device — the host never reads it, counts depend on lengths only.
+struct VcoState {
+    double k;
+    Carried<double> phase;            // in(): the phase after the last sample of the previous call (0 at start)
+    DevBuf<double> tiles;             // scan scratch: one double per tile of the largest window so far
+    VcoState(double k, hipStream_t s);
+    double* scratch(size_t n) { tiles.reserve((n + VCO_T - 1) / VCO_T); return tiles.p; }
+};
+struct Vco : SyncBlock {
+    VcoState v;
+    explicit Vco(double k);
+    void run(const void* in, void* out, size_t n, hipStream_t s) override;
+};
+// RationalResampler::new(src, interp, deci) -> Vco::new(_, k) fused (examples/fm_tx.rs:84-91): f32 in, Complex out.  The window
+// protocol, `pending` and eof are the resampler's own code; the interpolated f32 stream exists only as the scan's index map.
+struct FmTx : Resampler {
+    VcoState v;
+    FmTx(size_t interp, size_t deci, double k);
+protected:
+    void emit(const void* in, void* out, int64_t r, int64_t n_gather, int64_t c0, hipStream_t s) override;
+};
+
+// ComplexToMag2 (complex_to_mag2.rs:8-21): Complex -> re * re + im * im, a sync block.  Bit-exact.
+struct ComplexToMag2 : SyncBlock {
+    ComplexToMag2();
+    void run(const void* in, void* out, size_t n, hipStream_t s) override;
+};
+// SinglePoleIirFilter (single_pole_iir_filter.rs:11-93): y = alpha x + fl32(1 - alpha) y_prev as a tiled f64 scan
+// (kernels_burst.hip).  y_prev stays on the device, one f64 per row (Complex: re, im); the host never reads it.
+struct IirState {
+    IirCoef c{};
+    DevBuf<double> pw8, pws;          // the powers of b the scan combines runs with
+    Carried<double> y;                // in(): y after the last sample of the previous call (0 at start)
+    int rows = 1;
+    DevBuf<double> tiles;             // scan scratch: one double per row and tile of the largest window so far
+    IirState(float alpha, int rows, hipStream_t s);    // throws "alpha out of range" unless 0 <= alpha <= 1
+    double* scratch(size_t n) { tiles.reserve((size_t)rows * ((n + IIR_T - 1) / IIR_T)); return tiles.p; }
+};
+struct SinglePoleIir : SyncBlock {
+    IirState st;
+    SinglePoleIir(float alpha, size_t es);
+    void run(const void* in, void* out, size_t n, hipStream_t s) override;
+};
+// ComplexToMag2 -> SinglePoleIirFilter(alpha) -> the comparison of BurstTagger(threshold) (burst_tagger.rs:68-85) fused
+// (examples/burst_saver.rs:111-123): Complex in, the filtered power out, and per call the list of threshold crossings.
+struct BurstDetector : SyncBlock {
+    IirState st;
+    float thr;
+    Carried<int> flag;                        // in(): out > threshold at the last sample of the previous call (false at start)
+    Carried<unsigned long long> count;        // in(): entries of the most recent call's list
+    DevBuf<unsigned long long> list;          // (pos << 1) | cur, unordered; one slot per sample of the largest window so far
+    bool fetched = true;                      // `edges` holds the most recent call's list
+    std::vector<unsigned long long> edges;    // ... ascending
+    BurstDetector(float alpha, float threshold);
+    void begin_call() override;
+    void run(const void* in, void* out, size_t n, hipStream_t s) override;
+    const std::vector<unsigned long long>& fetch_edges();   // waits for the most recent call
+};
+
+// The bit-level sync blocks (kernels_bits.hip): BinarySlicer (binary_slicer.rs:17-19), XorConst(1), NrziDecode
+// (nrzi.rs:36-41), Descrambler (descrambler.rs:34-39), CorrelateAccessCodeTag (correlate_access_code.rs:93-118) — any subset,
+// in that order, as ONE kernel.  f32 in (the slicer is then the first stage) or u8 in; u8 out.  The state between calls
+// (BITS_ST_*) stays on the device; the host reads only the tag list, and only when asked.
+struct BitDecoder : SyncBlock {
+    BitsCfg cfg{};
+    Carried<unsigned long long> st;           // in(): what the stream so far left behind
+    DevBuf<unsigned> tilecnt;                 // tags of every tile of the most recent call
+    DevBuf<unsigned long long> list;          // (pos << 8) | diffs: tile t's at [t BITS_T ..), BITS_T slots each; grows with the window
+    DevBuf<unsigned long long> offs, total, packed;   // rr_bit_tags: the entries before each tile, their sum, the list without gaps
+    size_t last_tiles = 0;                    // tiles of the most recent call
+    bool fetched = true;                      // `tags` holds the most recent call's list
+    std::vector<unsigned long long> tags;     // ... ascending
+    // f32src: the slicer in front.  code_len == 0: no correlator.  Throws on the parameter errors of bits_check().
+    BitDecoder(const char* nm, bool f32src, int flags, unsigned long long mask, unsigned long long seed, unsigned len,
+               unsigned long long code, unsigned code_len, size_t allowed_diffs);
+    bool has_correlator() const { return cfg.L != 0; }
+    void begin_call() override;
+    void run(const void* in, void* out, size_t n, hipStream_t s) override;
+    const std::vector<unsigned long long>& fetch_tags();    // waits for the most recent call
+};
+// nullptr, or what is wrong with the parameters (said before any device is touched)
+const char* bits_check(int flags, unsigned long long seed, unsigned len, unsigned code_len);
+
+// The handles with no stream protocol: work_dev only throws `no_stream`.
+struct BatchBlock : Block {
+    const char* no_stream;
+    BatchBlock(const char* nm, size_t ies, size_t oes, const char* sentence) : Block(nm, ies, oes), no_stream(sentence) {}
+    int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) final { throw Error(no_stream); }
+protected:
+    // a call on host buffers: the body runs on the handle's own stream and has completed on return
+    template <class F> void host_call(F&& body) {
+        RR_HIP(hipSetDevice(device));
+        last_stream = stream;
+        body();
+        RR_HIP(hipStreamSynchronize(stream));
+        hstage().quiesced();
+    }
+    void settle() { sync(); if (hstage_) hstage_->quiesced(); }      // in front of every fetch: the latest call has completed
+};
+
+// Wpcr (wpcr.rs:105-239) in PDU form over a batch of disjoint bursts of one f32 buffer (kernels_wpcr.hip): no stream protocol
+// (work_dev is an error), no state between calls.  The scratch buffers are as long as the largest sample buffer so far and a
+// burst owns the range of each that its samples have in the input; the host keeps only the geometry of the latest call.
+struct Wpcr : BatchBlock {
+    static constexpr size_t MAX_LEN = 512000;     // the reference's stream capacity in f32 samples (stream.rs:105)
+    float samp_rate;                              // NaN: not set
+    DevBuf<unsigned> list, tilecnt;               // crossing positions (burst-owned slots); crossings of every sample tile
+    DevBuf<float> mag, reim;                      // |X[k]| and Re X / Im X of every burst's bins
+    DevBuf<unsigned char> desc;                   // this call's WpcrBurst records and the two tile -> burst maps
+    DevBuf<WpcrResult> res;
+    DevBuf<float> h_in, h_out;                    // process(): the host buffers' device copies
+    std::vector<unsigned char> hdesc;
+    std::vector<size_t> starts, lens;             // the latest call's geometry
+    bool fetched = true;                          // `results` holds the latest call's records
+    std::vector<WpcrResult> results;
+    explicit Wpcr(float samp_rate);
+    // throws "bursts overlap" / "burst outside the buffer" / "burst longer than 512000 samples"; the process calls run it before
+    // anything is enqueued
+    static void check(size_t n_total, const size_t* st, const size_t* ln, size_t nbursts);
+    void process_dev(const float* d_x, size_t n_total, const size_t* st, const size_t* ln, const float* mid, size_t nbursts,
+                     float* d_syms, hipStream_t s);
+    void process_host(const float* x, size_t n_total, const size_t* st, const size_t* ln, const float* mid, size_t nbursts,
+                      float* syms);
+    const std::vector<WpcrResult>& fetch_results();          // waits for the latest call
+    std::vector<float> fetch_spectrum(size_t burst);         // ... and downloads mag[0 .. N / 2) of one of its bursts
+    // PduToStream over the latest call (rr_wpcr_pack_dev): waits for its results, then one gather launch on s
+    DevBuf<long> pack_desc;
+    std::vector<long> hpack;
+    void pack_dev(const float* d_syms, float* d_out, size_t out_cap, size_t* produced, size_t* pdu_start, size_t* pdu_len, size_t cap,
+                  size_t* npdus, hipStream_t s);
+};
+
+// BurstTagger -> StreamToPdu -> [Midpointer] over windows of an f32 data / trigger stream pair (kernels_pdu.hip): no stream
+// protocol (work_dev is an error).  The state between pushes (PduState) stays on the device; the two arenas alternate, and the
+// one of the previous push holds the samples of a burst that is still open, so they are the carry as well.
+struct StreamToPdu : BatchBlock {
+    static constexpr size_t MAX_WINDOW = 1024000;         // the f32 stream capacity in samples (stream.rs:105)
+    float thr;
+    size_t max_size, tail;
+    bool midpoint;
+    Carried<PduState> st;
+    Carried<float> arena;                         // in(): the arena of the most recent push that moved samples
+    size_t n_prev = 0, n_total = 0;               // its window; its length (0: no such push yet, or the latest push was empty)
+    unsigned long long w0 = 0;                    // samples of the stream so far
+    DevBuf<unsigned> tilecnt, edges, jmp[2], mark;
+    DevBuf<unsigned long long> offs, etotal, count;
+    DevBuf<PduRoot> root;
+    DevBuf<PduRec> recs;
+    DevBuf<float> ranks;                          // Midpointer's low and high per record slot (rr_debug_pdu_ranks)
+    DevBuf<float> h_data, h_trig;                 // push(): the host windows' device copies
+    size_t last_n = 0;                            // the most recent push's window
+    bool fetched = true, efetched = true;         // `records` / `edgelist` hold the most recent push's
+    std::vector<rr_pdu_record> records;           // ... ascending
+    std::vector<size_t> slots;                    // record i's place in the device's (unordered) list
+    std::vector<unsigned> edgelist;               // (pos << 1) | cur, ascending
+    StreamToPdu(float threshold, size_t max_size, size_t tail, int flags);
+    void push_dev(const float* d_data, const float* d_trig, size_t n, hipStream_t s);
+    void push_host(const float* data, const float* trig, size_t n);
+    const std::vector<rr_pdu_record>& fetch_records();      // waits for the most recent push
+    const std::vector<unsigned>& fetch_edges();
+    const float* arena_dev() const { return n_total ? arena.in() : nullptr; }
+    void fetch_pdu(size_t idx, float* out, size_t cap);
+    void fetch_ranks(size_t idx, float* low, float* high);  // the two elements Midpointer's offset of PDU idx was made of
+};
+
+// Scrambler::g3ruh (descrambler.rs:41-47, 95-123) and NrziEncode (nrzi.rs:52-69) as one affine system over GF(2)
+// (kernels_frame.hip, frame_core.hpp): what LineCoder (the two sync blocks) and HdlcFramer share.  The state word stays on the
+// device between calls; mode 0 has none.
+struct LineState {
+    int mode = 0;                             // LINE_SCR | LINE_NRZI
+    DevBuf<unsigned> pw;                      // the LINE_NP powers of the tile matrix
+    Carried<unsigned> st;                     // in(): what the stream so far left behind
+    DevBuf<unsigned> z, carry;                // one word per tile of the largest call so far
+    void init(int mode, hipStream_t s);
+    // n = *n_dev when given (at most max_n), else max_n
+    void run(const unsigned char* in, void* out, bool out_f32, float lo, float hi, size_t max_n, const unsigned long long* n_dev,
+             hipStream_t s);
+};
+struct LineCoder : SyncBlock {
+    LineState line;
+    LineCoder(const char* nm, int mode);
+    void run(const void* in, void* out, size_t n, hipStream_t s) override;
+};
+
+// FcsAdder -> HdlcFramer -> PduToStream<u8> -> [Scrambler::g3ruh] -> [NrziEncode] -> [Map] in PDU form over a batch of packets of
+// one byte buffer (kernels_frame.hip): no stream protocol (work_dev is an error).  The host keeps the geometry of the latest
+// push; what it reads back (frame_host.hpp) is sized from that geometry.
+struct HdlcFramer : BatchBlock {
+    int flags;
+    float lo, hi;
+    LineState line;
+    DevBuf<unsigned long long> desc, total;   // this push's starts / pb / cpre; the framed bits it made
+    DevBuf<unsigned> part, crc, sums, tin, cb;
+    DevBuf<unsigned char> lb, pre;            // the packets' bytes with their FCS; the framed bits in front of the line coder
+    DevBuf<unsigned char> h_in, h_out;        // push_host(): the host buffers' device copies
+    std::vector<size_t> lens;                 // the latest push's geometry
+    size_t bound = 0;
+    bool fetched = true;                      // `records` / `produced` hold the latest push's
+    std::vector<rr_frame_record> records;
+    size_t produced = 0;
+    HdlcFramer(int flags, float lo, float hi);
+    void push_dev(const unsigned char* d_bytes, size_t n_bytes, const size_t* starts, const size_t* lens, size_t npackets, void* d_out,
+                  size_t out_cap, hipStream_t s);
+    void push_host(const unsigned char* bytes, size_t n_bytes, const size_t* starts, const size_t* lens, size_t npackets, void* out,
+                   size_t out_cap, size_t* produced);
+    const std::vector<rr_frame_record>& fetch_records();      // waits for the latest push
+};
+
+}  // namespace rr

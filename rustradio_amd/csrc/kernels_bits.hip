@@ -13,6 +13,7 @@
 // the tile at the window's start takes them from the state the handle carries (the last r, the last 64 d, the last 64 s, the
 // count of bits seen).  No workgroup waits on another one and there is one launch per call.
 #include "kernels.hpp"
+#include "packet_common.hpp"
 
 namespace rr {
 
@@ -246,7 +247,7 @@ void launch_bits_tag_offsets(const unsigned* tilecnt, long ntiles, u64* offs, u6
     RR_HIP(hipGetLastError());
 }
 void launch_bits_tag_gather(const unsigned* tilecnt, const u64* offs, const u64* list, long ntiles, u64* out, hipStream_t s) {
-    const unsigned grid = (unsigned)std::max<long>(1, std::min(ntiles, (long)device_cu_count() * 8));
+    const unsigned grid = tiles_grid(ntiles);
     hipLaunchKernelGGL(k_bits_tag_gather, dim3(grid), dim3(BITS_B), 0, s, tilecnt, offs, list, ntiles, out);
     RR_HIP(hipGetLastError());
 }
@@ -256,7 +257,7 @@ static void bits_launch(const SRC* in, unsigned char* out, long n, const BitsCfg
                         u64* list, hipStream_t s) {
     if (n <= 0) return;
     const long ntiles = (n + BITS_T - 1) / BITS_T;
-    const unsigned grid = (unsigned)std::max<long>(1, std::min(ntiles, (long)device_cu_count() * 8));
+    const unsigned grid = tiles_grid(ntiles);
     const bool vin = reinterpret_cast<uintptr_t>(in) % 16 == 0, vout = reinterpret_cast<uintptr_t>(out) % 16 == 0;
 #define RR_BITS_GO(VI, VO) hipLaunchKernelGGL((k_bits<SRC, VI, VO>), dim3(grid), dim3(BITS_B), 0, s, in, out, n, c, st_in, st_out, tilecnt, list)
     if (vin && vout) RR_BITS_GO(true, true);

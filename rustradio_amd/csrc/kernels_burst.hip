@@ -18,6 +18,7 @@
 // All scan arithmetic is f64 fma; a x[n] is exact (24 x 24 bits).  Exclusive prefixes are built from the earlier elements
 // only, so a NaN sample reaches its own output and every later one and none before it.
 #include "kernels.hpp"
+#include "packet_common.hpp"
 
 namespace rr {
 
@@ -139,17 +140,8 @@ struct IirEdges {
     unsigned long long* count;                // entries of this call (zero on entry)
     unsigned long long* count_next;           // the counter of the NEXT call: zeroed here, on the call's stream
     unsigned long long* list;                 // one slot per sample of the window
+    unsigned long long cap;                   // ... so this many: never reached
 };
-// every thread of the wave calls it (one atomic per wave that has an edge at all); the list is unordered
-__device__ __forceinline__ void iir_edge_append(bool e, unsigned long long entry, unsigned long long* count, unsigned long long* list) {
-    const unsigned long long m = __ballot(e);
-    if (m == 0) return;
-    const int lane = threadIdx.x & 63, leader = __ffsll(m) - 1;
-    unsigned long long slot = 0;
-    if (lane == leader) slot = atomicAdd(count, (unsigned long long)__popcll(m));
-    slot = __shfl(slot, leader, 64);
-    if (e) list[slot + __popcll(m & ((1ull << lane) - 1ull))] = entry;
-}
 
 // SINGLE: the window is one tile — y_in[row] is the tile's incoming y.
 template <class SRC, bool SINGLE, bool EDGES>
@@ -198,7 +190,7 @@ __global__ __launch_bounds__(IIR_B) void k_iir_apply(SRC src, float* __restrict_
                 if (j == 0) { if (tile == 0) prev = ed.flag_in[0] != 0; else have = false; }
                 else if (in) prev = s_buf[(j - 1) + (j - 1) / IIR_PER] > ed.thr;
                 const bool cur = v > ed.thr;
-                iir_edge_append(have && cur != prev, ((unsigned long long)(o0 + j) << 1) | (cur ? 1ull : 0ull), ed.count, ed.list);
+                wave_append(have && cur != prev, ((unsigned long long)(o0 + j) << 1) | (cur ? 1ull : 0ull), ed.count, ed.list, ed.cap);
             }
         }
         __syncthreads();                      // the next tile overwrites s_buf
@@ -213,12 +205,7 @@ __global__ __launch_bounds__(IIR_B) void k_iir_seams(const float* __restrict__ o
         cur = out[t * IIR_T] > ed.thr;
         e = cur != (out[t * IIR_T - 1] > ed.thr);
     }
-    iir_edge_append(e, ((unsigned long long)(t * IIR_T) << 1) | (cur ? 1ull : 0ull), ed.count, ed.list);
-}
-
-static inline unsigned iir_grid(long ntiles) {
-    const long cap = (long)device_cu_count() * 8;
-    return (unsigned)std::max<long>(1, std::min(ntiles, cap));
+    wave_append(e, ((unsigned long long)(t * IIR_T) << 1) | (cur ? 1ull : 0ull), ed.count, ed.list, ed.cap);
 }
 
 template <class SRC, bool EDGES>
@@ -232,9 +219,9 @@ static void iir_launch(SRC src, float* out, long out_stride, long out_rs, int ro
         RR_HIP(hipGetLastError());
         return;
     }
-    hipLaunchKernelGGL((k_iir_sums<SRC>), dim3(iir_grid(ntiles - 1), rows), dim3(IIR_B), 0, s, src, n, c.a, c.b, c.pw8, tiles, ntiles);
+    hipLaunchKernelGGL((k_iir_sums<SRC>), dim3(tiles_grid(ntiles - 1), rows), dim3(IIR_B), 0, s, src, n, c.a, c.b, c.pw8, tiles, ntiles);
     hipLaunchKernelGGL(k_iir_scan, dim3(rows), dim3(IIR_SB), 0, s, tiles, ntiles, ntiles, c.pws, c.bT, y_in);
-    hipLaunchKernelGGL((k_iir_apply<SRC, false, EDGES>), dim3(iir_grid(ntiles), rows), dim3(IIR_B), 0, s, src, out, out_stride, out_rs, n,
+    hipLaunchKernelGGL((k_iir_apply<SRC, false, EDGES>), dim3(tiles_grid(ntiles), rows), dim3(IIR_B), 0, s, src, out, out_stride, out_rs, n,
                        c.a, c.b, c.pw8, (const double*)tiles, ntiles, y_in, y_out, ed);
     if (EDGES)
         hipLaunchKernelGGL(k_iir_seams, dim3((unsigned)((ntiles - 1 + IIR_B - 1) / IIR_B)), dim3(IIR_B), 0, s, (const float*)out, ntiles, ed);
@@ -257,7 +244,7 @@ void launch_burst_detector(const cf* in, float* out, long n, const IirCoef& c, c
                            float thr, const int* flag_in, int* flag_out, unsigned long long* count, unsigned long long* count_next,
                            unsigned long long* list, hipStream_t s) {
     iir_launch<IirSrcMag2, true>(IirSrcMag2{in, 0}, out, 1, 0, 1, n, c, y_in, y_out, tiles,
-                                 IirEdges{thr, flag_in, flag_out, count, count_next, list}, s);
+                                 IirEdges{thr, flag_in, flag_out, count, count_next, list, (unsigned long long)n}, s);
 }
 
 __global__ __launch_bounds__(256) void k_mag2(const cf* __restrict__ in, float* __restrict__ out, long n) {

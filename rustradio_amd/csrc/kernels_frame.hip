@@ -21,6 +21,7 @@
 // No workgroup waits on another, nothing is added to the output atomically, and every output element has one writer.
 #include "frame_core.hpp"
 #include "kernels.hpp"
+#include "packet_common.hpp"
 
 namespace rr {
 
@@ -236,14 +237,13 @@ __global__ __launch_bounds__(FR_B) void k_frame_emit(FrameArgs a) {
 
 void launch_frame(const FrameArgs& a, hipStream_t s) {
     if (a.P <= 0) return;
-    const long cus = std::max(1, device_cu_count());
     if (a.fcs) {
-        const unsigned gc = (unsigned)std::max<long>(1, std::min((a.nchunks + FR_B - 1) / FR_B, cus * 8));
+        const unsigned gc = tiles_grid((a.nchunks + FR_B - 1) / FR_B);
         hipLaunchKernelGGL(k_frame_crc_chunks, dim3(gc), dim3(FR_B), 0, s, a);
-        const unsigned gf = (unsigned)std::max<long>(1, std::min((a.P + FR_B / 64 - 1) / (FR_B / 64), cus * 8));
+        const unsigned gf = tiles_grid((a.P + FR_B / 64 - 1) / (FR_B / 64));
         hipLaunchKernelGGL(k_frame_crc_fold, dim3(gf), dim3(FR_B), 0, s, a);
     }
-    const unsigned gt = (unsigned)std::max<long>(1, std::min(a.ntiles, cus * 8));
+    const unsigned gt = tiles_grid(a.ntiles);
     hipLaunchKernelGGL(k_frame_sum, dim3(gt), dim3(FR_B), 0, s, a);
     hipLaunchKernelGGL(k_frame_scan, dim3(1), dim3(FR_SB), 0, s, a);
     hipLaunchKernelGGL(k_frame_emit, dim3(gt), dim3(FR_B), 0, s, a);
@@ -374,9 +374,8 @@ __global__ __launch_bounds__(FR_B) void k_line_emit(LineArgs a) {
 
 void launch_line(const LineArgs& a, hipStream_t s) {
     if (a.max_n <= 0) return;
-    const long cus = std::max(1, device_cu_count());
     const long ntiles = (a.max_n + LINE_T - 1) / LINE_T;
-    const unsigned grid = (unsigned)std::max<long>(1, std::min(ntiles, cus * 8));
+    const unsigned grid = tiles_grid(ntiles);
     if (a.mode) {
         hipLaunchKernelGGL(k_line_z, dim3(grid), dim3(FR_B), 0, s, a);
         hipLaunchKernelGGL(k_line_scan, dim3(1), dim3(FR_SB), 0, s, a);

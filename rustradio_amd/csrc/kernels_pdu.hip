@@ -21,6 +21,7 @@
 // No thread walks the edge list, no workgroup waits on another: the order is the stream's.  The host enqueues the same launches
 // whatever the trigger holds (it does not know the edge count): a launch whose round is beyond the window's chain returns at once.
 #include "kernels.hpp"
+#include "packet_common.hpp"
 
 namespace rr {
 
@@ -179,17 +180,6 @@ __global__ __launch_bounds__(PDU_B) void k_pdu_jump(const PduRoot* __restrict__ 
     }
 }
 
-// every thread of the wave calls it: one atomic per wave that has a record at all; the records are in no order
-__device__ __forceinline__ void pdu_append(bool e, const PduRec& rec, const PduArgs& a) {
-    const u64 m = __ballot(e);
-    if (m == 0) return;
-    const int lane = threadIdx.x & 63, leader = __ffsll(m) - 1;
-    u64 slot = 0;
-    if (lane == leader) slot = atomicAdd(a.count, (u64)__popcll(m));
-    slot = __shfl(slot, leader, 64);
-    slot += __popcll(m & ((1ull << lane) - 1ull));
-    if (e && slot < (u64)a.rec_cap) a.recs[slot] = rec;
-}
 __device__ __forceinline__ PduRec pdu_rec(const PduArgs& a, u64 r_abs, u64 len) {
     PduRec rec;
     rec.start = (u64)((long)(r_abs - a.w0) + a.C);                // (a burst begun earlier: a negative offset from the window)
@@ -251,7 +241,7 @@ __global__ __launch_bounds__(PDU_B) void k_pdu_emit(PduArgs a) {
                 a.st_out->free = fr; a.st_out->open_r = orr; a.st_out->open_f = of;
             }
         }
-        pdu_append(e, rec, a);
+        wave_append(e, rec, a.count, a.recs, (u64)a.rec_cap);
     }
 }
 
@@ -378,15 +368,14 @@ __global__ __launch_bounds__(PDU_MB) void k_pdu_midpoint(const float* __restrict
 
 void launch_pdu(const PduArgs& a, hipStream_t s) {
     if (a.n <= 0) return;
-    const long cus = std::max(1, device_cu_count());
     const long ntiles = (a.n + PDU_T - 1) / PDU_T;
-    const unsigned gt = (unsigned)std::max<long>(1, std::min(ntiles, cus * 8));
+    const unsigned gt = tiles_grid(ntiles);
     RR_HIP(hipMemsetAsync(a.count, 0, sizeof(u64), s));
     hipLaunchKernelGGL((k_pdu_tiles<false>), dim3(gt), dim3(PDU_B), 0, s, a);
     launch_bits_tag_offsets(a.tilecnt, ntiles, a.offs, a.etotal, s);
     hipLaunchKernelGGL((k_pdu_tiles<true>), dim3(gt), dim3(PDU_B), 0, s, a);
     const long maxr = a.n / 2 + 1;            // rising edges a window of n samples can hold
-    const unsigned gr = (unsigned)std::max<long>(1, std::min((maxr + PDU_B - 1) / PDU_B, cus * 8));
+    const unsigned gr = tiles_grid((maxr + PDU_B - 1) / PDU_B);
     hipLaunchKernelGGL(k_pdu_next, dim3(gr), dim3(PDU_B), 0, s, a);
     int k = 0;
     for (; (1L << k) < maxr; ++k)
@@ -394,7 +383,7 @@ void launch_pdu(const PduArgs& a, hipStream_t s) {
                            k & 1 ? a.jmp0 : a.jmp1, a.mark, k);
     hipLaunchKernelGGL(k_pdu_emit, dim3(gr), dim3(PDU_B), 0, s, a);
     if (a.midpoint) {
-        const unsigned gm = (unsigned)std::max<long>(1, std::min(a.rec_cap, cus * 2));
+        const unsigned gm = (unsigned)std::max<long>(1, std::min(a.rec_cap, (long)std::max(1, device_cu_count()) * 2));
         hipLaunchKernelGGL(k_pdu_midpoint, dim3(gm), dim3(PDU_MB), 0, s, (const float*)a.arena, a.recs, (const u64*)a.count, a.rec_cap,
                            a.ranks);
     }
@@ -415,8 +404,7 @@ __global__ __launch_bounds__(PDU_B) void k_pdu_pack(const float* __restrict__ sy
 }
 void launch_pdu_pack(const float* syms, const long* desc, long nb, long total, float* out, hipStream_t s) {
     if (total <= 0 || nb <= 0) return;
-    const long cus = std::max(1, device_cu_count());
-    const unsigned grid = (unsigned)std::max<long>(1, std::min((total + PDU_B - 1) / PDU_B, cus * 8));
+    const unsigned grid = tiles_grid((total + PDU_B - 1) / PDU_B);
     hipLaunchKernelGGL(k_pdu_pack, dim3(grid), dim3(PDU_B), 0, s, syms, desc, nb, total, out);
     RR_HIP(hipGetLastError());
 }

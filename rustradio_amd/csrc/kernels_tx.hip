@@ -15,6 +15,7 @@
 // own prefix sum and every later one NaN or +-Inf, whose sin and cos are NaN: the reference's behaviour with no pass for it.
 // Exclusive prefixes are built from the earlier elements only (never inclusive minus own), so the samples before stay clean.
 #include "kernels.hpp"
+#include "packet_common.hpp"
 
 namespace rr {
 
@@ -186,11 +187,6 @@ __global__ __launch_bounds__(VCO_B) void k_vco_apply(VcoSrc<FUSED> src, cf* __re
     }
 }
 
-static inline unsigned vco_grid(long ntiles) {
-    const long cap = (long)device_cu_count() * 8;
-    return (unsigned)std::max<long>(1, std::min(ntiles, cap));
-}
-
 template <bool FUSED>
 static void vco_launch(VcoSrc<FUSED> src, cf* out, long n, double k, const double* carry_in, double* carry_out, double* tiles,
                        hipStream_t s) {
@@ -201,7 +197,7 @@ static void vco_launch(VcoSrc<FUSED> src, cf* out, long n, double k, const doubl
         RR_HIP(hipGetLastError());
         return;
     }
-    const unsigned g = vco_grid(ntiles);
+    const unsigned g = tiles_grid(ntiles);
     hipLaunchKernelGGL((k_vco_sums<FUSED>), dim3(g), dim3(VCO_B), 0, s, src, n, k, tiles);
     hipLaunchKernelGGL(k_vco_scan, dim3(1), dim3(VCO_SB), 0, s, tiles, ntiles, carry_in, carry_out);
     hipLaunchKernelGGL((k_vco_apply<FUSED, false>), dim3(g), dim3(VCO_B), 0, s, src, out, n, k, (const double*)tiles, carry_out);

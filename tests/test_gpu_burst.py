@@ -408,6 +408,29 @@ def test_a_call_that_moves_nothing_keeps_the_flag():
     assert [(int(p), bool(v)) for p, v in zip(*det.edges())] == [(0, False)]
 
 
+def test_an_empty_call_between_two_windows_leaves_the_state_alone():
+    """two windows of one tile plus one sample (the tile seam and the carried flag both in play), crossings at sample 0, at the
+    seam and at the last sample; the first window ends above the threshold, so a flag read from the wrong half of its pair
+    (false, as at the start) would move the second window's edge at sample 0"""
+    hi, lo = np.complex64(0.25), np.complex64(0)
+    w1 = np.array([hi] + [lo] * (T - 1) + [hi])
+    w2 = np.array([lo] * T + [hi])
+    want = [[(0, True), (1, False), (T, True)], [(0, False), (T, True)]]
+    runs = []
+    for empty in (False, True):
+        det, got = make_det(0.5, 0.03), []
+        for i, w in enumerate((w1, w2)):
+            if empty and i == 1:
+                assert det.work(w[:0], 100)[:4] == sync_rule(0, 100)
+                assert len(det.edges()[0]) == 0
+            st, c, p, need, y = det.work(w, len(w))
+            assert (st, c, p, need) == sync_rule(len(w), len(w))
+            got.append((bits(y).tolist(), [(int(a), bool(b)) for a, b in zip(*det.edges())]))
+        runs.append(got)
+    assert runs[0] == runs[1]
+    assert [e for _, e in runs[1]] == want
+
+
 def test_names_sizes_and_tag_rules():
     p = C.c_size_t(0)
     for blk, name, ies, oes in ((rr.ComplexToMag2(), "ComplexToMag2", 8, 4), (rr.SinglePoleIirFilter(0.1), "SinglePoleIirFilter", 4, 4),

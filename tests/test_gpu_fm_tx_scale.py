@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T = 2048                              # VCO_T: samples of a scan tile
 SB, SPER = 1024, 4                    # VCO_SB, VCO_SPER: k_vco_scan's threads and tile sums per thread
 CH = SB * SPER                        # tile sums of one chunk of k_vco_scan
-PER_CU = 8                            # vco_grid: at most this many workgroups per CU
+PER_CU = 8                            # tiles_grid (packet_common.hpp): at most this many workgroups per CU
 K75 = 2.0 * math.pi * 75000 / 480000
 
 _HEAD, _TAIL1, _TAIL2 = 3 * T + 17, 700, T + 5     # the calls around the big window
@@ -29,7 +29,7 @@ _SEED = 31
 
 
 def grid_cap():
-    """vco_grid's cap: a window of more tiles than this sends workgroups round their loops again"""
+    """the cap of tiles_grid: a window of more tiles than this sends workgroups round their loops again"""
     return PER_CU * torch.cuda.get_device_properties(0).multi_processor_count
 
 
@@ -61,8 +61,10 @@ def test_constants_mirror_the_kernel():
     assert f"constexpr int VCO_T = {T};" in open(os.path.join(csrc, "kernels.hpp")).read()
     src = open(os.path.join(csrc, "kernels_tx.hip")).read()
     assert f"constexpr int VCO_SB = {SB}, VCO_SPER = {SPER}, VCO_SCHUNK = VCO_SB * VCO_SPER;" in src
-    grid = src[src.index("static inline unsigned vco_grid("):]
-    assert re.search(r"cap = \(long\)device_cu_count\(\) \* %d;" % PER_CU, grid[:grid.index("}")])
+    assert "const unsigned g = tiles_grid(ntiles);" in src                         # ... of packet_common.hpp:
+    grid = open(os.path.join(csrc, "packet_common.hpp")).read()
+    grid = grid[grid.index("static inline unsigned tiles_grid("):]
+    assert re.search(r"std::min\(ntiles, \(long\)device_cu_count\(\) \* %d\)" % PER_CU, grid[:grid.index("}")])
     assert "for (long c0 = 0; c0 < ntiles; c0 += VCO_SCHUNK)" in src
     assert src.count("tile < ntiles; tile += gridDim.x") == 2
 

@@ -380,3 +380,34 @@ def test_process_pdus_without_midpoint_and_after_an_empty_push():
     assert len(w.results()) == 0 and w.pack(0, 0, 0)[0] == 0
     with pytest.raises(RuntimeError, match="not a stream_to_pdu handle"):
         w.process_pdus(w, 0)
+
+
+@pytest.mark.parametrize("refused,message", [
+    (lambda L: L.rr_stream_to_pdu_create(0.5, 512001, 0, 0), "max_size beyond 512000 samples"),
+    (lambda L: L.rr_hdlc_framer_create(1 << 20, 0.0, 1.0), "unknown hdlc framer flags"),
+])
+def test_a_refused_create_does_not_leak_the_pending_options(refused, message):
+    """rr_next_create_options belongs to ONE create call, also one that refuses before any device is touched.  On the raw
+    library: the create proxy of the package arms the options again in front of every create and would hide a leak."""
+    import ctypes as C
+    from rustradio_amd._lib import BuildOpts, lib as raw_lib
+    L = raw_lib()
+    taps = np.hanning(301).astype(np.complex64)                    # non-decimating, a few hundred taps
+
+    def fft_tile():
+        h = L.rr_fir_c32_create(taps.ctypes.data_as(C.c_void_p), len(taps), 1, 0, 0.0, 0.0)
+        assert h, rr.last_error()
+        tile = L.rr_fir_fft_tile(h)
+        L.rr_block_destroy(h)
+        return tile
+
+    assert L.rr_next_create_options(None) == 0
+    assert fft_tile() > 0                                          # the default at this length: FFT tiles
+    o = BuildOpts()
+    o.fir_path = 1                                                 # RR_PATH_DIRECT
+    assert L.rr_next_create_options(C.byref(o)) == 0
+    assert fft_tile() == 0                                         # (the override does reach a create)
+    assert fft_tile() > 0                                          # ... and only one
+    assert L.rr_next_create_options(C.byref(o)) == 0
+    assert not refused(L) and rr.last_error() == message
+    assert fft_tile() > 0
