@@ -511,6 +511,58 @@ int rr_hdlc_framer_records(rr_block *b, rr_frame_record *rec, size_t cap, size_t
  * seams with it). */
 int rr_hdlc_framer_dims(const rr_block *b, size_t *tile_bits);
 
+/* HdlcDeframer::new(src, min_size, max_size) (src/hdlc_deframer.rs:80-101) with set_keep_checksum (:119-121) and set_fix_bits
+ * (:114-116) as flags: line bits in, checked frames out, the last block of the packet receivers (examples/ax25-9600-rx.rs,
+ * ax25-1200-rx.rs, bell202.rs, g3ruh.rs).  A batch block like rr_stream_to_pdu: rr_block_work on the handle is an error.  A push
+ * takes the next n bits of the stream, one per u8 (its lowest bit: what rr_bit_decoder writes), and finds the frames whose closing
+ * flag ends inside them, bit-identical to the reference's machine (update_state, :123-232) whatever the split into pushes:
+ *   the flag needs 8 bits of the stream (Unsynced(0xff) at the start and after every reset, :130-138, 145, 169, 173);
+ *   more than 8 max_size collected bits reset the machine before the next bit is looked at (:144-146), so a frame of exactly
+ *     max_size bytes is dropped; seven ones reset it (:167-170); two flags sharing their 0 collect fewer than 7 bits and reset it
+ *     at the second flag's end (:171-174);
+ *   a frame is the destuffed bits without the closing flag's first 7, LSB first, if they are a whole number of at least min_size
+ *     bytes (:176-191); with RR_HDLC_KEEP_CHECKSUM every such frame is delivered as it is (:194-197);
+ *   without it frames of fewer than 2 bytes vanish (:199-202), the last 2 bytes are the CRC-16/X.25 (calc_crc, :309-315) of the
+ *     rest and are stripped; a wrong one counts in crc_error (:214-218) unless RR_HDLC_FIX_BITS repairs it: find_right_crc
+ *     (:41-71) flips one data bit, lowest byte and bit first, and delivers the repaired frame (flags bit 0, bitfixed); a single
+ *     wrong bit in the CRC field itself counts in bitfixed AND crc_error and delivers nothing.
+ * The state between pushes — the machine at the last flag end, the raw bits of the gap still open (at most carry_bits of
+ * rr_hdlc_deframer_dims) and the three counters — stays on the device; the host never reads it to decide a size.  The reference's
+ * output_space back-pressure (:237-253) has no counterpart: a push delivers every frame of its bits.
+ * NULL + rr_last_error, said before any device is touched: "unknown hdlc deframer flags", "hdlc deframer: max_size beyond 65535".
+ * min_size 0 and max_size 0 are legal, as in the reference. */
+enum { RR_HDLC_KEEP_CHECKSUM = 1, RR_HDLC_FIX_BITS = 2 };       /* set_keep_checksum / set_fix_bits */
+typedef struct {
+    unsigned long long pos;    /* the "packet_pos" tag (:193): stream position of the closing flag's last bit */
+    unsigned long long start;  /* first byte of the frame in the byte arena of this push */
+    unsigned len;              /* bytes delivered (FCS stripped unless RR_HDLC_KEEP_CHECKSUM) */
+    unsigned flags;            /* bit 0: a data bit was repaired */
+} rr_hdlc_frame;               /* 24 bytes */
+rr_block *rr_hdlc_deframer_create(size_t min_size, size_t max_size, int flags);
+/* The next n bits of the stream from the device buffer d_bits.  RR_ERR before any device is touched: "hdlc deframer: more than
+ * 2^30 bits in one push", "hdlc deframer: null bits" (n > 0 with a null buffer).  Enqueued on hip_stream (used as given) and
+ * returns without waiting; seven launches whose grids depend on n and max_size alone, never on what the bits hold.  n == 0
+ * launches nothing, has no frames and leaves every state alone. */
+int rr_hdlc_deframer_push_dev(rr_block *b, const void *d_bits, size_t n, void *hip_stream);
+/* The same with a host pointer: copies the bits down, runs and waits. */
+int rr_hdlc_deframer_push(rr_block *b, const unsigned char *bits, size_t n);
+/* The frames that ended inside the most recent push, ascending by pos.  Waits for that push, writes the first min(*total, cap)
+ * records; rec == NULL with cap == 0 only counts (the contract of rr_wpcr_results).  Everything the device wrote is checked
+ * against the bounds of the push before it is used ("hdlc deframer: ..." and no frames otherwise). */
+int rr_hdlc_frames(rr_block *b, rr_hdlc_frame *rec, size_t cap, size_t *total);
+/* The byte arena of the most recent push, which rec.start indexes: *total bytes, the first min(*total, cap) copied.  Bytes that
+ * belong to no frame are 0. */
+int rr_hdlc_frame_bytes(rr_block *b, unsigned char *out, size_t cap, size_t *total);
+/* The same arena on the device for a consumer there (ordered behind the push on its stream); valid until the next push.
+ * NULL and *n_total = 0 when the most recent push was empty. */
+const void *rr_hdlc_bytes_dev(rr_block *b, size_t *n_total);
+/* decoded, crc_error, bitfixed (:92-96) of the handle so far.  Waits for the most recent push. */
+int rr_hdlc_stats(rr_block *b, unsigned long long *decoded, unsigned long long *crc_error, unsigned long long *bitfixed);
+/* *tile_bits = the bits of one tile of the marking kernels (the first tile of a push begins *carried* bits in front of the push's
+ * first bit, so tests aim at the seams through a push of a handle that carries the 8 bits of a fresh stream); *carry_bits = the
+ * most bits a handle carries from push to push: M + floor((M - 1) / 5) + 16, M = 8 max_size + 1. */
+int rr_hdlc_deframer_dims(const rr_block *b, size_t *tile_bits, size_t *carry_bits);
+
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)
  * as wired in examples/ax25-1200-rx.rs:238-247: f32 in, Complex out, ONE decimating FIR with the composite

@@ -92,6 +92,19 @@ unsafe extern "C" {
                                npackets: usize, d_out: *mut c_void, out_cap: usize, hip_stream: *mut c_void) -> c_int;
     #[allow(dead_code)]
     fn rr_hdlc_framer_dims(b: *const RrBlock, tile_bits: *mut usize) -> c_int;
+    // (declared for completeness: HdlcDeframer takes a ReadStream<u8> and feeds an NCWriteStream<Vec<u8>> with the `packet_pos` tag;
+    //  its typed block needs rr_hdlc_frames (a struct) and rr_hdlc_frame_bytes / rr_hdlc_deframer_push (byte pointers) too, types outside
+    //  this file's FFI map; not written yet)
+    #[allow(dead_code)]
+    fn rr_hdlc_deframer_create(min_size: usize, max_size: usize, flags: c_int) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_hdlc_deframer_push_dev(b: *mut RrBlock, d_bits: *const c_void, n: usize, hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_hdlc_bytes_dev(b: *mut RrBlock, n_total: *mut usize) -> *const c_void;
+    #[allow(dead_code)]
+    fn rr_hdlc_stats(b: *mut RrBlock, decoded: *mut u64, crc_error: *mut u64, bitfixed: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn rr_hdlc_deframer_dims(b: *const RrBlock, tile_bits: *mut usize, carry_bits: *mut usize) -> c_int;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;

@@ -749,6 +749,68 @@ class HdlcFramer(Block):
         return rec, produced.value
 
 
+HDLC_KEEP_CHECKSUM, HDLC_FIX_BITS = 1, 2      # RR_HDLC_*
+# rr_hdlc_frame
+HDLC_FRAME = np.dtype([("pos", np.uint64), ("start", np.uint64), ("len", np.uint32), ("flags", np.uint32)], align=True)
+
+
+class HdlcDeframer(Block):
+    """HdlcDeframer::new(src, min_size, max_size) with set_keep_checksum / set_fix_bits as flags behind one handle
+    (rr_hdlc_deframer_create; src/hdlc_deframer.rs:80-232; not a stream block: work() raises): the next bits of a stream in, one
+    per u8, the frames whose closing flag ends inside them out.  The machine, the open gap's bits and the counters stay on the
+    device between pushes.  See include/rustradio_amd.h."""
+
+    def __init__(self, min_size: int, max_size: int, flags: int = 0):
+        super().__init__(lib().rr_hdlc_deframer_create(int(min_size), int(max_size), int(flags)), np.uint8, np.uint8)
+        self.min_size, self.max_size, self.flags = int(min_size), int(max_size), int(flags)
+
+    def dims(self):
+        """-> (tile_bits, carry_bits) (rr_hdlc_deframer_dims)"""
+        t, c = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_hdlc_deframer_dims(self._h, C.byref(t), C.byref(c)) != 0:
+            raise RuntimeError(last_error())
+        return t.value, c.value
+
+    def push_dev(self, d_bits: int, n: int, stream: int = 0) -> None:
+        """rr_hdlc_deframer_push_dev: the next n bits from a raw device pointer; asynchronous on `stream`; frames() waits"""
+        if lib().rr_hdlc_deframer_push_dev(self._h, C.c_void_p(d_bits), int(n), C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+
+    def push(self, bits):
+        """rr_hdlc_deframer_push on host bits -> [(pos, bytes, fixed)] of the frames that ended inside them"""
+        x = np.ascontiguousarray(bits, np.uint8).ravel()
+        if lib().rr_hdlc_deframer_push(self._h, _ptr(x) if len(x) else None, len(x)) != 0:
+            raise ValueError(last_error())
+        return self.result()
+
+    def frames(self) -> np.ndarray:
+        """-> HDLC_FRAME per frame of the most recent push, ascending by pos (rr_hdlc_frames; waits)"""
+        return _fetch(lib().rr_hdlc_frames, self._h, HDLC_FRAME)[0]
+
+    def frame_bytes(self) -> np.ndarray:
+        """-> the byte arena of the most recent push, which frames()["start"] indexes (rr_hdlc_frame_bytes; waits)"""
+        return _fetch(lib().rr_hdlc_frame_bytes, self._h, np.uint8)[0]
+
+    def bytes_dev(self):
+        """-> (raw device pointer or None, bytes) of the same arena (rr_hdlc_bytes_dev); valid until the next push"""
+        n = C.c_size_t(0)
+        p = lib().rr_hdlc_bytes_dev(self._h, C.byref(n))
+        return p, n.value
+
+    def result(self):
+        """frames() and frame_bytes() of the most recent push as [(pos, bytes, fixed)]"""
+        rec = self.frames()
+        arena = self.frame_bytes() if len(rec) else np.zeros(0, np.uint8)
+        return [(int(r["pos"]), arena[int(r["start"]):int(r["start"]) + int(r["len"])].tobytes(), bool(r["flags"] & 1)) for r in rec]
+
+    def stats(self):
+        """-> (decoded, crc_error, bitfixed) of the handle so far (rr_hdlc_stats; waits)"""
+        d, e, f = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        if lib().rr_hdlc_stats(self._h, C.byref(d), C.byref(e), C.byref(f)) != 0:
+            raise RuntimeError(last_error())
+        return d.value, e.value, f.value
+
+
 WPCR_MAX_LEN = 512_000      # samples of one burst: the reference's stream capacity in f32
 # rr_wpcr_result
 WPCR_RESULT = np.dtype([("ok", np.int32), ("bin", np.uint32), ("sps", np.float32), ("phase0", np.float32), ("phase", np.float32),

@@ -12,6 +12,7 @@
 #include "dstream.hpp"
 #include "frame_core.hpp"
 #include "frame_host.hpp"
+#include "hdlc_host.hpp"
 #include "pdu_host.hpp"
 #include "taps.hpp"
 
@@ -79,6 +80,7 @@ template <class T> static T* as(const rr_block* b, const char* what, const char*
     return p;
 }
 static const char NOT_WPCR[] = "not a wpcr handle", NOT_PDU[] = "not a stream_to_pdu handle", NOT_FRAMER[] = "not an hdlc framer handle";
+static const char NOT_DEFRAMER[] = "not an hdlc deframer handle";
 // a fetched list of (pos << shift) | val entries into the caller's two arrays
 template <class E> static void unpack(const std::vector<E>& e, unsigned shift, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
     *total = e.size();
@@ -432,6 +434,58 @@ int rr_hdlc_framer_dims(const rr_block* b, size_t* tile_bits) {
     if (!f || !tile_bits) { if (f) rr::set_last_error("rr_hdlc_framer_dims: null argument"); return RR_ERR; }
     static_assert(rr::FRAME_T == rr::LINE_T, "one tile length for the stuffing scan and the line coder");
     *tile_bits = rr::FRAME_T;
+    return 0;
+}
+rr_block* rr_hdlc_deframer_create(size_t min_size, size_t max_size, int flags) {
+    if (const char* e = rr::hdlc_check_create(min_size, max_size, flags)) return refuse_create(e);
+    return make_block([&] { return new rr::HdlcDeframer(min_size, max_size, flags); });
+}
+int rr_hdlc_deframer_push_dev(rr_block* b, const void* d_bits, size_t n, void* hip_stream) {
+    auto* d = as<rr::HdlcDeframer>(b, "rr_hdlc_deframer_push_dev", NOT_DEFRAMER);
+    if (!d) return RR_ERR;
+    if (const char* e = rr::hdlc_check_push(d_bits, n)) { rr::set_last_error(e); return RR_ERR; }     // before any device is touched
+    return on_device(d, hip_stream, [&](hipStream_t s) { d->push_dev(static_cast<const unsigned char*>(d_bits), n, s); });
+}
+int rr_hdlc_deframer_push(rr_block* b, const unsigned char* bits, size_t n) {
+    auto* d = as<rr::HdlcDeframer>(b, "rr_hdlc_deframer_push", NOT_DEFRAMER);
+    if (!d) return RR_ERR;
+    if (const char* e = rr::hdlc_check_push(bits, n)) { rr::set_last_error(e); return RR_ERR; }
+    return guarded([&] { d->push_host(bits, n); });
+}
+int rr_hdlc_frames(rr_block* b, rr_hdlc_frame* rec, size_t cap, size_t* total) {
+    auto* d = as<rr::HdlcDeframer>(b, "rr_hdlc_frames", NOT_DEFRAMER);
+    if (!d) return RR_ERR;
+    if (!total || (cap && !rec)) { rr::set_last_error("rr_hdlc_frames: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] { rr::hdlc_copy_frames(d->fetch_frames(), rec, cap, total); });
+}
+int rr_hdlc_frame_bytes(rr_block* b, unsigned char* out, size_t cap, size_t* total) {
+    auto* d = as<rr::HdlcDeframer>(b, "rr_hdlc_frame_bytes", NOT_DEFRAMER);
+    if (!d) return RR_ERR;
+    if (!total || (cap && !out)) { rr::set_last_error("rr_hdlc_frame_bytes: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] { rr::hdlc_copy_bytes(d->fetch_bytes(), out, cap, total); });
+}
+const void* rr_hdlc_bytes_dev(rr_block* b, size_t* n_total) {
+    auto* d = as<rr::HdlcDeframer>(b, "rr_hdlc_bytes_dev", NOT_DEFRAMER);
+    if (n_total) *n_total = d ? d->arena_len() : 0;
+    return d && d->arena_len() ? d->arena_dev() : nullptr;
+}
+int rr_hdlc_stats(rr_block* b, unsigned long long* decoded, unsigned long long* crc_error, unsigned long long* bitfixed) {
+    auto* d = as<rr::HdlcDeframer>(b, "rr_hdlc_stats", NOT_DEFRAMER);
+    if (!d) return RR_ERR;
+    if (!decoded || !crc_error || !bitfixed) { rr::set_last_error("rr_hdlc_stats: null argument"); return RR_ERR; }
+    return on_device(d, [&] {
+        unsigned long long s[3] = {0, 0, 0};
+        d->fetch_stats(s);
+        *decoded = s[0]; *crc_error = s[1]; *bitfixed = s[2];
+    });
+}
+int rr_hdlc_deframer_dims(const rr_block* b, size_t* tile_bits, size_t* carry_bits) {
+    auto* d = as<rr::HdlcDeframer>(b, "rr_hdlc_deframer_dims", NOT_DEFRAMER);
+    if (!d || !tile_bits || !carry_bits) { if (d) rr::set_last_error("rr_hdlc_deframer_dims: null argument"); return RR_ERR; }
+    *tile_bits = rr::HDLC_T;
+    *carry_bits = rr::hdlc_carry_bits(d->max_size);
     return 0;
 }
 rr_block* rr_rtlsdr_decode_create(void) {

@@ -1,5 +1,5 @@
 // blocks_packet.cpp — host side of the packet-side blocks (blocks_packet.hpp): the sync blocks, the burst and bit blocks, and the
-// batch handles (Wpcr, StreamToPdu, HdlcFramer).  Citations are to the reference's src, as in blocks.cpp.
+// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer).  Citations are to the reference's src, as in blocks.cpp.
 #include "blocks_packet.hpp"
 
 #include <algorithm>
@@ -9,6 +9,7 @@
 
 #include "frame_core.hpp"
 #include "frame_host.hpp"
+#include "hdlc_host.hpp"
 #include "pdu_host.hpp"
 
 namespace rr {
@@ -532,6 +533,109 @@ const std::vector<rr_frame_record>& HdlcFramer::fetch_records() {
         fetched = true;
     }
     return records;
+}
+
+// ---- HdlcDeframer (hdlc_deframer.rs:80-232; kernels_hdlc.hip) -----------------------------------------------------------------------
+static_assert(sizeof(HdlcRec) == sizeof(rr_hdlc_frame) && offsetof(HdlcRec, pos) == offsetof(rr_hdlc_frame, pos) &&
+              offsetof(HdlcRec, start) == offsetof(rr_hdlc_frame, start) && offsetof(HdlcRec, len) == offsetof(rr_hdlc_frame, len) &&
+              offsetof(HdlcRec, flags) == offsetof(rr_hdlc_frame, flags), "HdlcRec is rr_hdlc_frame");
+HdlcDeframer::HdlcDeframer(size_t mn, size_t mx, int fl)
+    : BatchBlock("HdlcDeframer", 1, 1, "HdlcDeframer delivers frames: rr_hdlc_deframer_push / rr_hdlc_deframer_push_dev"),
+      min_size(mn), max_size(mx), flags(fl) {
+    if (const char* e = hdlc_check_create(mn, mx, fl)) throw Error(e);
+    // Unsynced(0xff) (hdlc_deframer.rs:28-32): 8 ones nobody asks about in front of the stream, and every flag is seen whole
+    HdlcState init{};
+    init.count = HDLC_HALO;
+    init.state = HDLC_U;
+    st.upload(&init, 1, stream);
+    const std::vector<unsigned char> ones(hdlc_carry_bits(mx), 1);
+    cbits.upload(ones.data(), ones.size(), stream);
+    carry = HDLC_HALO;
+    scal.reserve(5);
+    fin.reserve(1);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void HdlcDeframer::push_dev(const unsigned char* d_bits, size_t n, hipStream_t s) {
+    if (const char* e = hdlc_check_push(d_bits, n)) throw Error(e);
+    frames.clear();
+    bytes.clear();
+    fetched = bfetched = true;                 // a push of no bits has no frames and leaves every state alone
+    last_n = n;
+    last_w0 = w0;
+    if (!n) return;
+    const HdlcBounds bd = hdlc_bounds(carry, n);
+    b_nv = bd.nv; b_frames = bd.frames; b_arena = bd.arena;
+    HdlcArgs a{};
+    a.bits = d_bits; a.n = (long)n;
+    a.cin = cbits.in(); a.cout = cbits.out(); a.st_in = st.in(); a.st_out = st.out();
+    a.carry_cap = (long)hdlc_carry_bits(max_size);
+    a.nv_max = (long)bd.nv;
+    a.ntiles = (long)((bd.nv + HDLC_T - 1) / HDLC_T);
+    a.w0 = w0; a.min_size = min_size; a.max_size = max_size;
+    a.keep = (flags & RR_HDLC_KEEP_CHECKSUM) != 0; a.fix = (flags & RR_HDLC_FIX_BITS) != 0;
+    const size_t nwords = (size_t)a.ntiles * (HDLC_T / 64) + 1, ecap = bd.nv / 7 + 2, nblocks = (ecap + HDLC_GB - 1) / HDLC_GB;
+    raw.reserve(nwords); fl.reserve(nwords); ab.reserve(nwords); sf.reserve(nwords);
+    tilecnt.reserve((size_t)a.ntiles); offs.reserve((size_t)a.ntiles);
+    ends.reserve(ecap); gmap.reserve(ecap); pmap.reserve(ecap); bmap.reserve(nblocks); bstate.reserve(nblocks);
+    arena.reserve(std::max<size_t>(bd.arena, 1));
+    recs.reserve(std::max<size_t>(bd.frames, 1));
+    a.raw = raw.p; a.fl = fl.p; a.ab = ab.p; a.sf = sf.p; a.tilecnt = tilecnt.p; a.offs = offs.p;
+    a.etotal = scal.p; a.count = scal.p + 1; a.pstats = scal.p + 2;
+    a.ends = ends.p; a.ends_cap = (long)ecap; a.gmap = gmap.p; a.pmap = pmap.p; a.bmap = bmap.p; a.bstate = bstate.p; a.fin = fin.p;
+    a.arena = arena.p; a.arena_cap = (long)bd.arena; a.recs = recs.p; a.rec_cap = (long)bd.frames;
+    prof_begin(s);
+    if (bd.arena) RR_HIP(hipMemsetAsync(arena.p, 0, bd.arena, s));
+    launch_hdlc(a, s);
+    prof_end(s);
+    st.flip();
+    cbits.flip();
+    carry = hdlc_next_carry(carry, n, max_size);
+    w0 += n;
+    fetched = bfetched = false;
+}
+void HdlcDeframer::push_host(const unsigned char* bits, size_t n) {
+    host_call([&] {
+        if (const char* e = hdlc_check_push(bits, n)) throw Error(e);
+        if (n) {
+            h_bits.reserve(n);
+            hstage().h2d(h_bits.p, bits, n, stream);
+        }
+        push_dev(h_bits.p, n, stream);
+    });
+}
+const std::vector<rr_hdlc_frame>& HdlcDeframer::fetch_frames() {
+    settle();
+    if (!fetched) {
+        fetched = true;                        // (a refused push has no frames: the refusal is not repeated)
+        HdlcBounds bd;
+        bd.nv = b_nv; bd.frames = b_frames; bd.arena = b_arena;
+        unsigned long long k = 0;
+        stage_download_sync(&k, scal.p + 1, sizeof k, stream);
+        if (const char* e = hdlc_check_count(k, bd)) throw Error(e);
+        std::vector<rr_hdlc_frame> r((size_t)k);
+        if (k) stage_download_sync(r.data(), recs.p, (size_t)k * sizeof(rr_hdlc_frame), stream);
+        HdlcState now{}, before{};
+        stage_download_sync(&now, st.in(), sizeof now, stream);
+        stage_download_sync(&before, st.out(), sizeof before, stream);       // (the pair's other half: the state the push started from)
+        if (const char* e = hdlc_validate(r, bd, max_size, last_w0, last_n, before.stats, now.stats)) throw Error(e);
+        frames.swap(r);
+    }
+    return frames;
+}
+const std::vector<unsigned char>& HdlcDeframer::fetch_bytes() {
+    fetch_frames();                            // (waits; the arena is read only behind a push whose records stood the checks)
+    if (!bfetched) {
+        bytes.assign(b_arena, 0);
+        if (b_arena) stage_download_sync(bytes.data(), arena.p, b_arena, stream);
+        bfetched = true;
+    }
+    return bytes;
+}
+void HdlcDeframer::fetch_stats(unsigned long long out[3]) {
+    settle();
+    HdlcState now{};
+    stage_download_sync(&now, st.in(), sizeof now, stream);
+    for (int k = 0; k < 3; k++) out[k] = now.stats[k];
 }
 
 }  // namespace rr

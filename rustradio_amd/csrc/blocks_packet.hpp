@@ -261,4 +261,37 @@ struct HdlcFramer : BatchBlock {
     const std::vector<rr_frame_record>& fetch_records();      // waits for the latest push
 };
 
+// HdlcDeframer (hdlc_deframer.rs:80-232) over windows of a bit stream (kernels_hdlc.hip): no stream protocol (work_dev is an
+// error).  The state between pushes — the machine at the last flag end, the raw bits of the gap still open, the counters — stays
+// on the device; the host keeps the stream position and an upper bound of the carried bits, and sizes everything it reads back
+// from those (hdlc_host.hpp).
+struct HdlcDeframer : BatchBlock {
+    size_t min_size, max_size;
+    int flags;
+    Carried<HdlcState> st;                        // in(): what the stream so far left behind
+    Carried<unsigned char> cbits;                 // ... and its carried bits, one per byte
+    size_t carry = 0;                             // the carried bits, at most
+    unsigned long long w0 = 0;                    // bits of the stream so far
+    DevBuf<unsigned long long> raw, fl, ab, sf, offs, scal;      // scal: etotal, count, pstats[3]
+    DevBuf<unsigned> tilecnt, ends;
+    DevBuf<unsigned char> gmap, pmap, bmap, bstate, arena;
+    DevBuf<int> fin;
+    DevBuf<HdlcRec> recs;
+    DevBuf<unsigned char> h_bits;                 // push_host(): the host window's device copy
+    size_t last_n = 0;                            // the most recent push: its bits, where they began, its bounds
+    unsigned long long last_w0 = 0;
+    size_t b_nv = 0, b_frames = 0, b_arena = 0;
+    bool fetched = true, bfetched = true;         // `frames` / `bytes` hold the most recent push's
+    std::vector<rr_hdlc_frame> frames;            // ... ascending by pos
+    std::vector<unsigned char> bytes;
+    HdlcDeframer(size_t min_size, size_t max_size, int flags);
+    void push_dev(const unsigned char* d_bits, size_t n, hipStream_t s);
+    void push_host(const unsigned char* bits, size_t n);
+    const std::vector<rr_hdlc_frame>& fetch_frames();         // waits for the most recent push
+    const std::vector<unsigned char>& fetch_bytes();
+    const unsigned char* arena_dev() const { return last_n ? arena.p : nullptr; }
+    size_t arena_len() const { return last_n ? b_arena : 0; }
+    void fetch_stats(unsigned long long out[3]);
+};
+
 }  // namespace rr

@@ -446,6 +446,55 @@ struct LineArgs {
 };
 void launch_line(const LineArgs& a, hipStream_t s);
 
+// ---- kernels_hdlc.hip: HdlcDeframer (hdlc_deframer.rs:123-232) over the next n bits of a stream (hdlc_core.hpp holds the
+//      arithmetic) -------------------------------------------------------------------------------------------------------------------------
+// The VIRTUAL stream of a push: the st_in->count bits the stream so far left in cin (HDLC_HALO bits, then the raw bits of the gap
+// still open), then bits[0 .. n).  nv_max >= count + n is the host's own bound; it alone sizes the grids and the scratch:
+// nwords = 64 ntiles words each of raw / fl / ab / sf (ntiles = ceil(nv_max / HDLC_T)), ends_cap = nv_max / 7 + 2 flag ends and
+// gap maps, ceil(ends_cap / HDLC_GB) block maps and states.  Frames go to arena (arena_cap bytes, zeroed by the caller) at byte
+// floor((s + 1) / 8) of the gap's first flag end s, their records to recs in no order, *count of them; pstats: this push's share
+// of the three counters.  st_out / cout: what the next push starts from (distinct from st_in / cin).  Seven launches whatever the
+// bits hold; n == 0 launches nothing.
+constexpr int HDLC_T = 4096;                  // virtual bits of one tile
+constexpr int HDLC_GB = 256;                  // gaps of one block of the map scan
+struct HdlcState {
+    unsigned long long stats[3];              // decoded, crc_error, bitfixed so far
+    unsigned count;                           // carried bits
+    int state;                                // the machine at the anchor, carried bit HDLC_HALO - 1
+};
+struct HdlcRec {                              // rr_hdlc_frame
+    unsigned long long pos, start;
+    unsigned len, flags;
+};
+struct HdlcArgs {
+    const unsigned char* bits;
+    long n;
+    const unsigned char* cin;
+    unsigned char* cout;
+    const HdlcState* st_in;
+    HdlcState* st_out;
+    long carry_cap;                           // bytes of cout
+    long nv_max, ntiles;
+    unsigned long long w0;                    // stream position of bits[0]
+    unsigned long long min_size, max_size;
+    int keep, fix;
+    unsigned long long *raw, *fl, *ab, *sf;
+    unsigned* tilecnt;
+    unsigned long long* offs;
+    unsigned long long* etotal;
+    unsigned* ends;
+    long ends_cap;
+    unsigned char *gmap, *pmap, *bmap, *bstate;
+    int* fin;
+    unsigned char* arena;
+    long arena_cap;
+    HdlcRec* recs;
+    long rec_cap;
+    unsigned long long* count;
+    unsigned long long* pstats;
+};
+void launch_hdlc(const HdlcArgs& a, hipStream_t s);
+
 // ---- head fix of the fused FirFilter -> FftFilter blocks (stream start only, a few hundred samples) ----------------
 // z[m] = sum_k t1[k] V[voff + m + L1 - 1 - k], m < n: the front FirFilter's first outputs (fir.rs:166-177) from the virtual stream
 void launch_head_z(VSrc<cf> V, long voff, const cf* t1, int L1, cf* z, long n, hipStream_t s);

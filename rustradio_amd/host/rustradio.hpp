@@ -892,6 +892,50 @@ public:
     }
 };
 
+// ---- HdlcDeframer (src/hdlc_deframer.rs:80-232): the message (PDU) form of its output -------------------------------------------------
+// (rr_hdlc_deframer_create / rr_hdlc_deframer_push / rr_hdlc_frames / rr_hdlc_frame_bytes / rr_hdlc_stats).  push() takes the next
+// bits of the stream, one per byte, and returns what the NCWriteStream<Vec<u8>> behind the block receives for them: one
+// (bytes, tags) per frame whose closing flag ended inside them, each with the `packet_pos` tag (:193).  The machine, the open
+// gap's bits and the counters stay in the block from push to push; output_space (:237-253) has no counterpart.
+class HdlcDeframer {
+    detail::Handle h_;
+public:
+    using Packet = std::pair<std::vector<uint8_t>, std::vector<Tag>>;
+    struct Stats { unsigned long long decoded, crc_error, bitfixed; };
+    HdlcDeframer(size_t min_size, size_t max_size, bool keep_checksum = false, bool fix_bits = false)
+        : h_(rr_hdlc_deframer_create(min_size, max_size, (keep_checksum ? RR_HDLC_KEEP_CHECKSUM : 0) | (fix_bits ? RR_HDLC_FIX_BITS : 0))) {}
+    rr_block* handle() const { return h_.h; }
+    std::vector<Packet> push(const std::vector<uint8_t>& bits, std::vector<bool>* repaired = nullptr) {
+        if (rr_hdlc_deframer_push(h_.h, bits.data(), bits.size()) != 0) throw Error(rr_last_error());
+        size_t n = 0, nb = 0;
+        if (rr_hdlc_frames(h_.h, nullptr, 0, &n) != 0) throw Error(rr_last_error());
+        std::vector<rr_hdlc_frame> rec(n + 1);
+        if (n && rr_hdlc_frames(h_.h, rec.data(), n, &n) != 0) throw Error(rr_last_error());
+        if (rr_hdlc_frame_bytes(h_.h, nullptr, 0, &nb) != 0) throw Error(rr_last_error());
+        std::vector<uint8_t> arena(nb + 1);
+        if (n && nb && rr_hdlc_frame_bytes(h_.h, arena.data(), nb, &nb) != 0) throw Error(rr_last_error());
+        std::vector<Packet> out(n);
+        if (repaired) repaired->assign(n, false);
+        for (size_t i = 0; i < n; i++) {
+            if (rec[i].start > nb || rec[i].len > nb - rec[i].start) throw Error("HdlcDeframer: frame outside the arena");
+            out[i].first.assign(arena.begin() + (long)rec[i].start, arena.begin() + (long)(rec[i].start + rec[i].len));
+            out[i].second.emplace_back(0, "packet_pos", (uint64_t)rec[i].pos);
+            if (repaired) (*repaired)[i] = (rec[i].flags & 1u) != 0;
+        }
+        return out;
+    }
+    Stats stats() {
+        Stats s{0, 0, 0};
+        if (rr_hdlc_stats(h_.h, &s.decoded, &s.crc_error, &s.bitfixed) != 0) throw Error(rr_last_error());
+        return s;
+    }
+    size_t carry_bits() const {
+        size_t t = 0, c = 0;
+        if (rr_hdlc_deframer_dims(h_.h, &t, &c) != 0) throw Error(rr_last_error());
+        return c;
+    }
+};
+
 // ---- #[rustradio(sync)] blocks: MultiplyConst (src/multiply_const.rs), FastFM (src/quadrature_demod.rs:144-165) ----------
 // work() per rustradio_macros_code/src/lib.rs:458-515; a tag at position pos < n passes through at pos.
 template <class In, class Out> class SyncBlock : public Block {
