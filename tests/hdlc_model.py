@@ -52,12 +52,44 @@ def find_right_crc(data: bytes, got: int, fix_bits: bool):
     return None, crc, False
 
 
+_TABLE_NP = np.array(_TABLE, np.uint32)
+
+
+def find_right_crc_lockstep(data: bytes, got: int, fix_bits: bool):
+    """find_right_crc for long bodies: the same table CRC of the same 8 N single-flip copies, all of them stepped together byte
+    by byte (copy h is the data with bit h & 7 of byte h >> 3 flipped), and the first copy in find_right_crc's order that
+    matches.  Each copy's CRC is computed in full; nothing is derived from another copy's."""
+    crc = crc16_x25(data)
+    if got == crc or not fix_bits:
+        return None, crc, False
+    n = len(data)
+    if n:
+        fcs = np.full(8 * n, 0xffff, np.uint32)
+        masks = 1 << np.arange(8, dtype=np.uint32)
+        for i, b in enumerate(bytes(data)):
+            idx = (fcs ^ b) & 0xff
+            idx[8 * i:8 * i + 8] ^= masks
+            fcs = (fcs >> 8) ^ _TABLE_NP[idx]
+        hits = np.flatnonzero((fcs ^ 0xffff) == got)
+        if len(hits):
+            h = int(hits[0])
+            copy = bytearray(data)
+            copy[h >> 3] ^= 1 << (h & 7)
+            return bytes(copy), got, True
+    for crcbit in range(16):
+        if got ^ (1 << crcbit) == crc:
+            return None, got ^ (1 << crcbit), True
+    return None, crc, False
+
+
 class HdlcModel:
-    """the sequential machine; frames are (packet_pos, bytes, bitfixed)"""
+    """the sequential machine; frames are (packet_pos, bytes, bitfixed).  `repair` stands in for find_right_crc (same arguments,
+    same result: find_right_crc_lockstep where bodies are long)"""
     UNSYNCED, SYNCED, FINAL = 0, 1, 2
 
-    def __init__(self, min_size, max_size, keep_checksum=False, fix_bits=False):
+    def __init__(self, min_size, max_size, keep_checksum=False, fix_bits=False, repair=find_right_crc):
         self.min_size, self.max_size, self.keep, self.fix = min_size, max_size, keep_checksum, fix_bits
+        self.repair = repair
         self.state, self.reg, self.ones, self.bits = self.UNSYNCED, 0xff, 0, []
         self.decoded = self.crc_error = self.bitfixed = 0
         self.pos = 0
@@ -104,7 +136,7 @@ class HdlcModel:
             if len(data) < 2:
                 return
             body, got = data[:-2], data[-2] | data[-1] << 8
-            new, crc, fixed = find_right_crc(body, got, self.fix)
+            new, crc, fixed = self.repair(body, got, self.fix)
             if fixed:
                 self.bitfixed += 1
             if new is not None:

@@ -2,8 +2,8 @@
 bit: frames, positions, repaired flags and the three counters; there is no tolerance anywhere in this file.
 
 The handles are module-scoped, one per configuration of CONFIGS, each paired with an HdlcModel that is fed the same bits, so
-the expectation follows the handle whatever the order of the tests.  Between tests a push of 16 ones returns both to
-Unsynced(0xff) with 8 bits carried.  No test creates handles in a loop."""
+the expectation follows the handle whatever the order of the tests.  Between tests Rig.reset returns the model to Unsynced(0xff),
+and Rig.clear, where a test aims at the tiles, the handle to its 8 halo bits as well.  No test creates handles in a loop."""
 import ctypes as C
 import json
 import os
@@ -16,6 +16,7 @@ import frame_model as fm
 import hdlc_model as hm
 import rustradio_amd as rr
 from hdlc_model import FLAG, bytes_to_bits, crc16_x25, frame_bits, stuff
+from hdlc_rig import Rig
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,36 +34,9 @@ class _DevMem:
         self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
 
 
-class Rig:
-    def __init__(self):
-        self.dev = {c: rr.HdlcDeframer(*c) for c in CONFIGS}
-        self.model = {c: hm.HdlcModel(c[0], c[1], bool(c[2] & KEEP), bool(c[2] & FIX)) for c in CONFIGS}
-
-    def feed(self, cfg, bits, via="push"):
-        """the same bits into the handle and its model -> the frames, which must agree, as must the counters"""
-        x = np.ascontiguousarray(bits, np.uint8)
-        want = self.model[cfg].run(x)
-        d = self.dev[cfg]
-        if via == "push":
-            got = d.push(x)
-        else:
-            t = torch.from_numpy(x.copy()).cuda() if len(x) else torch.zeros(1, dtype=torch.uint8, device="cuda")
-            d.push_dev(t.data_ptr(), len(x))
-            got = d.result()
-        assert got == want, (cfg, len(x), got[:3], want[:3])
-        assert d.stats() == self.model[cfg].stats(), cfg
-        return got
-
-    def reset(self, cfg):
-        """16 ones: both sides Unsynced(0xff), nothing emitted, 8 bits carried"""
-        assert self.feed(cfg, [1] * 16) == []
-        m = self.model[cfg]
-        assert (m.state, m.reg, m.bits) == (m.UNSYNCED, 0xff, [])
-
-
 @pytest.fixture(scope="module")
 def rig():
-    return Rig()
+    return Rig(CONFIGS)
 
 
 @pytest.fixture(scope="module")
@@ -223,12 +197,12 @@ def test_long_frames(rig):
 
 # ---- 5. tile seams ------------------------------------------------------------------------------------------------------------------------
 def test_closing_flag_at_the_tile_seams(rig, T):
-    """behind reset() a handle carries 8 bits, so bit i of the push is virtual bit i + 8 of the tiles"""
+    """behind clear() a handle carries 8 bits, so bit i of the push is virtual bit i + 8 of the tiles"""
     cfg = (1, 10, KEEP)
     frame = frame_bits(b"\x42\x99\x10", with_crc=False)
     for off in (0, 1, 6, 7, T - 1):
         end = T + off - 8                           # the push bit that is the closing flag's last
-        rig.reset(cfg)
+        rig.clear(cfg)
         bits = [0] * (end + 1 - len(frame)) + frame + [0] * 9
         got = rig.feed(cfg, bits, "dev")
         assert [f[1] for f in got] == [b"\x42\x99\x10"] and got[0][0] == rig.model[cfg].pos - 10, off
@@ -238,11 +212,11 @@ def test_stuffed_zero_and_abort_across_a_seam(rig, T):
     cfg = (10, 1500, FIX)
     payload = b"\xff" * 700                         # a stuffed 0 behind every five bits: one alignment of six puts one on the seam's first bit
     for lead in range(6):
-        rig.reset(cfg)
+        rig.clear(cfg)
         assert [f[1] for f in rig.feed(cfg, [0] * lead + frame_bits(payload), "dev")] == [payload]
     cfg = (1, 10, KEEP)
     for k in range(1, 8):                           # seven ones, k of them in front of the seam, inside a frame
-        rig.reset(cfg)
+        rig.clear(cfg)
         head = FLAG + stuff(bytes_to_bits(b"\x01\x02"))
         bits = [0] * (T - 8 - k - len(head)) + head + [1] * 7 + [0] + frame_bits(b"\x33", with_crc=False)
         assert [f[1] for f in rig.feed(cfg, bits, "dev")] == [b"\x33"], k
@@ -251,12 +225,12 @@ def test_stuffed_zero_and_abort_across_a_seam(rig, T):
 def test_a_frame_spanning_three_tiles_and_pushes_of_a_tile(rig, T, drawn):
     cfg = (10, 1500, FIX)
     payload = np.random.default_rng(14).integers(0, 256, 1400, dtype=np.uint8).tobytes()
-    rig.reset(cfg)
+    rig.clear(cfg)
     bits = [0] * (T - 500) + frame_bits(payload)
     assert len(bits) > 3 * T - 500
     assert [f[1] for f in rig.feed(cfg, bits, "dev")] == [payload]
     cfg = (1, 10, KEEP)
-    rig.reset(cfg)
+    rig.clear(cfg)
     at, total = 0, 0
     for n in (T, T - 1, T + 1, T - 8, T):
         total += len(rig.feed(cfg, drawn[at:at + n], "dev"))

@@ -312,7 +312,8 @@ def fm_stream(seed=5, sps=5.2083, kf=0.35, offset=0.25):
 
 def test_end_to_end_two_g3ruh_bursts_one_across_a_push():
     """rr_burst_detector + rr_quaddemod -> rr_stream_to_pdu -> rr_wpcr_process_pdus -> rr_wpcr_pack_dev -> rr_bit_decoder on
-    device buffers; the host model of HdlcDeframer recovers both frames"""
+    device buffers; the host model of HdlcDeframer recovers both frames, and rr_hdlc_deframer, fed the same device buffer, what the
+    model recovers: frames, positions and counters"""
     kf, thr = 0.35, 0.3
     x, payloads = fm_stream(kf=kf)
     n = len(x) - 1
@@ -327,6 +328,7 @@ def test_end_to_end_two_g3ruh_bursts_one_across_a_push():
     pdus = rr.StreamToPdu(thr, 6000, 20, rr.PDU_MIDPOINT)
     w, dec = rr.Wpcr(samp_rate=50000.0), rr.BitDecoder(nrzi=True, descrambler=G3RUH)
     deframer, frames, seen = hm.HdlcModel(10, 200), [], []
+    dev_deframer = rr.HdlcDeframer(10, 200)
     for a, c in [(0, cut), (cut, n)]:
         pdus.push_dev(data.data_ptr() + 4 * a, env.data_ptr() + 4 * a, c - a)
         rec = pdus.records()
@@ -354,9 +356,13 @@ def test_end_to_end_two_g3ruh_bursts_one_across_a_push():
             bits = torch.zeros(cap, dtype=torch.uint8, device="cuda")
             assert dec.work_dev(packed.data_ptr(), cap, bits.data_ptr(), cap)[2] == cap
             dec.sync()
-            frames += deframer.run(bits.cpu().numpy())
+            ended = deframer.run(bits.cpu().numpy())
+            frames += ended
+            dev_deframer.push_dev(bits.data_ptr(), cap)
+            assert dev_deframer.result() == ended and dev_deframer.stats() == deframer.stats()
     assert [len(s) for s in seen] == [1, 1] and seen[1][0][0] < cut, seen          # the second burst began in the first push
     assert [f[1] for f in frames] == payloads, (seen, [len(f[1]) for f in frames])
+    assert dev_deframer.stats() == deframer.stats() and deframer.stats()[0] == len(payloads)
 
 
 def test_process_pdus_without_midpoint_and_after_an_empty_push():

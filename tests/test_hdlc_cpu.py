@@ -119,3 +119,61 @@ def test_single_bit_repair_takes_the_lowest_byte_and_bit():
         bits = FLAG + stuff(broken) + FLAG
         assert both(bits, (1, 100, False, True)) == ([(len(bits) - 1, payload, True)], (1, 0, 1))
         assert both(bits, (1, 100, False, False)) == ([], (0, 1, 0))
+
+
+# ---- find_right_crc_lockstep, the repair of the long bodies ---------------------------------------------------------------------------
+def test_lockstep_repair_equals_find_right_crc():
+    rng = np.random.default_rng(31)
+    assert hm.find_right_crc_lockstep(b"", 0x1234, True) == hm.find_right_crc(b"", 0x1234, True)
+    assert hm.find_right_crc_lockstep(b"", 0x0001, True) == hm.find_right_crc(b"", 0x0001, True) == (None, 0x0000, True)
+    seen = set()
+    for n in (1, 2, 24, 100):
+        data = rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+        good = crc16_x25(data)
+        cases = [(data, good, "intact")]
+        for h in sorted({0, 1, 7, 8 * n // 2, 8 * n - 8, 8 * n - 1} & set(range(8 * n))):
+            broken = bytearray(data)
+            broken[h >> 3] ^= 1 << (h & 7)
+            cases.append((bytes(broken), good, "data"))
+        cases += [(data, good ^ (1 << c), "crc") for c in range(16)]
+        cases += [(data, good ^ 0x0003, "two crc bits"), (data, good ^ 0x8001, "two crc bits")]
+        for body, got, what in cases:
+            for fix in (False, True):
+                want = hm.find_right_crc(body, got, fix)
+                assert hm.find_right_crc_lockstep(body, got, fix) == want, (n, what, fix)
+                seen.add((what, fix, want[0] is not None, want[2]))
+    # a repaired body, a repaired checksum, nothing to repair and nothing repairable have all been seen (two wrong CRC bits look
+    # like one wrong data bit for some bodies, so "two crc bits" may be either of the last two)
+    assert ("data", True, True, True) in seen and ("crc", True, False, True) in seen and ("intact", True, False, False) in seen
+    assert any(s[0] == "two crc bits" and s[1] and not s[3] for s in seen)
+    assert all(not s[3] for s in seen if not s[1])
+
+
+def test_lockstep_repair_past_the_crc_period():
+    """CRC-16/X.25 has period 32,767: in a body of 4,200 bytes bit h and bit h + 32,767 change the CRC alike, and so do CRC-field
+    bit c and data bit 833 + c.  find_right_crc takes the lowest, whatever was flipped (hdlc_deframer.rs:41-71)."""
+    rng = np.random.default_rng(32)
+    data = rng.integers(0, 256, 4200, dtype=np.uint8).tobytes()
+    good = crc16_x25(data)
+
+    def flipped(h):
+        b = bytearray(data)
+        b[h >> 3] ^= 1 << (h & 7)
+        return bytes(b)
+
+    def repaired_bit(new, old):
+        d = np.flatnonzero(np.unpackbits(np.frombuffer(new, np.uint8) ^ np.frombuffer(old, np.uint8), bitorder="little"))
+        assert len(d) == 1
+        return int(d[0])
+
+    for h, lowest in ((32767, 0), (33599, 832)):
+        new, crc, fixed = hm.find_right_crc_lockstep(flipped(h), good, True)
+        assert fixed and crc == good and repaired_bit(new, flipped(h)) == lowest
+    for c in (0, 7, 8, 15):
+        new, crc, fixed = hm.find_right_crc_lockstep(data, good ^ (1 << c), True)
+        assert fixed and crc == good ^ (1 << c) and repaired_bit(new, data) == 833 + c          # a corrupt frame is delivered
+        assert crc16_x25(new) == crc
+    # HdlcModel with it in find_right_crc's place: the frame comes out with bit 0 turned over as well
+    bits = FLAG + stuff(bytes_to_bits(flipped(32767) + bytes([good & 0xff, good >> 8]))) + FLAG
+    m = HdlcModel(0, 65535, False, True, hm.find_right_crc_lockstep)
+    assert m.run(bits) == [(len(bits) - 1, flipped(0)[:4095] + flipped(32767)[4095:], True)] and m.stats() == (1, 0, 1)
