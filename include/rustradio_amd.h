@@ -110,7 +110,10 @@ typedef struct {
                                ref_blocks_on); 0 / 2 = the default, a small launch of its own behind every call */
     int host_in_staged;     /* rr_block_work on a page-locked INPUT window: > 0 copy it to device memory first (a copy kernel, 55 GB/s)
                                instead of letting the block's kernels read it in place, < 0 always in place; 0 = the block's default */
-    int reserved[3];
+    int sync_lanes;         /* rr_symbol_sync_create: streams per wave of the clock kernel, 1 or 64; 0 = by stream count */
+    int sync_prof_launch;   /* rr_symbol_sync_create: 1 / 2 / 3 = rr_block_profile times that launch of a push (signs, clock, gather)
+                               alone; 0 = the three as one bracket */
+    int reserved[1];
 } rr_build_opts;
 int rr_next_create_options(const rr_build_opts *opts);   /* NULL clears a pending override */
 
@@ -562,6 +565,48 @@ int rr_hdlc_stats(rr_block *b, unsigned long long *decoded, unsigned long long *
  * first bit, so tests aim at the seams through a push of a handle that carries the 8 bits of a fresh stream); *carry_bits = the
  * most bits a handle carries from push to push: M + floor((M - 1) / 5) + 16, M = 8 max_size + 1. */
 int rr_hdlc_deframer_dims(const rr_block *b, size_t *tile_bits, size_t *carry_bits);
+
+/* SymbolSync::new(src, sps, max_deviation, TedZeroCrossing, IirFilter::new(taps)) x nstreams (src/symbol_sync.rs:71-98, work
+ * :115-217; src/iir_filter.rs:104-125): the symbol clock of the streaming data receivers (examples/ax25-9600-rx.rs:186-193,
+ * ax25-1200-rx.rs:293-300, il2p-1200-rx.rs:110-117), between the FM front end (rr_fm_chain / rr_fm_multi / rr_channelizer) and
+ * rr_bit_decoder, with the samples, the symbols and the clock state staying on the device.  A batch block like rr_hdlc_deframer:
+ * rr_block_work on the handle is an error.  One handle runs nstreams independent SymbolSyncs, each with its own state.
+ * EXACT: symbols, clock values and counts are bit-identical to the reference block's, whatever the split of a stream into pushes
+ * (its state is per sample; every f32 operation is rounded on its own, in its order).  fill(sps) puts ntaps - 1 copies of sps
+ * into a history of deviations, so with the examples' taps the clock starts pinned at sps + max_deviation: reproduced, not repaired.
+ * There is no parallel form within one stream: a push is three launches whatever nstreams and the samples are (signs packed 64 to
+ * a word; one lane per stream walking them with the reference's loop; a gather), and ONE stream runs on ONE lane, slower than one
+ * host core (README, profiles/symsync_probe.md).
+ * DEVIATIONS, both refusals: the reference takes any max_deviation and loops forever once clock <= 0, and has no cap on the taps.
+ * NULL + rr_last_error, said before any device is touched: "sps must be above 1" (:78; NaN too), "max_deviation out of range"
+ * (unless 0 <= max_deviation <= sps / 2), "SymbolSync needs 1 to 8 finite taps", "nstreams out of range" (0 or above 4096).
+ * NOT TESTED: after a non-finite clock (overflowing taps only) the block emits nothing more, as the reference would; stream_pos
+ * saturates at 2^24 through a run that long without a sign change, as the reference's does.
+ * The reference's assert at :157 (stream_pos > last_sym_boundary_pos) cannot fire: the boundary is a copy of an earlier stream_pos,
+ *   stream_pos has grown by 1.0 at least once since (below 2^24 + 1 that is never rounded away) and a step back moves both alike.
+ * The one at :175 (t > 0) cannot fire: it stands behind t > 0.8 (sps - max_deviation) >= 0.4 sps > 0. */
+rr_block *rr_symbol_sync_create(float sps, float max_deviation, const float *taps, size_t ntaps, size_t nstreams);
+/* stream c: n samples at d_in + c*in_stride; its symbols at d_syms + c*out_stride, its clock values (d_clock may be NULL:
+ * out_clock() never called) at d_clock + c*out_stride.  in_stride >= n, out_stride >= n (a sample emits at most one symbol), the
+ * layout of rr_fm_multi_create's output windows.  Elements at and beyond a stream's count are never written.  RR_ERR before any
+ * device is touched: a stride below n, n >= 2^31, a null buffer with n > 0.  n == 0 launches nothing, produces 0 for every stream
+ * and leaves every state alone.  Asynchronous on hip_stream. */
+int rr_symbol_sync_push_dev(rr_block *b, const void *d_in, size_t in_stride, size_t n,
+                            void *d_syms, void *d_clock, size_t out_stride, void *hip_stream);
+/* The same with host pointers: copies the samples down, runs, waits and copies each stream's produced[c] symbols (and clock values)
+ * back. */
+int rr_symbol_sync_push(rr_block *b, const float *in, size_t in_stride, size_t n,
+                        float *syms, float *clock, size_t out_stride, size_t *produced /* [nstreams] */);
+/* symbols of each stream in the most recent push; waits for it (one download of 8*nstreams bytes).  *total = nstreams, the first
+ * min(*total, cap) written (the contract of rr_wpcr_results); a count is clamped to the push's n before anybody sees it. */
+int rr_symbol_sync_produced(rr_block *b, size_t *produced, size_t cap, size_t *total);
+/* the same counts where the next device stage can read them: unsigned long long[nstreams], valid until the next push */
+const void *rr_symbol_sync_counts_dev(rr_block *b);
+/* *streams_per_wave = 1 (one active lane per wave) or 64: how the clock kernel maps streams to lanes (rr_build_opts.sync_lanes) */
+int rr_symbol_sync_dims(const rr_block *b, size_t *streams_per_wave);
+/* carried state of one stream after the most recent push (waits): clock, stream_pos, last_sym_boundary_pos, next_sym_middle,
+ * last_sign, and the filter history oldest first (*nhist = ntaps - 1, the first min(*nhist, cap) written) */
+int rr_debug_symbol_sync_state(rr_block *b, size_t stream, float *four, int *last_sign, float *hist, size_t cap, size_t *nhist);
 
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)

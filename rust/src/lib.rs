@@ -105,6 +105,25 @@ unsafe extern "C" {
     fn rr_hdlc_stats(b: *mut RrBlock, decoded: *mut u64, crc_error: *mut u64, bitfixed: *mut u64) -> c_int;
     #[allow(dead_code)]
     fn rr_hdlc_deframer_dims(b: *const RrBlock, tile_bits: *mut usize, carry_bits: *mut usize) -> c_int;
+    // (declared for completeness: SymbolSync takes a ReadStream<Float> and feeds a WriteStream<Float> plus the optional out_clock()
+    //  stream; one handle runs N of them, so its typed block belongs with the N-channel blocks; not written yet)
+    #[allow(dead_code)]
+    fn rr_symbol_sync_create(sps: f32, max_deviation: f32, taps: *const f32, ntaps: usize, nstreams: usize) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_symbol_sync_push_dev(b: *mut RrBlock, d_in: *const c_void, in_stride: usize, n: usize, d_syms: *mut c_void, d_clock: *mut c_void,
+                               out_stride: usize, hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_symbol_sync_push(b: *mut RrBlock, input: *const f32, in_stride: usize, n: usize, syms: *mut f32, clock: *mut f32,
+                           out_stride: usize, produced: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_symbol_sync_produced(b: *mut RrBlock, produced: *mut usize, cap: usize, total: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_symbol_sync_counts_dev(b: *mut RrBlock) -> *const c_void;
+    #[allow(dead_code)]
+    fn rr_symbol_sync_dims(b: *const RrBlock, streams_per_wave: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_debug_symbol_sync_state(b: *mut RrBlock, stream: usize, four: *mut f32, last_sign: *mut c_int, hist: *mut f32, cap: usize,
+                                  nhist: *mut usize) -> c_int;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;

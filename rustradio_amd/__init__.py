@@ -15,6 +15,7 @@ what the reference would pass to `consume()`/`produce()`.
     Hilbert              src/hilbert.rs:22-129
     Wpcr                 src/wpcr.rs:84-239      (message form: a batch of bursts per call)
     StreamToPdu          src/burst_tagger.rs:68-85, src/stream_to_pdu.rs:198-275, src/wpcr.rs:44-82 (BurstTagger -> StreamToPdu -> Midpointer)
+    SymbolSync           src/symbol_sync.rs:46-217, src/iir_filter.rs:104-125   (N streams per handle, a window of each per call)
     low_pass / low_pass_complex / hilbert_taps / make_window   src/fir.rs:594-680, src/window.rs
 
 All sample arithmetic runs in HIP kernels on the GPU; nothing here computes samples.
@@ -62,7 +63,8 @@ def _effective_opts() -> dict:
 def build_options(**kw):
     """fir_path='direct'|'fft', fir_prune=+-1, fir_half=-1, fir_cfg=0..7, fft_log2f=10..14, fft_no_split=1,
     fftfloat_complex=1, fm_full=1, fm_poly=-1 (8 / 12: the multi-channel kernel variant), dstream_no_vmm=1, fir_poly=+-1,
-    fft_nonfinite_tiles=1 (none) | 3 (in the tile kernel's tail), host_in_staged=+-1"""
+    fft_nonfinite_tiles=1 (none) | 3 (in the tile kernel's tail), host_in_staged=+-1, sync_lanes=1 | 64 (SymbolSync: streams
+    per wave of the clock kernel), sync_prof_launch=1..3 (SymbolSync: profile() times that launch alone)"""
     prev = getattr(_tls, "opts", None)
     _tls.opts = dict(_effective_opts(), **kw)
     try:
@@ -811,7 +813,77 @@ class HdlcDeframer(Block):
         return d.value, e.value, f.value
 
 
-WPCR_MAX_LEN = 512_000      # samples of one burst: the reference's stream capacity in f32
+class SymbolSync(Block):
+    """SymbolSync::new(src, sps, max_deviation, TedZeroCrossing, IirFilter::new(taps)) x nstreams behind one handle
+    (rr_symbol_sync_create; src/symbol_sync.rs:46-217; not a stream block: work() raises): the next n samples of each stream in,
+    its symbols (and the clock value that goes with each) out, bit-identical to the reference block's.  Every stream's state stays
+    on the device between pushes.  See include/rustradio_amd.h."""
+
+    def __init__(self, sps: float, max_deviation: float, taps, nstreams: int = 1):
+        t = np.ascontiguousarray(taps, np.float32).ravel()
+        super().__init__(lib().rr_symbol_sync_create(float(sps), float(max_deviation), _ptr(t) if len(t) else None, len(t), int(nstreams)),
+                         np.float32, np.float32)
+        self.nstreams, self.ntaps = int(nstreams), len(t)
+
+    @property
+    def streams_per_wave(self) -> int:
+        """rr_symbol_sync_dims: 1 or 64"""
+        v = C.c_size_t(0)
+        if lib().rr_symbol_sync_dims(self._h, C.byref(v)) != 0:
+            raise RuntimeError(last_error())
+        return v.value
+
+    def push_dev(self, d_in: int, in_stride: int, n: int, d_syms: int, d_clock, out_stride: int, stream: int = 0) -> None:
+        """rr_symbol_sync_push_dev: stream c's next n samples at d_in + c * in_stride (raw device pointers, f32 elements), its
+        symbols to d_syms + c * out_stride, its clock values to d_clock + c * out_stride (None: not wanted); asynchronous on
+        `stream`; produced() waits"""
+        if lib().rr_symbol_sync_push_dev(self._h, C.c_void_p(d_in), int(in_stride), int(n), C.c_void_p(d_syms),
+                                         C.c_void_p(d_clock) if d_clock else None, int(out_stride), C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+
+    def push(self, x, clock: bool = True):
+        """rr_symbol_sync_push on a host array of shape (nstreams, n) (or (n,) for one stream) -> ([symbols of stream c],
+        [clock values of stream c] or None)"""
+        a = np.ascontiguousarray(x, np.float32)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        if a.ndim != 2 or a.shape[0] != self.nstreams:
+            raise ValueError("SymbolSync.push: one row per stream")
+        n = a.shape[1]
+        syms = np.zeros((self.nstreams, max(n, 1)), np.float32)
+        clk = np.zeros_like(syms) if clock else None
+        produced = (C.c_size_t * self.nstreams)()
+        if lib().rr_symbol_sync_push(self._h, _ptr(a) if n else None, n, n, _ptr(syms) if n else None, _ptr(clk) if clock and n else None,
+                                     n, produced) != 0:
+            raise ValueError(last_error())
+        return ([syms[c, :produced[c]].copy() for c in range(self.nstreams)],
+                [clk[c, :produced[c]].copy() for c in range(self.nstreams)] if clock else None)
+
+    def produced(self) -> np.ndarray:
+        """-> symbols of each stream in the most recent push, uint64[nstreams] (rr_symbol_sync_produced; waits)"""
+        out = (C.c_size_t * self.nstreams)()
+        total = C.c_size_t(0)
+        if lib().rr_symbol_sync_produced(self._h, out, self.nstreams, C.byref(total)) != 0:
+            raise RuntimeError(last_error())
+        return np.array(out[:total.value], np.uint64)
+
+    def counts_dev(self) -> int:
+        """-> raw device pointer to the same counts, unsigned long long[nstreams] (rr_symbol_sync_counts_dev); valid until the
+        next push"""
+        return lib().rr_symbol_sync_counts_dev(self._h)
+
+    def state(self, stream: int = 0) -> dict:
+        """-> the carried state of one stream after the most recent push (rr_debug_symbol_sync_state; waits): clock, stream_pos,
+        last_sym_boundary_pos, next_sym_middle (float32), last_sign (bool), hist (float32[ntaps - 1], oldest first)"""
+        four = np.zeros(4, np.float32)
+        hist = np.zeros(8, np.float32)
+        sign, nh = C.c_int(0), C.c_size_t(0)
+        if lib().rr_debug_symbol_sync_state(self._h, int(stream), _ptr(four), C.byref(sign), _ptr(hist), len(hist), C.byref(nh)) != 0:
+            raise ValueError(last_error())
+        return {"clock": four[0], "stream_pos": four[1], "last_sym_boundary_pos": four[2], "next_sym_middle": four[3],
+                "last_sign": bool(sign.value), "hist": hist[:nh.value].copy()}
+
+
+WPCR_MAX_LEN = 512_000     # samples of one burst: the reference's stream capacity in f32
 # rr_wpcr_result
 WPCR_RESULT = np.dtype([("ok", np.int32), ("bin", np.uint32), ("sps", np.float32), ("phase0", np.float32), ("phase", np.float32),
                         ("frequency", np.float32), ("nsyms", np.uint64)], align=True)

@@ -14,6 +14,7 @@
 #include "frame_host.hpp"
 #include "hdlc_host.hpp"
 #include "pdu_host.hpp"
+#include "symsync_host.hpp"
 #include "taps.hpp"
 
 struct rr_block {
@@ -80,7 +81,7 @@ template <class T> static T* as(const rr_block* b, const char* what, const char*
     return p;
 }
 static const char NOT_WPCR[] = "not a wpcr handle", NOT_PDU[] = "not a stream_to_pdu handle", NOT_FRAMER[] = "not an hdlc framer handle";
-static const char NOT_DEFRAMER[] = "not an hdlc deframer handle";
+static const char NOT_DEFRAMER[] = "not an hdlc deframer handle", NOT_SYNC[] = "not a symbol sync handle";
 // a fetched list of (pos << shift) | val entries into the caller's two arrays
 template <class E> static void unpack(const std::vector<E>& e, unsigned shift, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
     *total = e.size();
@@ -103,6 +104,7 @@ int rr_next_create_options(const rr_build_opts* o) {
     b.fft_log2f = o->fft_log2f; b.fft_no_split = o->fft_no_split; b.fftfloat_complex = o->fftfloat_complex;
     b.fm_full = o->fm_full; b.fm_poly = o->fm_poly; b.dstream_no_vmm = o->dstream_no_vmm;
     b.fir_poly = o->fir_poly; b.fft_nonfinite_tiles = o->fft_nonfinite_tiles; b.host_in_staged = o->host_in_staged;
+    b.sync_lanes = o->sync_lanes; b.sync_prof_launch = o->sync_prof_launch;
     if (b.fir_path < 0 || b.fir_path > 2 || b.fir_cfg > 7 || (b.fft_log2f != 0 && (b.fft_log2f < 10 || b.fft_log2f > 14))) {
         rr::set_last_error("rr_next_create_options: value out of range");
         return RR_ERR;
@@ -487,6 +489,57 @@ int rr_hdlc_deframer_dims(const rr_block* b, size_t* tile_bits, size_t* carry_bi
     *tile_bits = rr::HDLC_T;
     *carry_bits = rr::hdlc_carry_bits(d->max_size);
     return 0;
+}
+rr_block* rr_symbol_sync_create(float sps, float max_deviation, const float* taps, size_t ntaps, size_t nstreams) {
+    if (const char* e = rr::symsync_check(sps, max_deviation, taps, ntaps, nstreams)) return refuse_create(e);
+    return make_block([&] { return new rr::SymbolSync(sps, max_deviation, taps, ntaps, nstreams); });
+}
+int rr_symbol_sync_push_dev(rr_block* b, const void* d_in, size_t in_stride, size_t n, void* d_syms, void* d_clock, size_t out_stride,
+                            void* hip_stream) {
+    auto* y = as<rr::SymbolSync>(b, "rr_symbol_sync_push_dev", NOT_SYNC);
+    if (!y) return RR_ERR;
+    if (const char* e = rr::symsync_check_push(d_in, in_stride, n, d_syms, out_stride)) { rr::set_last_error(e); return RR_ERR; }
+    return on_device(y, hip_stream, [&](hipStream_t s) {
+        y->push_dev(static_cast<const float*>(d_in), in_stride, n, static_cast<float*>(d_syms), static_cast<float*>(d_clock), out_stride, s);
+    });
+}
+int rr_symbol_sync_push(rr_block* b, const float* in, size_t in_stride, size_t n, float* syms, float* clock, size_t out_stride,
+                        size_t* produced) {
+    auto* y = as<rr::SymbolSync>(b, "rr_symbol_sync_push", NOT_SYNC);
+    if (!y) return RR_ERR;
+    if (!produced) { rr::set_last_error("rr_symbol_sync_push: null argument"); return RR_ERR; }
+    if (const char* e = rr::symsync_check_push(in, in_stride, n, syms, out_stride)) { rr::set_last_error(e); return RR_ERR; }
+    return guarded([&] { y->push_host(in, in_stride, n, syms, clock, out_stride, produced); });
+}
+int rr_symbol_sync_produced(rr_block* b, size_t* produced, size_t cap, size_t* total) {
+    auto* y = as<rr::SymbolSync>(b, "rr_symbol_sync_produced", NOT_SYNC);
+    if (!y) return RR_ERR;
+    if (!total || (cap && !produced)) { rr::set_last_error("rr_symbol_sync_produced: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(y, [&] { rr::symsync_copy_counts(y->fetch_counts(), produced, cap, total); });
+}
+const void* rr_symbol_sync_counts_dev(rr_block* b) {
+    auto* y = as<rr::SymbolSync>(b, "rr_symbol_sync_counts_dev", NOT_SYNC);
+    return y ? y->count.p : nullptr;
+}
+int rr_symbol_sync_dims(const rr_block* b, size_t* streams_per_wave) {
+    auto* y = as<rr::SymbolSync>(b, "rr_symbol_sync_dims", NOT_SYNC);
+    if (!y || !streams_per_wave) { if (y) rr::set_last_error("rr_symbol_sync_dims: null argument"); return RR_ERR; }
+    *streams_per_wave = (size_t)y->spw;
+    return 0;
+}
+int rr_debug_symbol_sync_state(rr_block* b, size_t stream, float* four, int* last_sign, float* hist, size_t cap, size_t* nhist) {
+    auto* y = as<rr::SymbolSync>(b, "rr_debug_symbol_sync_state", NOT_SYNC);
+    if (!y) return RR_ERR;
+    if (!four || !last_sign || !nhist || (cap && !hist)) { rr::set_last_error("rr_debug_symbol_sync_state: null argument"); return RR_ERR; }
+    return on_device(y, [&] {
+        const rr::SyncState s = y->fetch_state(stream);
+        four[0] = s.clock; four[1] = s.stream_pos; four[2] = s.last_sym_boundary_pos; four[3] = s.next_sym_middle;
+        *last_sign = s.last_sign;
+        const size_t nh = (size_t)y->prm.ntaps - 1;
+        *nhist = nh;
+        for (size_t i = 0; i < nh && i < cap; i++) hist[i] = s.hist[nh - 1 - i];       // (the device keeps it newest first)
+    });
 }
 rr_block* rr_rtlsdr_decode_create(void) {
     return make_block([&] { return new rr::RtlSdrDecode(); });

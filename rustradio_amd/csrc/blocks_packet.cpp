@@ -1,5 +1,5 @@
 // blocks_packet.cpp — host side of the packet-side blocks (blocks_packet.hpp): the sync blocks, the burst and bit blocks, and the
-// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer).  Citations are to the reference's src, as in blocks.cpp.
+// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, SymbolSync).  Citations are to the reference's src, as in blocks.cpp.
 #include "blocks_packet.hpp"
 
 #include <algorithm>
@@ -11,6 +11,7 @@
 #include "frame_host.hpp"
 #include "hdlc_host.hpp"
 #include "pdu_host.hpp"
+#include "symsync_host.hpp"
 
 namespace rr {
 
@@ -636,6 +637,94 @@ void HdlcDeframer::fetch_stats(unsigned long long out[3]) {
     HdlcState now{};
     stage_download_sync(&now, st.in(), sizeof now, stream);
     for (int k = 0; k < 3; k++) out[k] = now.stats[k];
+}
+
+// ---- SymbolSync (symbol_sync.rs:46-217; kernels_sync.hip) ---------------------------------------------------------------------------------
+// The mapping of streams to lanes of the clock kernel is a measured choice (profiles/symsync_probe.md): one stream per wave ran a
+// stream at 5.1 to 6.8 Msample/s, 64 per wave at 1.6 to 1.9 (nearly every iteration some lane takes the sign-change branch and all
+// 64 pay), and up to the 4096 streams a handle takes the device has a SIMD's share for every wave of the first mapping (4096 x
+// 16,384: 3.4 ms against 10.5 ms).  So it is one stream per wave at every stream count; rr_build_opts.sync_lanes forces either.
+SymbolSync::SymbolSync(float sps, float max_deviation, const float* taps, size_t ntaps, size_t ns)
+    : BatchBlock("SymbolSync", 4, 4, "SymbolSync runs nstreams streams: rr_symbol_sync_push / rr_symbol_sync_push_dev"), nstreams(ns) {
+    if (const char* e = symsync_check(sps, max_deviation, taps, ntaps, ns)) throw Error(e);
+    prm = symsync_params(sps, max_deviation, taps, ntaps);
+    const int forced = build_opts().sync_lanes;
+    if (forced != 0 && forced != 1 && forced != 64) throw Error("rr_build_opts.sync_lanes: 0, 1 or 64");
+    spw = forced ? forced : 1;
+    prof_launch = build_opts().sync_prof_launch;
+    if (prof_launch < 0 || prof_launch > 3) throw Error("rr_build_opts.sync_prof_launch: 0 .. 3");
+    SyncState init{};
+    sync_init(init, prm);
+    const std::vector<SyncState> all(ns, init);
+    st.upload(all.data(), ns, stream);
+    count.reserve(ns);
+    RR_HIP(hipMemsetAsync(count.p, 0, ns * sizeof(unsigned long long), stream));
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void SymbolSync::push_dev(const float* d_in, size_t in_stride, size_t n, float* d_syms, float* d_clock, size_t out_stride, hipStream_t s) {
+    if (const char* e = symsync_check_push(d_in, in_stride, n, d_syms, out_stride)) throw Error(e);
+    counts.assign(nstreams, 0);
+    last_n = n;
+    if (!n) {                                  // a push of no samples produces nothing and leaves every state alone
+        RR_HIP(hipMemsetAsync(count.p, 0, nstreams * sizeof(unsigned long long), s));
+        fetched = true;
+        return;
+    }
+    SyncArgs a{};
+    a.in = d_in; a.in_stride = (long)in_stride; a.n = (long)n; a.nstreams = (long)nstreams;
+    a.syms = d_syms; a.clk = d_clock; a.out_stride = (long)out_stride;
+    a.nwords = (long)symsync_words(n);
+    words.reserve(nstreams * (size_t)a.nwords);
+    idx.reserve(nstreams * n);
+    a.words = words.p; a.idx = idx.p; a.count = count.p;
+    a.st_in = st.in(); a.st_out = st.out();
+    a.prm = prm;
+    a.spw = spw;
+    if (!prof_launch) prof_begin(s);
+    for (int k = 1; k <= 3; k++) {
+        if (prof_launch == k) prof_begin(s);
+        launch_sync(a, k, s);
+        if (prof_launch == k) prof_end(s);
+    }
+    if (!prof_launch) prof_end(s);
+    st.flip();
+    fetched = false;
+}
+void SymbolSync::push_host(const float* in, size_t in_stride, size_t n, float* syms, float* clock, size_t out_stride, size_t* produced) {
+    host_call([&] {
+        if (const char* e = symsync_check_push(in, in_stride, n, syms, out_stride)) throw Error(e);
+        if (n) {
+            const size_t span = symsync_span(nstreams, in_stride, n);
+            h_in.reserve(span);
+            h_syms.reserve(nstreams * n);
+            if (clock) h_clk.reserve(nstreams * n);
+            hstage().h2d(h_in.p, in, span * sizeof(float), stream);
+        }
+        push_dev(h_in.p, in_stride, n, h_syms.p, clock ? h_clk.p : nullptr, n, stream);
+        const std::vector<size_t>& k = fetch_counts();       // waits; clamped to n
+        for (size_t c = 0; c < nstreams; c++) {
+            if (k[c]) hstage().d2h(syms + c * out_stride, h_syms.p + c * n, k[c] * sizeof(float), stream);
+            if (k[c] && clock) hstage().d2h(clock + c * out_stride, h_clk.p + c * n, k[c] * sizeof(float), stream);
+            produced[c] = k[c];
+        }
+    });
+}
+const std::vector<size_t>& SymbolSync::fetch_counts() {
+    settle();
+    if (!fetched) {
+        std::vector<unsigned long long> raw(nstreams);
+        stage_download_sync(raw.data(), count.p, nstreams * sizeof(unsigned long long), stream);
+        symsync_clamp_counts(raw.data(), nstreams, last_n, counts);
+        fetched = true;
+    }
+    return counts;
+}
+SyncState SymbolSync::fetch_state(size_t c) {
+    if (c >= nstreams) throw Error("symbol sync: no such stream");
+    settle();
+    SyncState s{};
+    stage_download_sync(&s, st.in() + c, sizeof s, stream);
+    return s;
 }
 
 }  // namespace rr

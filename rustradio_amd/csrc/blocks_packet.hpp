@@ -294,4 +294,26 @@ struct HdlcDeframer : BatchBlock {
     void fetch_stats(unsigned long long out[3]);
 };
 
+// SymbolSync (symbol_sync.rs:46-217) x nstreams over windows of nstreams f32 streams (kernels_sync.hip): no stream protocol
+// (work_dev is an error).  Each stream's state between pushes (SyncState) stays on the device; the host keeps only the geometry of
+// the most recent push and clamps the counts it reads back to it (symsync_host.hpp).
+struct SymbolSync : BatchBlock {
+    SyncParams prm{};
+    size_t nstreams;
+    int spw;                                      // streams per wave of the clock kernel: 1 or 64
+    int prof_launch;                              // rr_build_opts.sync_prof_launch: 1 .. 3 = profiling brackets that launch alone
+    Carried<SyncState> st;                        // in(): what the streams so far left behind
+    DevBuf<unsigned long long> words, count;      // the signs of the most recent push; symbols of each stream in it
+    DevBuf<unsigned> idx;                         // the window-relative index of every emission, n slots per stream
+    DevBuf<float> h_in, h_syms, h_clk;            // push_host(): the host buffers' device copies
+    size_t last_n = 0;                            // the most recent push's window
+    bool fetched = true;                          // `counts` holds the most recent push's
+    std::vector<size_t> counts;
+    SymbolSync(float sps, float max_deviation, const float* taps, size_t ntaps, size_t nstreams);
+    void push_dev(const float* d_in, size_t in_stride, size_t n, float* d_syms, float* d_clock, size_t out_stride, hipStream_t s);
+    void push_host(const float* in, size_t in_stride, size_t n, float* syms, float* clock, size_t out_stride, size_t* produced);
+    const std::vector<size_t>& fetch_counts();                // waits for the most recent push
+    SyncState fetch_state(size_t stream);                     // ... and downloads one stream's state
+};
+
 }  // namespace rr

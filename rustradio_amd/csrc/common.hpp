@@ -53,6 +53,8 @@ struct BuildOpts {
     int fft_nonfinite_tiles = 0;   // FftFilter / FftFilterFloat: no reference-block pass for non-finite samples
     int host_in_staged = 0;    // page-locked input windows: > 0 staged through a copy kernel, < 0 read in place, 0 the block's default
     int fir_poly = 0;          // 0 auto, > 0 on wherever supported, < 0 off: decimating FirFilter<Complex> on decimate-first tiles
+    int sync_lanes = 0;        // SymbolSync: 0 auto, 1 / 64 streams per wave of the clock kernel
+    int sync_prof_launch = 0;  // SymbolSync: 1 .. 3 = rr_block_profile times that launch of a push alone
 };
 const BuildOpts& build_opts();
 void set_build_opts(const BuildOpts* o);   // nullptr = reset

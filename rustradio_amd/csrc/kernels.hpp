@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "nan_fix.hpp"
+#include "symsync_core.hpp"
 
 namespace rr {
 
@@ -494,6 +495,30 @@ struct HdlcArgs {
     unsigned long long* pstats;
 };
 void launch_hdlc(const HdlcArgs& a, hipStream_t s);
+
+// ---- kernels_sync.hip: SymbolSync (symbol_sync.rs:115-217) over the next n samples of nstreams independent streams
+//      (symsync_core.hpp holds the arithmetic) -------------------------------------------------------------------------------------------
+// Stream c: n samples at in + c in_stride; its symbols at syms + c out_stride, its clock values (clk may be null) at
+// clk + c out_stride, count[c] of each; its state from st_in[c] to st_out[c] (distinct).  Scratch: words[c nwords + w] holds
+// the signs of samples 64 w .. 64 w + 63 of stream c (nwords = ceil(n / 64)), idx[c n + k] the window-relative index of
+// emission k.  Three launches whatever the samples hold (launch_sync: signs, clock, gather); which = 1 .. 3 runs that one alone.
+// spw: streams per wave of the clock kernel, 1 (one active lane per wave) or 64.
+struct SyncArgs {
+    const float* in;
+    long in_stride, n, nstreams;
+    float* syms;
+    float* clk;
+    long out_stride;
+    unsigned long long* words;
+    long nwords;
+    unsigned* idx;
+    unsigned long long* count;
+    const SyncState* st_in;
+    SyncState* st_out;
+    SyncParams prm;
+    int spw;
+};
+void launch_sync(const SyncArgs& a, int which, hipStream_t s);
 
 // ---- head fix of the fused FirFilter -> FftFilter blocks (stream start only, a few hundred samples) ----------------
 // z[m] = sum_k t1[k] V[voff + m + L1 - 1 - k], m < n: the front FirFilter's first outputs (fir.rs:166-177) from the virtual stream

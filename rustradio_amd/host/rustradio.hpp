@@ -936,6 +936,54 @@ public:
     }
 };
 
+// ---- SymbolSync (src/symbol_sync.rs:46-217) x nstreams: the window form of its streams ---------------------------------------------
+// (rr_symbol_sync_create / rr_symbol_sync_push / rr_symbol_sync_push_dev / rr_symbol_sync_produced).  push() takes the next samples
+// of every stream and returns what the block's dst (and out_clock(), when asked for) receive for them; each stream's clock state
+// stays in the block from push to push.  The output always has room, so the `opos == olen` break (:150-152) has no counterpart.
+class SymbolSync {
+    detail::Handle h_;
+    size_t nstreams_;
+public:
+    struct Output { std::vector<std::vector<float>> symbols, clock; };      // one vector per stream; clock empty unless asked for
+    SymbolSync(float sps, float max_deviation, const std::vector<float>& taps, size_t nstreams = 1)
+        : h_(rr_symbol_sync_create(sps, max_deviation, taps.data(), taps.size(), nstreams)), nstreams_(nstreams) {}
+    rr_block* handle() const { return h_.h; }
+    size_t nstreams() const { return nstreams_; }
+    // rows[c] = the next samples of stream c, all of one length
+    Output push(const std::vector<std::vector<float>>& rows, bool want_clock = false) {
+        if (rows.size() != nstreams_) throw Error("SymbolSync: one row per stream");
+        const size_t n = rows.empty() ? 0 : rows[0].size();
+        std::vector<float> in(nstreams_ * n + 1), syms(nstreams_ * n + 1), clk(want_clock ? nstreams_ * n + 1 : 1);
+        for (size_t c = 0; c < nstreams_; c++) {
+            if (rows[c].size() != n) throw Error("SymbolSync: rows of one length");
+            std::copy(rows[c].begin(), rows[c].end(), in.begin() + (long)(c * n));
+        }
+        std::vector<size_t> produced(nstreams_);
+        if (rr_symbol_sync_push(h_.h, in.data(), n, n, syms.data(), want_clock ? clk.data() : nullptr, n, produced.data()) != 0)
+            throw Error(rr_last_error());
+        Output out;
+        out.symbols.resize(nstreams_);
+        if (want_clock) out.clock.resize(nstreams_);
+        for (size_t c = 0; c < nstreams_; c++) {
+            const size_t k = std::min(produced[c], n);
+            out.symbols[c].assign(syms.begin() + (long)(c * n), syms.begin() + (long)(c * n + k));
+            if (want_clock) out.clock[c].assign(clk.begin() + (long)(c * n), clk.begin() + (long)(c * n + k));
+        }
+        return out;
+    }
+    // device windows in the layout of rr_fm_multi_create's output; asynchronous on hip_stream, produced() waits
+    void push_dev(const void* d_in, size_t in_stride, size_t n, void* d_syms, void* d_clock, size_t out_stride, void* hip_stream = nullptr) {
+        if (rr_symbol_sync_push_dev(h_.h, d_in, in_stride, n, d_syms, d_clock, out_stride, hip_stream) != 0) throw Error(rr_last_error());
+    }
+    std::vector<size_t> produced() {
+        std::vector<size_t> k(nstreams_);
+        size_t total = 0;
+        if (rr_symbol_sync_produced(h_.h, k.data(), k.size(), &total) != 0) throw Error(rr_last_error());
+        return k;
+    }
+    const void* counts_dev() { return rr_symbol_sync_counts_dev(h_.h); }
+};
+
 // ---- #[rustradio(sync)] blocks: MultiplyConst (src/multiply_const.rs), FastFM (src/quadrature_demod.rs:144-165) ----------
 // work() per rustradio_macros_code/src/lib.rs:458-515; a tag at position pos < n passes through at pos.
 template <class In, class Out> class SyncBlock : public Block {
