@@ -608,6 +608,62 @@ int rr_symbol_sync_dims(const rr_block *b, size_t *streams_per_wave);
  * last_sign, and the filter history oldest first (*nhist = ntaps - 1, the first min(*nhist, cap) written) */
 int rr_debug_symbol_sync_state(rr_block *b, size_t stream, float *four, int *last_sign, float *hist, size_t cap, size_t *nhist);
 
+/* BinarySlicer (src/binary_slicer.rs:17-19) -> [XorConst(1)] -> [NrziDecode (src/nrzi.rs:36-41)] -> [Descrambler::new(mask, seed,
+ * len) (src/descrambler.rs:34-39)] -> HdlcDeframer::new(min_size, max_size) (src/hdlc_deframer.rs:80-232) x nstreams, as wired in
+ * examples/ax25-9600-rx.rs:195-215: the consumer of rr_symbol_sync.  One handle takes the ragged symbol windows of nstreams
+ * streams, with their counts read on the device, and delivers the checked frames of all of them in seven launches whatever
+ * nstreams and the symbols are; each stream's decoder and deframer state, its own stream position included, stays on the device.
+ * rr_fm_multi -> rr_symbol_sync -> rr_hdlc_receiver is the multi-channel packet receiver with no host round trip before the frames.
+ * A batch block like rr_hdlc_deframer: rr_block_work on the handle is an error.
+ * EXACT: for every stream, frames, bytes, pos, the repaired flag and the three counters are those of rr_bit_decoder_create(bit_flags,
+ * mask, seed, len, 0, 0, 0) on f32 feeding rr_hdlc_deframer_create(min_size, max_size, hdlc_flags) on that stream alone, whatever
+ * the split into pushes and whatever the other streams hold.  pos counts that stream's own symbols.  The symbols are sliced and
+ * run through the bit chain as 64-bit words inside the deframer's first kernel: no stream of one byte per bit exists.
+ * NULL + rr_last_error, said before any device is touched: "nstreams out of range" (0 or above 4096), then the refusals of
+ * rr_bit_decoder_create ("unknown bit decoder flags", "descrambler length out of range", "seed wider than the register") and of
+ * rr_hdlc_deframer_create ("unknown hdlc deframer flags", "hdlc deframer: max_size beyond 65535").
+ * Device memory: 2 * nstreams * carry_bits bytes of carried bits (rr_hdlc_receiver_dims) live as long as the handle.
+ * NOT TESTED: max_size above a few hundred with many streams; a push of 2^30 symbols. */
+typedef struct {
+    unsigned long long pos;    /* stream position (in that stream's own symbols) of the closing flag's last bit */
+    unsigned long long start;  /* first byte of the frame in the byte arena of this push (absolute: every stream owns a region) */
+    unsigned len;              /* bytes delivered (FCS stripped unless RR_HDLC_KEEP_CHECKSUM) */
+    unsigned flags;            /* bit 0: a data bit was repaired */
+    unsigned stream;
+    unsigned reserved;         /* 0 */
+} rr_hdlc_stream_frame;        /* 32 bytes */
+rr_block *rr_hdlc_receiver_create(size_t nstreams, int bit_flags /* RR_BITS_* */, unsigned long long mask, unsigned long long seed,
+                                  unsigned len, size_t min_size, size_t max_size, int hdlc_flags /* RR_HDLC_* */);
+/* stream c: the next min(d_counts[c], n_cap) f32 symbols at d_syms + c*stride, the layout rr_symbol_sync_push_dev writes.
+ * d_counts: unsigned long long[nstreams] on the device, the pointer rr_symbol_sync_counts_dev returns, read there and clamped to
+ * n_cap before it is used; NULL: every stream has n_cap.  Elements at and beyond a stream's count are never read.  A stream whose
+ * count is 0 keeps every piece of its state.  RR_ERR before any device is touched: "hdlc receiver: stride shorter than n_cap",
+ * "hdlc receiver: more than 2^30 symbols in one push" (nstreams * n_cap), "hdlc receiver: null symbols" (n_cap > 0 with a null
+ * buffer).  n_cap == 0 launches nothing, has no frames and leaves every state alone.  Asynchronous on hip_stream (used as given). */
+int rr_hdlc_receiver_push_dev(rr_block *b, const void *d_syms, size_t stride, size_t n_cap, const void *d_counts, void *hip_stream);
+/* The same with host pointers (counts may be NULL): copies symbols and counts down, runs and waits. */
+int rr_hdlc_receiver_push(rr_block *b, const float *syms, size_t stride, size_t n_cap, const size_t *counts /* [nstreams] or NULL */);
+/* The frames of all streams that ended inside the most recent push, ascending by (stream, pos).  Waits for that push, writes the
+ * first min(*total, cap) records; rec == NULL with cap == 0 only counts (the contract of rr_wpcr_results).  Everything the device
+ * wrote — the record count, every record's stream, length, place in its stream's region of the arena, position and flags, the
+ * streams' positions and counters — is checked against the host's own bounds before it is used ("hdlc receiver: ..." and no frames
+ * otherwise). */
+int rr_hdlc_receiver_frames(rr_block *b, rr_hdlc_stream_frame *rec, size_t cap, size_t *total);
+/* The byte arena of the most recent push, which rec.start indexes: *total bytes (nstreams equal regions), the first
+ * min(*total, cap) copied.  Bytes that belong to no frame are 0. */
+int rr_hdlc_receiver_frame_bytes(rr_block *b, unsigned char *out, size_t cap, size_t *total);
+/* The same arena on the device (ordered behind the push on its stream); valid until the next push.  NULL and *n_total = 0 when
+ * the most recent push was empty. */
+const void *rr_hdlc_receiver_bytes_dev(rr_block *b, size_t *n_total);
+/* decoded, crc_error, bitfixed of every stream so far; waits for the most recent push.  *total = nstreams, the first
+ * min(*total, cap) of each array written (the contract of rr_symbol_sync_produced); an array may be NULL. */
+int rr_hdlc_receiver_stats(rr_block *b, unsigned long long *decoded, unsigned long long *crc_error, unsigned long long *bitfixed,
+                           size_t cap, size_t *total);
+/* symbols every stream has taken so far (its stream position); waits for the most recent push.  Same contract. */
+int rr_hdlc_receiver_consumed(rr_block *b, unsigned long long *symbols, size_t cap, size_t *total);
+/* *tile_bits, *carry_bits: as rr_hdlc_deframer_dims, for every stream. */
+int rr_hdlc_receiver_dims(const rr_block *b, size_t *tile_bits, size_t *carry_bits);
+
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)
  * as wired in examples/ax25-1200-rx.rs:238-247: f32 in, Complex out, ONE decimating FIR with the composite

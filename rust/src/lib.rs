@@ -124,6 +124,24 @@ unsafe extern "C" {
     #[allow(dead_code)]
     fn rr_debug_symbol_sync_state(b: *mut RrBlock, stream: usize, four: *mut f32, last_sign: *mut c_int, hist: *mut f32, cap: usize,
                                   nhist: *mut usize) -> c_int;
+    // (declared for completeness: one handle takes the symbol windows of N SymbolSyncs and delivers the frames of N HdlcDeframers,
+    //  so its typed block belongs with the N-channel blocks; rr_hdlc_receiver_frames (a struct), _frame_bytes (byte pointers) and
+    //  _push (a size_t array in) have types outside this file's FFI map; not written yet)
+    #[allow(dead_code)]
+    fn rr_hdlc_receiver_create(nstreams: usize, bit_flags: c_int, mask: u64, seed: u64, len: c_uint, min_size: usize, max_size: usize,
+                               hdlc_flags: c_int) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_hdlc_receiver_push_dev(b: *mut RrBlock, d_syms: *const c_void, stride: usize, n_cap: usize, d_counts: *const c_void,
+                                 hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_hdlc_receiver_bytes_dev(b: *mut RrBlock, n_total: *mut usize) -> *const c_void;
+    #[allow(dead_code)]
+    fn rr_hdlc_receiver_stats(b: *mut RrBlock, decoded: *mut u64, crc_error: *mut u64, bitfixed: *mut u64, cap: usize,
+                              total: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_hdlc_receiver_consumed(b: *mut RrBlock, symbols: *mut u64, cap: usize, total: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_hdlc_receiver_dims(b: *const RrBlock, tile_bits: *mut usize, carry_bits: *mut usize) -> c_int;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;

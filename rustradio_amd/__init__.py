@@ -813,6 +813,91 @@ class HdlcDeframer(Block):
         return d.value, e.value, f.value
 
 
+# rr_hdlc_stream_frame
+HDLC_STREAM_FRAME = np.dtype([("pos", np.uint64), ("start", np.uint64), ("len", np.uint32), ("flags", np.uint32),
+                              ("stream", np.uint32), ("reserved", np.uint32)], align=True)
+
+
+class HdlcReceiver(Block):
+    """BinarySlicer -> [XorConst(1)] -> [NrziDecode] -> [Descrambler] -> HdlcDeframer x nstreams behind one handle
+    (rr_hdlc_receiver_create; examples/ax25-9600-rx.rs:195-215; not a stream block: work() raises): the ragged symbol windows
+    SymbolSync leaves on the device in, with their counts read there, the checked frames of all streams out.  Every stream's
+    state stays on the device between pushes.  descrambler: (mask, seed, length) or None.  See include/rustradio_amd.h."""
+
+    def __init__(self, nstreams: int, min_size: int, max_size: int, invert: bool = False, nrzi: bool = False, descrambler=None,
+                 flags: int = 0):
+        bits = (BITS_INVERT if invert else 0) | (BITS_NRZI if nrzi else 0) | (BITS_DESCRAMBLE if descrambler is not None else 0)
+        mask, seed, length = descrambler if descrambler is not None else (0, 0, 0)
+        super().__init__(lib().rr_hdlc_receiver_create(int(nstreams), bits, int(mask), int(seed), int(length), int(min_size),
+                                                       int(max_size), int(flags)), np.float32, np.uint8)
+        self.nstreams, self.min_size, self.max_size, self.flags = int(nstreams), int(min_size), int(max_size), int(flags)
+
+    def dims(self):
+        """-> (tile_bits, carry_bits) (rr_hdlc_receiver_dims)"""
+        t, c = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_hdlc_receiver_dims(self._h, C.byref(t), C.byref(c)) != 0:
+            raise RuntimeError(last_error())
+        return t.value, c.value
+
+    def push_dev(self, d_syms: int, stride: int, n_cap: int, d_counts=None, stream: int = 0) -> None:
+        """rr_hdlc_receiver_push_dev: stream c's next min(d_counts[c], n_cap) symbols at d_syms + c * stride (raw device pointers;
+        d_counts: unsigned long long[nstreams], SymbolSync.counts_dev(), or None: n_cap each); asynchronous on `stream`;
+        frames() waits"""
+        if lib().rr_hdlc_receiver_push_dev(self._h, C.c_void_p(d_syms) if d_syms else None, int(stride), int(n_cap),
+                                           C.c_void_p(d_counts) if d_counts else None, C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+
+    def push(self, syms, counts=None):
+        """rr_hdlc_receiver_push on a host array of shape (nstreams, n_cap) (or (n_cap,) for one stream), of which stream c
+        holds counts[c] symbols (None: n_cap) -> result()"""
+        a = np.ascontiguousarray(syms, np.float32)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        if a.ndim != 2 or a.shape[0] != self.nstreams:
+            raise ValueError("HdlcReceiver.push: one row per stream")
+        n = a.shape[1]
+        k = None
+        if counts is not None:
+            if len(counts) != self.nstreams:
+                raise ValueError("HdlcReceiver.push: one count per stream")
+            k = (C.c_size_t * self.nstreams)(*[int(v) for v in counts])
+        if lib().rr_hdlc_receiver_push(self._h, _ptr(a) if n else None, n, n, k) != 0:
+            raise ValueError(last_error())
+        return self.result()
+
+    def frames(self) -> np.ndarray:
+        """-> HDLC_STREAM_FRAME per frame of the most recent push, ascending by (stream, pos) (rr_hdlc_receiver_frames; waits)"""
+        return _fetch(lib().rr_hdlc_receiver_frames, self._h, HDLC_STREAM_FRAME)[0]
+
+    def frame_bytes(self) -> np.ndarray:
+        """-> the byte arena of the most recent push, which frames()["start"] indexes (rr_hdlc_receiver_frame_bytes; waits)"""
+        return _fetch(lib().rr_hdlc_receiver_frame_bytes, self._h, np.uint8)[0]
+
+    def bytes_dev(self):
+        """-> (raw device pointer or None, bytes) of the same arena (rr_hdlc_receiver_bytes_dev); valid until the next push"""
+        n = C.c_size_t(0)
+        p = lib().rr_hdlc_receiver_bytes_dev(self._h, C.byref(n))
+        return p, n.value
+
+    def result(self):
+        """frames() and frame_bytes() of the most recent push -> per stream [(pos, bytes, fixed)], as HdlcDeframer.result()"""
+        rec = self.frames()
+        arena = self.frame_bytes() if len(rec) else np.zeros(0, np.uint8)
+        out = [[] for _ in range(self.nstreams)]
+        for r in rec:
+            out[int(r["stream"])].append((int(r["pos"]), arena[int(r["start"]):int(r["start"]) + int(r["len"])].tobytes(),
+                                          bool(r["flags"] & 1)))
+        return out
+
+    def stats(self) -> np.ndarray:
+        """-> uint64[nstreams, 3]: decoded, crc_error, bitfixed of every stream so far (rr_hdlc_receiver_stats; waits)"""
+        d, e, f = _fetch(lib().rr_hdlc_receiver_stats, self._h, np.uint64, np.uint64, np.uint64)
+        return np.stack([d, e, f], axis=1)
+
+    def consumed(self) -> np.ndarray:
+        """-> uint64[nstreams]: symbols every stream has taken so far (rr_hdlc_receiver_consumed; waits)"""
+        return _fetch(lib().rr_hdlc_receiver_consumed, self._h, np.uint64)[0]
+
+
 class SymbolSync(Block):
     """SymbolSync::new(src, sps, max_deviation, TedZeroCrossing, IirFilter::new(taps)) x nstreams behind one handle
     (rr_symbol_sync_create; src/symbol_sync.rs:46-217; not a stream block: work() raises): the next n samples of each stream in,

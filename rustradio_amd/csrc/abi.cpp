@@ -13,6 +13,7 @@
 #include "frame_core.hpp"
 #include "frame_host.hpp"
 #include "hdlc_host.hpp"
+#include "hdlcrx_host.hpp"
 #include "pdu_host.hpp"
 #include "symsync_host.hpp"
 #include "taps.hpp"
@@ -82,6 +83,7 @@ template <class T> static T* as(const rr_block* b, const char* what, const char*
 }
 static const char NOT_WPCR[] = "not a wpcr handle", NOT_PDU[] = "not a stream_to_pdu handle", NOT_FRAMER[] = "not an hdlc framer handle";
 static const char NOT_DEFRAMER[] = "not an hdlc deframer handle", NOT_SYNC[] = "not a symbol sync handle";
+static const char NOT_RECEIVER[] = "not an hdlc receiver handle";
 // a fetched list of (pos << shift) | val entries into the caller's two arrays
 template <class E> static void unpack(const std::vector<E>& e, unsigned shift, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
     *total = e.size();
@@ -486,6 +488,71 @@ int rr_hdlc_stats(rr_block* b, unsigned long long* decoded, unsigned long long* 
 int rr_hdlc_deframer_dims(const rr_block* b, size_t* tile_bits, size_t* carry_bits) {
     auto* d = as<rr::HdlcDeframer>(b, "rr_hdlc_deframer_dims", NOT_DEFRAMER);
     if (!d || !tile_bits || !carry_bits) { if (d) rr::set_last_error("rr_hdlc_deframer_dims: null argument"); return RR_ERR; }
+    *tile_bits = rr::HDLC_T;
+    *carry_bits = rr::hdlc_carry_bits(d->max_size);
+    return 0;
+}
+rr_block* rr_hdlc_receiver_create(size_t nstreams, int bit_flags, unsigned long long mask, unsigned long long seed, unsigned len,
+                                  size_t min_size, size_t max_size, int hdlc_flags) {
+    if (const char* e = rr::hdlcrx_check_create(nstreams, bit_flags, seed, len, min_size, max_size, hdlc_flags)) return refuse_create(e);
+    return make_block([&] { return new rr::HdlcReceiver(nstreams, bit_flags, mask, seed, len, min_size, max_size, hdlc_flags); });
+}
+int rr_hdlc_receiver_push_dev(rr_block* b, const void* d_syms, size_t stride, size_t n_cap, const void* d_counts, void* hip_stream) {
+    auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_push_dev", NOT_RECEIVER);
+    if (!d) return RR_ERR;
+    if (const char* e = rr::hdlcrx_check_push(d->nstreams, d_syms, stride, n_cap)) { rr::set_last_error(e); return RR_ERR; }   // before any device is touched
+    return on_device(d, hip_stream, [&](hipStream_t s) {
+        d->push_dev(static_cast<const float*>(d_syms), stride, n_cap, static_cast<const unsigned long long*>(d_counts), s);
+    });
+}
+int rr_hdlc_receiver_push(rr_block* b, const float* syms, size_t stride, size_t n_cap, const size_t* counts) {
+    auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_push", NOT_RECEIVER);
+    if (!d) return RR_ERR;
+    if (const char* e = rr::hdlcrx_check_push(d->nstreams, syms, stride, n_cap)) { rr::set_last_error(e); return RR_ERR; }
+    return guarded([&] { d->push_host(syms, stride, n_cap, counts); });
+}
+int rr_hdlc_receiver_frames(rr_block* b, rr_hdlc_stream_frame* rec, size_t cap, size_t* total) {
+    auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_frames", NOT_RECEIVER);
+    if (!d) return RR_ERR;
+    if (!total || (cap && !rec)) { rr::set_last_error("rr_hdlc_receiver_frames: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] { rr::hdlcrx_copy_frames(d->fetch_frames(), rec, cap, total); });
+}
+int rr_hdlc_receiver_frame_bytes(rr_block* b, unsigned char* out, size_t cap, size_t* total) {
+    auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_frame_bytes", NOT_RECEIVER);
+    if (!d) return RR_ERR;
+    if (!total || (cap && !out)) { rr::set_last_error("rr_hdlc_receiver_frame_bytes: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] { rr::hdlc_copy_bytes(d->fetch_bytes(), out, cap, total); });
+}
+const void* rr_hdlc_receiver_bytes_dev(rr_block* b, size_t* n_total) {
+    auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_bytes_dev", NOT_RECEIVER);
+    if (n_total) *n_total = d ? d->arena_len() : 0;
+    return d ? d->arena_dev() : nullptr;
+}
+int rr_hdlc_receiver_stats(rr_block* b, unsigned long long* decoded, unsigned long long* crc_error, unsigned long long* bitfixed, size_t cap,
+                           size_t* total) {
+    auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_stats", NOT_RECEIVER);
+    if (!d) return RR_ERR;
+    if (!total) { rr::set_last_error("rr_hdlc_receiver_stats: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] {
+        const std::vector<unsigned long long> s = d->fetch_stats();
+        rr::hdlcrx_copy_u64(s, 0, 3, decoded, cap, total);
+        rr::hdlcrx_copy_u64(s, 1, 3, crc_error, cap, total);
+        rr::hdlcrx_copy_u64(s, 2, 3, bitfixed, cap, total);
+    });
+}
+int rr_hdlc_receiver_consumed(rr_block* b, unsigned long long* symbols, size_t cap, size_t* total) {
+    auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_consumed", NOT_RECEIVER);
+    if (!d) return RR_ERR;
+    if (!total || (cap && !symbols)) { rr::set_last_error("rr_hdlc_receiver_consumed: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] { rr::hdlcrx_copy_u64(d->fetch_consumed(), 0, 1, symbols, cap, total); });
+}
+int rr_hdlc_receiver_dims(const rr_block* b, size_t* tile_bits, size_t* carry_bits) {
+    auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_dims", NOT_RECEIVER);
+    if (!d || !tile_bits || !carry_bits) { if (d) rr::set_last_error("rr_hdlc_receiver_dims: null argument"); return RR_ERR; }
     *tile_bits = rr::HDLC_T;
     *carry_bits = rr::hdlc_carry_bits(d->max_size);
     return 0;

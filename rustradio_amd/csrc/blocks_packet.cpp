@@ -1,5 +1,5 @@
 // blocks_packet.cpp — host side of the packet-side blocks (blocks_packet.hpp): the sync blocks, the burst and bit blocks, and the
-// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, SymbolSync).  Citations are to the reference's src, as in blocks.cpp.
+// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, SymbolSync, HdlcReceiver).  Citations are to the reference's src, as in blocks.cpp.
 #include "blocks_packet.hpp"
 
 #include <algorithm>
@@ -10,6 +10,8 @@
 #include "frame_core.hpp"
 #include "frame_host.hpp"
 #include "hdlc_host.hpp"
+#include "hdlcrx_core.hpp"
+#include "hdlcrx_host.hpp"
 #include "pdu_host.hpp"
 #include "symsync_host.hpp"
 
@@ -143,11 +145,7 @@ const std::vector<unsigned long long>& BurstDetector::fetch_edges() {
 
 // ---- BinarySlicer, NrziDecode, Descrambler, CorrelateAccessCodeTag and their fusion (kernels_bits.hip) ---------------------------
 const char* bits_check(int flags, unsigned long long seed, unsigned len, unsigned code_len) {
-    if (flags & ~(RR_BITS_INVERT | RR_BITS_NRZI | RR_BITS_DESCRAMBLE)) return "unknown bit decoder flags";
-    if (flags & RR_BITS_DESCRAMBLE) {
-        if (len >= 64) return "descrambler length out of range";                       // descrambler.rs:22 (assert)
-        if (len < 63 && seed >> (len + 1)) return "seed wider than the register";
-    }
+    if (const char* e = hdlcrx_check_bits(flags, seed, len)) return e;                 // (the stages HdlcReceiver runs as well)
     if (code_len > 64) return "access code longer than 64 bits";
     return nullptr;
 }
@@ -725,6 +723,158 @@ SyncState SymbolSync::fetch_state(size_t c) {
     SyncState s{};
     stage_download_sync(&s, st.in() + c, sizeof s, stream);
     return s;
+}
+
+// ---- HdlcReceiver (binary_slicer.rs, nrzi.rs, descrambler.rs, hdlc_deframer.rs; kernels_hdlcrx.hip) -------------------------------------
+static_assert(sizeof(HdlcRxRec) == sizeof(rr_hdlc_stream_frame) && offsetof(HdlcRxRec, pos) == offsetof(rr_hdlc_stream_frame, pos) &&
+              offsetof(HdlcRxRec, start) == offsetof(rr_hdlc_stream_frame, start) && offsetof(HdlcRxRec, len) == offsetof(rr_hdlc_stream_frame, len) &&
+              offsetof(HdlcRxRec, flags) == offsetof(rr_hdlc_stream_frame, flags) && offsetof(HdlcRxRec, stream) == offsetof(rr_hdlc_stream_frame, stream),
+              "HdlcRxRec is rr_hdlc_stream_frame");
+HdlcReceiver::HdlcReceiver(size_t ns, int bit_flags, unsigned long long mask, unsigned long long seed, unsigned len, size_t mn, size_t mx,
+                           int fl)
+    : BatchBlock("HdlcReceiver", 4, 1, "HdlcReceiver delivers frames: rr_hdlc_receiver_push / rr_hdlc_receiver_push_dev"),
+      nstreams(ns), min_size(mn), max_size(mx), flags(fl) {
+    if (const char* e = hdlcrx_check_create(ns, bit_flags, seed, len, mn, mx, fl)) throw Error(e);
+    cfg.invert = bit_flags & RR_BITS_INVERT ? 1 : 0;
+    cfg.nrzi = bit_flags & RR_BITS_NRZI ? 1 : 0;
+    unsigned long long one[RX_ST_N] = {0, 0, 0};                      // last: 0 (nrzi.rs:32-33); no symbol taken yet
+    if (bit_flags & RR_BITS_DESCRAMBLE) {
+        cfg.dmask = rx_dmask(mask, len);
+        one[RX_ST_DHIST] = rx_dhist0(seed, len);                      // before the stream the register is the seed
+    }
+    std::vector<unsigned long long> b0(ns * RX_ST_N);
+    for (size_t c = 0; c < ns; c++) std::copy(one, one + RX_ST_N, b0.begin() + c * RX_ST_N);
+    bst.upload(b0.data(), b0.size(), stream);
+    // Unsynced(0xff) (hdlc_deframer.rs:28-32): 8 ones nobody asks about in front of every stream, and every flag is seen whole
+    HdlcState init{};
+    init.count = HDLC_HALO;
+    init.state = HDLC_U;
+    const std::vector<HdlcState> all(ns, init);
+    st.upload(all.data(), ns, stream);
+    const size_t cb = ns * hdlc_carry_bits(mx);
+    for (auto& b : cbits.buf) { b.reserve(cb); RR_HIP(hipMemsetAsync(b.p, 1, cb, stream)); }
+    carry = HDLC_HALO;
+    etotal.reserve(ns); pstats.reserve(3 * ns); fin.reserve(ns); count.reserve(1);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void HdlcReceiver::push_dev(const float* d_syms, size_t stride, size_t n_cap, const unsigned long long* d_counts, hipStream_t s) {
+    if (const char* e = hdlcrx_check_push(nstreams, d_syms, stride, n_cap)) throw Error(e);
+    frames.clear();
+    bytes.clear();
+    fetched = bfetched = true;                 // a push of no symbols has no frames and leaves every state alone
+    last_cap = n_cap;
+    if (!n_cap) return;
+    b_carry = carry;
+    const HdlcRxBounds bd = hdlcrx_bounds(nstreams, carry, n_cap);
+    HdlcRxArgs r{};
+    r.syms = d_syms; r.stride = (long)stride; r.n_cap = (long)n_cap; r.nstreams = (long)nstreams; r.counts = d_counts;
+    r.invert = cfg.invert; r.nrzi = cfg.nrzi; r.dmask = cfg.dmask;
+    r.bst_in = bst.in(); r.bst_out = bst.out();
+    HdlcArgs& a = r.h;
+    a.cin = cbits.in(); a.cout = cbits.out(); a.st_in = st.in(); a.st_out = st.out();
+    a.carry_cap = (long)hdlc_carry_bits(max_size);
+    a.nv_max = (long)bd.one.nv;
+    a.ntiles = (long)((bd.one.nv + HDLC_T - 1) / HDLC_T);
+    a.min_size = min_size; a.max_size = max_size;
+    a.keep = (flags & RR_HDLC_KEEP_CHECKSUM) != 0; a.fix = (flags & RR_HDLC_FIX_BITS) != 0;
+    const size_t nwords = (size_t)a.ntiles * (HDLC_T / 64) + 1, ecap = bd.one.nv / 7 + 2, nblocks = (ecap + HDLC_GB - 1) / HDLC_GB;
+    r.p_words = (long)nwords; r.p_tiles = a.ntiles; r.p_ends = (long)ecap; r.p_blocks = (long)nblocks;
+    r.p_carry = a.carry_cap; r.p_arena = (long)bd.one.arena;
+    const size_t ns = nstreams;
+    raw.reserve(ns * nwords); fl.reserve(ns * nwords); ab.reserve(ns * nwords); sf.reserve(ns * nwords);
+    tilecnt.reserve(ns * (size_t)a.ntiles); offs.reserve(ns * (size_t)a.ntiles);
+    ends.reserve(ns * ecap); gmap.reserve(ns * ecap); pmap.reserve(ns * ecap); bmap.reserve(ns * nblocks); bstate.reserve(ns * nblocks);
+    arena.reserve(std::max<size_t>(bd.arena, 1));
+    recs.reserve(std::max<size_t>(bd.frames, 1));
+    a.raw = raw.p; a.fl = fl.p; a.ab = ab.p; a.sf = sf.p; a.tilecnt = tilecnt.p; a.offs = offs.p;
+    a.etotal = etotal.p; a.count = count.p; a.pstats = pstats.p;
+    a.ends = ends.p; a.ends_cap = (long)ecap; a.gmap = gmap.p; a.pmap = pmap.p; a.bmap = bmap.p; a.bstate = bstate.p; a.fin = fin.p;
+    a.arena = arena.p; a.arena_cap = (long)bd.one.arena; a.rec_cap = (long)bd.frames;
+    r.recs = recs.p;
+    prof_begin(s);
+    if (bd.arena) RR_HIP(hipMemsetAsync(arena.p, 0, bd.arena, s));
+    launch_hdlcrx(r, s);
+    prof_end(s);
+    bst.flip();
+    st.flip();
+    cbits.flip();
+    carry = hdlc_next_carry(carry, n_cap, max_size);
+    fetched = bfetched = false;
+}
+void HdlcReceiver::push_host(const float* syms, size_t stride, size_t n_cap, const size_t* counts) {
+    host_call([&] {
+        if (const char* e = hdlcrx_check_push(nstreams, syms, stride, n_cap)) throw Error(e);
+        if (n_cap) {
+            // only what the counts cover is read from the caller's buffer, as on the device
+            h_syms.reserve(nstreams * n_cap);
+            std::vector<unsigned long long> k(nstreams, n_cap);
+            for (size_t c = 0; c < nstreams; c++) {
+                if (counts) k[c] = std::min<unsigned long long>(counts[c], n_cap);
+                if (k[c]) hstage().h2d(h_syms.p + c * n_cap, syms + c * stride, (size_t)k[c] * sizeof(float), stream);
+            }
+            if (counts) {
+                h_counts.reserve(nstreams);
+                hstage().h2d(h_counts.p, k.data(), nstreams * sizeof(unsigned long long), stream);
+            }
+        }
+        push_dev(h_syms.p, n_cap, n_cap, counts ? h_counts.p : nullptr, stream);
+    });
+}
+size_t HdlcReceiver::arena_len() const { return last_cap ? hdlcrx_bounds(nstreams, b_carry, last_cap).arena : 0; }
+const std::vector<rr_hdlc_stream_frame>& HdlcReceiver::fetch_frames() {
+    settle();
+    if (!fetched) {
+        fetched = true;                        // (a refused push has no frames: the refusal is not repeated)
+        const HdlcRxBounds bd = hdlcrx_bounds(nstreams, b_carry, last_cap);
+        unsigned long long k = 0;
+        stage_download_sync(&k, count.p, sizeof k, stream);
+        if (const char* e = hdlcrx_check_count(k, bd)) throw Error(e);
+        std::vector<rr_hdlc_stream_frame> r((size_t)k);
+        if (k) stage_download_sync(r.data(), recs.p, (size_t)k * sizeof(rr_hdlc_stream_frame), stream);
+        // the pairs' other halves hold what the push started from
+        std::vector<HdlcState> now(nstreams), before(nstreams);
+        stage_download_sync(now.data(), st.in(), nstreams * sizeof(HdlcState), stream);
+        stage_download_sync(before.data(), st.out(), nstreams * sizeof(HdlcState), stream);
+        std::vector<unsigned long long> bnow(nstreams * RX_ST_N), bbefore(nstreams * RX_ST_N);
+        stage_download_sync(bnow.data(), bst.in(), bnow.size() * sizeof(unsigned long long), stream);
+        stage_download_sync(bbefore.data(), bst.out(), bbefore.size() * sizeof(unsigned long long), stream);
+        std::vector<unsigned long long> p0(nstreams), p1(nstreams), s0(3 * nstreams), s1(3 * nstreams);
+        for (size_t c = 0; c < nstreams; c++) {
+            p0[c] = bbefore[c * RX_ST_N + RX_ST_POS]; p1[c] = bnow[c * RX_ST_N + RX_ST_POS];
+            for (int q = 0; q < 3; q++) { s0[3 * c + q] = before[c].stats[q]; s1[3 * c + q] = now[c].stats[q]; }
+        }
+        std::vector<size_t> moved;
+        if (const char* e = hdlcrx_clamp_consumed(p0.data(), p1.data(), nstreams, last_cap, moved)) throw Error(e);
+        if (const char* e = hdlcrx_validate(r, bd, max_size, p0.data(), moved.data(), s0.data(), s1.data())) throw Error(e);
+        frames.swap(r);
+    }
+    return frames;
+}
+const std::vector<unsigned char>& HdlcReceiver::fetch_bytes() {
+    fetch_frames();                            // (waits; the arena is read only behind a push whose records stood the checks)
+    if (!bfetched) {
+        const size_t n = arena_len();
+        bytes.assign(n, 0);
+        if (n) stage_download_sync(bytes.data(), arena.p, n, stream);
+        bfetched = true;
+    }
+    return bytes;
+}
+std::vector<unsigned long long> HdlcReceiver::fetch_stats() {
+    settle();
+    std::vector<HdlcState> now(nstreams);
+    stage_download_sync(now.data(), st.in(), nstreams * sizeof(HdlcState), stream);
+    std::vector<unsigned long long> out(3 * nstreams);
+    for (size_t c = 0; c < nstreams; c++)
+        for (int q = 0; q < 3; q++) out[3 * c + q] = now[c].stats[q];
+    return out;
+}
+std::vector<unsigned long long> HdlcReceiver::fetch_consumed() {
+    settle();
+    std::vector<unsigned long long> b(nstreams * RX_ST_N), out(nstreams);
+    stage_download_sync(b.data(), bst.in(), b.size() * sizeof(unsigned long long), stream);
+    for (size_t c = 0; c < nstreams; c++) out[c] = b[c * RX_ST_N + RX_ST_POS];
+    return out;
 }
 
 }  // namespace rr

@@ -316,4 +316,41 @@ struct SymbolSync : BatchBlock {
     SyncState fetch_state(size_t stream);                     // ... and downloads one stream's state
 };
 
+// BinarySlicer -> [XorConst(1)] -> [NrziDecode] -> [Descrambler] -> HdlcDeframer x nstreams over ragged windows of nstreams f32
+// symbol streams (kernels_hdlcrx.hip): no stream protocol (work_dev is an error).  Each stream's state between pushes — the bit
+// chain's (RX_ST_*), the deframer's (HdlcState), its carried bits, its own stream position — stays on the device.  The host keeps
+// one upper bound of the carried bits for all streams and sizes everything it reads back from that, nstreams and n_cap
+// (hdlcrx_host.hpp).
+struct HdlcReceiver : BatchBlock {
+    size_t nstreams, min_size, max_size;
+    int flags;                                    // RR_HDLC_*
+    BitsCfg cfg{};                                // invert, nrzi, dmask
+    Carried<unsigned long long> bst;              // in(): RX_ST_N words per stream
+    Carried<HdlcState> st;                        // in(): one per stream
+    Carried<unsigned char> cbits;                 // in(): hdlc_carry_bits(max_size) bytes per stream, one carried bit each
+    size_t carry = 0;                             // the carried bits of any stream, at most
+    DevBuf<unsigned long long> raw, fl, ab, sf, offs, etotal, pstats, count;
+    DevBuf<unsigned> tilecnt, ends;
+    DevBuf<unsigned char> gmap, pmap, bmap, bstate, arena;
+    DevBuf<int> fin;
+    DevBuf<HdlcRxRec> recs;
+    DevBuf<float> h_syms;                         // push_host(): the host buffers' device copies
+    DevBuf<unsigned long long> h_counts;
+    size_t last_cap = 0;                          // the most recent push: its n_cap and its bounds
+    size_t b_carry = 0;
+    bool fetched = true, bfetched = true;         // `frames` / `bytes` hold the most recent push's
+    std::vector<rr_hdlc_stream_frame> frames;     // ... ascending by (stream, pos)
+    std::vector<unsigned char> bytes;
+    HdlcReceiver(size_t nstreams, int bit_flags, unsigned long long mask, unsigned long long seed, unsigned len, size_t min_size,
+                 size_t max_size, int hdlc_flags);
+    void push_dev(const float* d_syms, size_t stride, size_t n_cap, const unsigned long long* d_counts, hipStream_t s);
+    void push_host(const float* syms, size_t stride, size_t n_cap, const size_t* counts);
+    const std::vector<rr_hdlc_stream_frame>& fetch_frames();  // waits for the most recent push
+    const std::vector<unsigned char>& fetch_bytes();
+    size_t arena_len() const;
+    const unsigned char* arena_dev() const { return arena_len() ? arena.p : nullptr; }
+    std::vector<unsigned long long> fetch_stats();            // 3 per stream
+    std::vector<unsigned long long> fetch_consumed();         // 1 per stream
+};
+
 }  // namespace rr

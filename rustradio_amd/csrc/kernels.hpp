@@ -496,6 +496,34 @@ struct HdlcArgs {
 };
 void launch_hdlc(const HdlcArgs& a, hipStream_t s);
 
+// ---- kernels_hdlcrx.hip: BinarySlicer -> [XorConst(1)] -> [NrziDecode] -> [Descrambler] -> HdlcDeframer over the next symbols of
+//      nstreams independent streams (hdlcrx_core.hpp holds the bit chain in word form, hdlc_body.hpp the deframer's kernels) -----
+// Stream c: min(counts ? counts[c] : n_cap, n_cap) f32 symbols at syms + c stride, read on the device; nothing at or beyond
+// that count is read.  `h` is stream 0's view with the HOST's bounds in nv_max / ntiles / ends_cap / arena_cap (one number serves
+// all streams) and a null `bits`; stream c's buffers stand c pitches further on: p_words words of raw / fl / ab / sf, p_tiles of
+// tilecnt / offs, p_ends of ends / gmap / pmap, p_blocks of bmap / bstate, p_carry bytes of cin / cout, p_arena bytes of arena,
+// one etotal / fin / st_in / st_out and three pstats each.  bst_in / bst_out: RX_ST_N words per stream (hdlcrx_core.hpp).
+// h.count is ONE counter and recs ONE list of rec_cap records for all streams; a record's start is absolute (c p_arena + ...).
+// The seven launches of launch_hdlc with the stream as the grid's y, whatever nstreams and the symbols are; n_cap == 0 launches
+// nothing.  A stream with no symbols has its state copied from the in to the out buffers.
+struct HdlcRxRec {                            // rr_hdlc_stream_frame
+    unsigned long long pos, start;
+    unsigned len, flags, stream, reserved;
+};
+struct HdlcRxArgs {
+    const float* syms;
+    long stride, n_cap, nstreams;
+    const unsigned long long* counts;         // may be null: every stream has n_cap
+    int invert, nrzi;
+    unsigned long long dmask;                 // BitsCfg::dmask
+    const unsigned long long* bst_in;
+    unsigned long long* bst_out;
+    HdlcArgs h;
+    long p_words, p_tiles, p_ends, p_blocks, p_carry, p_arena;
+    HdlcRxRec* recs;
+};
+void launch_hdlcrx(const HdlcRxArgs& a, hipStream_t s);
+
 // ---- kernels_sync.hip: SymbolSync (symbol_sync.rs:115-217) over the next n samples of nstreams independent streams
 //      (symsync_core.hpp holds the arithmetic) -------------------------------------------------------------------------------------------
 // Stream c: n samples at in + c in_stride; its symbols at syms + c out_stride, its clock values (clk may be null) at

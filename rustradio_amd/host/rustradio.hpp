@@ -984,6 +984,86 @@ public:
     const void* counts_dev() { return rr_symbol_sync_counts_dev(h_.h); }
 };
 
+// ---- BinarySlicer -> [XorConst(1)] -> [NrziDecode] -> [Descrambler] -> HdlcDeframer x nstreams: the consumer of SymbolSync ----------
+// (rr_hdlc_receiver_create / _push / _push_dev / _frames / _frame_bytes / _stats / _consumed).  push() takes the next symbols of
+// every stream (rows of any lengths) and returns, per stream, what HdlcDeframer's dst receives for them; push_dev() takes
+// SymbolSync's device windows and counts_dev() as they are.  Every stream's state stays in the block from push to push.
+class HdlcReceiver {
+    detail::Handle h_;
+    size_t nstreams_;
+public:
+    using Packet = HdlcDeframer::Packet;
+    using Stats = HdlcDeframer::Stats;
+    // bit_flags: RR_BITS_*; mask, seed, len: Descrambler::new's (read with RR_BITS_DESCRAMBLE only)
+    HdlcReceiver(size_t nstreams, int bit_flags, unsigned long long mask, unsigned long long seed, unsigned len, size_t min_size,
+                 size_t max_size, bool keep_checksum = false, bool fix_bits = false)
+        : h_(rr_hdlc_receiver_create(nstreams, bit_flags, mask, seed, len, min_size, max_size,
+                                     (keep_checksum ? RR_HDLC_KEEP_CHECKSUM : 0) | (fix_bits ? RR_HDLC_FIX_BITS : 0))),
+          nstreams_(nstreams) {}
+    rr_block* handle() const { return h_.h; }
+    size_t nstreams() const { return nstreams_; }
+    // the frames of the most recent push, per stream, in stream order (waits for it)
+    std::vector<std::vector<Packet>> packets(std::vector<std::vector<bool>>* repaired = nullptr) {
+        size_t n = 0, nb = 0;
+        if (rr_hdlc_receiver_frames(h_.h, nullptr, 0, &n) != 0) throw Error(rr_last_error());
+        std::vector<rr_hdlc_stream_frame> rec(n + 1);
+        if (n && rr_hdlc_receiver_frames(h_.h, rec.data(), n, &n) != 0) throw Error(rr_last_error());
+        if (rr_hdlc_receiver_frame_bytes(h_.h, nullptr, 0, &nb) != 0) throw Error(rr_last_error());
+        std::vector<uint8_t> arena(nb + 1);
+        if (n && nb && rr_hdlc_receiver_frame_bytes(h_.h, arena.data(), nb, &nb) != 0) throw Error(rr_last_error());
+        std::vector<std::vector<Packet>> out(nstreams_);
+        if (repaired) repaired->assign(nstreams_, {});
+        for (size_t i = 0; i < n; i++) {
+            if (rec[i].stream >= nstreams_) throw Error("HdlcReceiver: no such stream");
+            if (rec[i].start > nb || rec[i].len > nb - rec[i].start) throw Error("HdlcReceiver: frame outside the arena");
+            Packet p;
+            p.first.assign(arena.begin() + (long)rec[i].start, arena.begin() + (long)(rec[i].start + rec[i].len));
+            p.second.emplace_back(0, "packet_pos", (uint64_t)rec[i].pos);
+            out[rec[i].stream].push_back(std::move(p));
+            if (repaired) (*repaired)[rec[i].stream].push_back((rec[i].flags & 1u) != 0);
+        }
+        return out;
+    }
+    // rows[c] = the next symbols of stream c
+    std::vector<std::vector<Packet>> push(const std::vector<std::vector<float>>& rows, std::vector<std::vector<bool>>* repaired = nullptr) {
+        if (rows.size() != nstreams_) throw Error("HdlcReceiver: one row per stream");
+        size_t n_cap = 0;
+        for (auto& r : rows) n_cap = std::max(n_cap, r.size());
+        std::vector<float> in(nstreams_ * n_cap + 1);
+        std::vector<size_t> counts(nstreams_);
+        for (size_t c = 0; c < nstreams_; c++) {
+            std::copy(rows[c].begin(), rows[c].end(), in.begin() + (long)(c * n_cap));
+            counts[c] = rows[c].size();
+        }
+        if (rr_hdlc_receiver_push(h_.h, in.data(), n_cap, n_cap, counts.data()) != 0) throw Error(rr_last_error());
+        return packets(repaired);
+    }
+    // device windows in the layout SymbolSync::push_dev writes, d_counts = SymbolSync::counts_dev() (or null: n_cap each);
+    // asynchronous on hip_stream, packets() waits
+    void push_dev(const void* d_syms, size_t stride, size_t n_cap, const void* d_counts, void* hip_stream = nullptr) {
+        if (rr_hdlc_receiver_push_dev(h_.h, d_syms, stride, n_cap, d_counts, hip_stream) != 0) throw Error(rr_last_error());
+    }
+    std::vector<Stats> stats() {
+        std::vector<unsigned long long> d(nstreams_), e(nstreams_), f(nstreams_);
+        size_t total = 0;
+        if (rr_hdlc_receiver_stats(h_.h, d.data(), e.data(), f.data(), nstreams_, &total) != 0) throw Error(rr_last_error());
+        std::vector<Stats> out(nstreams_);
+        for (size_t c = 0; c < nstreams_; c++) out[c] = Stats{d[c], e[c], f[c]};
+        return out;
+    }
+    std::vector<unsigned long long> consumed() {
+        std::vector<unsigned long long> k(nstreams_);
+        size_t total = 0;
+        if (rr_hdlc_receiver_consumed(h_.h, k.data(), k.size(), &total) != 0) throw Error(rr_last_error());
+        return k;
+    }
+    size_t carry_bits() const {
+        size_t t = 0, c = 0;
+        if (rr_hdlc_receiver_dims(h_.h, &t, &c) != 0) throw Error(rr_last_error());
+        return c;
+    }
+};
+
 // ---- #[rustradio(sync)] blocks: MultiplyConst (src/multiply_const.rs), FastFM (src/quadrature_demod.rs:144-165) ----------
 // work() per rustradio_macros_code/src/lib.rs:458-515; a tag at position pos < n passes through at pos.
 template <class In, class Out> class SyncBlock : public Block {
