@@ -112,6 +112,17 @@ def states_equal(a, b):
             and np.array_equal(np.asarray(a["hist"], np.float32).view(np.uint32), np.asarray(b["hist"], np.float32).view(np.uint32)))
 
 
+def states_match(a, b):
+    """states_equal, but a field that is NaN in one must be NaN in the other, whatever its payload and sign bits: IEEE 754 leaves
+    the payload of a NaN an operation makes to the implementation, and the device and numpy differ in it"""
+    def same(x, y):
+        x, y = np.asarray(x, np.float32).ravel(), np.asarray(y, np.float32).ravel()
+        nx, ny = np.isnan(x), np.isnan(y)
+        return x.shape == y.shape and np.array_equal(nx, ny) and np.array_equal(x.view(np.uint32)[~nx], y.view(np.uint32)[~ny])
+    f = ("clock", "stream_pos", "last_sym_boundary_pos", "next_sym_middle", "hist")
+    return all(same(a[k], b[k]) for k in f) and a["last_sign"] == b["last_sign"]
+
+
 def bits_equal(a, b):
     a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
@@ -121,6 +132,14 @@ def bits_equal(a, b):
 AX25_9600 = (50000.0 / 9600.0, 0.1, [0.0001, 0.99999999])      # examples/ax25-9600-rx.rs:186-193
 AX25_1200 = (50000.0 / 1200.0, 0.5, [0.0001, 0.99999999])
 ADAPTIVE_9600 = (50000.0 / 9600.0, 0.5, [0.1, 0.9])
+# ---- the edges of sps: nearly every sample a symbol (the smallest f32 above 1 among them), and a handful of symbols ------------
+SPS_EDGES = {"1.25": (1.25, 0.625, [0.5, 0.5]), "1.5": (1.5, 0.75, [0.1, 0.9]), "2": (2.0, 0.0, [1.0]),
+             "200": (200.0, 20.0, [0.2, 0.5, 0.3]), "1+ulp": (float(np.nextafter(F(1.0), F(2.0))), 0.5, [0.5, 0.5])}
+SPS_EDGE_N = 3000
+SPS_EDGE_PUSHES = (1, 63, 64, 65, 0, SPS_EDGE_N - 193)
+# taps that overflow at the first clock update: 5 * 3e38 is +Inf, +Inf - Inf is NaN, and f32::clamp hands a NaN through
+NONFINITE = (5.0, 0.5, [1.0, 3e38, -3e38])
+NONFINITE_N = 1500
 
 
 # ---- signals ------------------------------------------------------------------------------------------------------------------------
@@ -142,6 +161,16 @@ def nrz(nsyms, sps, seed, offset=0.0, smooth=0, noise=0.0):
     if noise:
         x = x + noise * rng.standard_normal(len(x))
     return x.astype(np.float32)
+
+
+def sps_edge_signal(key):
+    """SPS_EDGE_N samples of noisy NRZ at the symbol length of SPS_EDGES[key], 0.3 % slow"""
+    sps = SPS_EDGES[key][0]
+    return nrz(int(SPS_EDGE_N / sps) + 8, sps, 40 + len(key), offset=0.003, noise=0.1)[:SPS_EDGE_N]
+
+
+def nonfinite_signal():
+    return nrz(NONFINITE_N // 5 + 8, NONFINITE[0], 63, offset=0.002, noise=0.1)[:NONFINITE_N]
 
 
 def with_gap(x, at, length):
