@@ -472,8 +472,8 @@ int rr_hdlc_frame_bytes(rr_block* b, unsigned char* out, size_t cap, size_t* tot
 }
 const void* rr_hdlc_bytes_dev(rr_block* b, size_t* n_total) {
     auto* d = as<rr::HdlcDeframer>(b, "rr_hdlc_bytes_dev", NOT_DEFRAMER);
-    if (n_total) *n_total = d ? d->arena_len() : 0;
-    return d && d->arena_len() ? d->arena_dev() : nullptr;
+    if (n_total) *n_total = d ? d->core.arena_len() : 0;
+    return d && d->core.arena_len() ? d->core.arena_dev() : nullptr;
 }
 int rr_hdlc_stats(rr_block* b, unsigned long long* decoded, unsigned long long* crc_error, unsigned long long* bitfixed) {
     auto* d = as<rr::HdlcDeframer>(b, "rr_hdlc_stats", NOT_DEFRAMER);
@@ -489,7 +489,7 @@ int rr_hdlc_deframer_dims(const rr_block* b, size_t* tile_bits, size_t* carry_bi
     auto* d = as<rr::HdlcDeframer>(b, "rr_hdlc_deframer_dims", NOT_DEFRAMER);
     if (!d || !tile_bits || !carry_bits) { if (d) rr::set_last_error("rr_hdlc_deframer_dims: null argument"); return RR_ERR; }
     *tile_bits = rr::HDLC_T;
-    *carry_bits = rr::hdlc_carry_bits(d->max_size);
+    *carry_bits = rr::hdlc_carry_bits(d->core.max_size);
     return 0;
 }
 rr_block* rr_hdlc_receiver_create(size_t nstreams, int bit_flags, unsigned long long mask, unsigned long long seed, unsigned len,
@@ -500,7 +500,7 @@ rr_block* rr_hdlc_receiver_create(size_t nstreams, int bit_flags, unsigned long 
 int rr_hdlc_receiver_push_dev(rr_block* b, const void* d_syms, size_t stride, size_t n_cap, const void* d_counts, void* hip_stream) {
     auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_push_dev", NOT_RECEIVER);
     if (!d) return RR_ERR;
-    if (const char* e = rr::hdlcrx_check_push(d->nstreams, d_syms, stride, n_cap)) { rr::set_last_error(e); return RR_ERR; }   // before any device is touched
+    if (const char* e = rr::hdlcrx_check_push(d->core.nstreams, d_syms, stride, n_cap)) { rr::set_last_error(e); return RR_ERR; }   // before any device is touched
     return on_device(d, hip_stream, [&](hipStream_t s) {
         d->push_dev(static_cast<const float*>(d_syms), stride, n_cap, static_cast<const unsigned long long*>(d_counts), s);
     });
@@ -508,7 +508,7 @@ int rr_hdlc_receiver_push_dev(rr_block* b, const void* d_syms, size_t stride, si
 int rr_hdlc_receiver_push(rr_block* b, const float* syms, size_t stride, size_t n_cap, const size_t* counts) {
     auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_push", NOT_RECEIVER);
     if (!d) return RR_ERR;
-    if (const char* e = rr::hdlcrx_check_push(d->nstreams, syms, stride, n_cap)) { rr::set_last_error(e); return RR_ERR; }
+    if (const char* e = rr::hdlcrx_check_push(d->core.nstreams, syms, stride, n_cap)) { rr::set_last_error(e); return RR_ERR; }
     return guarded([&] { d->push_host(syms, stride, n_cap, counts); });
 }
 int rr_hdlc_receiver_frames(rr_block* b, rr_hdlc_stream_frame* rec, size_t cap, size_t* total) {
@@ -527,8 +527,8 @@ int rr_hdlc_receiver_frame_bytes(rr_block* b, unsigned char* out, size_t cap, si
 }
 const void* rr_hdlc_receiver_bytes_dev(rr_block* b, size_t* n_total) {
     auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_bytes_dev", NOT_RECEIVER);
-    if (n_total) *n_total = d ? d->arena_len() : 0;
-    return d ? d->arena_dev() : nullptr;
+    if (n_total) *n_total = d ? d->core.arena_len() : 0;
+    return d ? d->core.arena_dev() : nullptr;
 }
 int rr_hdlc_receiver_stats(rr_block* b, unsigned long long* decoded, unsigned long long* crc_error, unsigned long long* bitfixed, size_t cap,
                            size_t* total) {
@@ -554,7 +554,7 @@ int rr_hdlc_receiver_dims(const rr_block* b, size_t* tile_bits, size_t* carry_bi
     auto* d = as<rr::HdlcReceiver>(b, "rr_hdlc_receiver_dims", NOT_RECEIVER);
     if (!d || !tile_bits || !carry_bits) { if (d) rr::set_last_error("rr_hdlc_receiver_dims: null argument"); return RR_ERR; }
     *tile_bits = rr::HDLC_T;
-    *carry_bits = rr::hdlc_carry_bits(d->max_size);
+    *carry_bits = rr::hdlc_carry_bits(d->core.max_size);
     return 0;
 }
 rr_block* rr_symbol_sync_create(float sps, float max_deviation, const float* taps, size_t ntaps, size_t nstreams) {

@@ -9,9 +9,7 @@
 
 #include "frame_core.hpp"
 #include "frame_host.hpp"
-#include "hdlc_host.hpp"
 #include "hdlcrx_core.hpp"
-#include "hdlcrx_host.hpp"
 #include "pdu_host.hpp"
 #include "symsync_host.hpp"
 
@@ -149,20 +147,21 @@ const char* bits_check(int flags, unsigned long long seed, unsigned len, unsigne
     if (code_len > 64) return "access code longer than 64 bits";
     return nullptr;
 }
+// RR_BITS_* and Descrambler::new(mask, seed, len) as the stages' configuration (hdlcrx_core.hpp says how the register maps to
+// delays) -> the history word in front of the stream: the seed, or 0 without a descrambler
+static unsigned long long bits_decode(int flags, unsigned long long mask, unsigned long long seed, unsigned len, BitsCfg& cfg) {
+    cfg.invert = flags & RR_BITS_INVERT ? 1 : 0;
+    cfg.nrzi = flags & RR_BITS_NRZI ? 1 : 0;
+    if (!(flags & RR_BITS_DESCRAMBLE)) return 0;
+    cfg.dmask = rx_dmask(mask, len);
+    return rx_dhist0(seed, len);
+}
 BitDecoder::BitDecoder(const char* nm, bool f32src, int flags, unsigned long long mask, unsigned long long seed, unsigned len,
                        unsigned long long code, unsigned code_len, size_t allowed_diffs)
     : SyncBlock(nm, f32src ? 4 : 1, 1) {
     if (const char* e = bits_check(flags, seed, len, code_len)) throw Error(e);
-    cfg.invert = flags & RR_BITS_INVERT ? 1 : 0;
-    cfg.nrzi = flags & RR_BITS_NRZI ? 1 : 0;
     unsigned long long init[BITS_ST_N] = {0, 0, 0, 0};                                // last: 0 (nrzi.rs:32-33); nothing seen
-    if (flags & RR_BITS_DESCRAMBLE) {
-        // shift_reg holds d[n-1-k] in bit len-k (descrambler.rs:37), so mask bit j reads d[n - delta], delta = 1 + len - j;
-        // before the stream the register is the seed: d[-1-k] = bit len-k of it
-        for (unsigned j = 0; j <= len; j++)
-            if (mask >> j & 1) cfg.dmask |= 1ull << (len - j);
-        init[BITS_ST_DHIST] = seed << (63 - len);
-    }
+    init[BITS_ST_DHIST] = bits_decode(flags, mask, seed, len, cfg);
     cfg.L = (int)code_len;
     cfg.code = code_len == 64 ? code : code & ((1ull << code_len) - 1ull);
     cfg.allowed = (unsigned)std::min<size_t>(allowed_diffs, 64);
@@ -299,6 +298,22 @@ std::vector<float> Wpcr::fetch_spectrum(size_t burst) {
     if (!m.empty()) stage_download_sync(m.data(), mag.p + starts[burst], m.size() * sizeof(float), stream);
     return m;
 }
+void Wpcr::pack_dev(const float* d_syms, float* d_out, size_t out_cap, size_t* produced, size_t* pdu_start, size_t* pdu_len, size_t cap,
+                    size_t* npdus, hipStream_t s) {
+    const std::vector<WpcrResult>& r = fetch_results();
+    std::vector<rr_wpcr_result> res(r.size());
+    if (!r.empty()) std::memcpy(res.data(), r.data(), r.size() * sizeof(rr_wpcr_result));
+    size_t k = 0;
+    const size_t total = pdu_pack_plan(res, starts, hpack, pdu_start, pdu_len, cap, &k);
+    if (total > out_cap) throw Error("output shorter than the packed symbols");
+    *produced = total;
+    *npdus = k;
+    if (!total) return;
+    if (!d_syms || !d_out) throw Error("rr_wpcr_pack_dev: null argument");
+    pack_desc.reserve(hpack.size());
+    hstage().h2d(pack_desc.p, hpack.data(), hpack.size() * sizeof(long), s);
+    launch_pdu_pack(d_syms, pack_desc.p, (long)(hpack.size() / 3), (long)total, d_out, s);
+}
 
 // ---- StreamToPdu (burst_tagger.rs:68-85, stream_to_pdu.rs:198-275, wpcr.rs:62-78; kernels_pdu.hip) -------------------------------------
 static_assert(sizeof(PduRec) == sizeof(rr_pdu_record) && offsetof(PduRec, nlow) == offsetof(rr_pdu_record, nlow) &&
@@ -400,23 +415,6 @@ void StreamToPdu::fetch_ranks(size_t idx, float* low, float* high) {
     stage_download_sync(lh, ranks.p + 2 * slots[idx], sizeof lh, stream);
     *low = lh[0];
     *high = lh[1];
-}
-void Wpcr::pack_dev(const float* d_syms, float* d_out, size_t out_cap, size_t* produced, size_t* pdu_start, size_t* pdu_len, size_t cap,
-                    size_t* npdus, hipStream_t s) {
-    const std::vector<WpcrResult>& r = fetch_results();
-    static_assert(sizeof(WpcrResult) == sizeof(rr_wpcr_result), "WpcrResult is rr_wpcr_result");
-    std::vector<rr_wpcr_result> res(r.size());
-    if (!r.empty()) std::memcpy(res.data(), r.data(), r.size() * sizeof(rr_wpcr_result));
-    size_t k = 0;
-    const size_t total = pdu_pack_plan(res, starts, hpack, pdu_start, pdu_len, cap, &k);
-    if (total > out_cap) throw Error("output shorter than the packed symbols");
-    *produced = total;
-    *npdus = k;
-    if (!total) return;
-    if (!d_syms || !d_out) throw Error("rr_wpcr_pack_dev: null argument");
-    pack_desc.reserve(hpack.size());
-    hstage().h2d(pack_desc.p, hpack.data(), hpack.size() * sizeof(long), s);
-    launch_pdu_pack(d_syms, pack_desc.p, (long)(hpack.size() / 3), (long)total, d_out, s);
 }
 
 // ---- Scrambler::g3ruh, NrziEncode and the HDLC framer (descrambler.rs:41-47, nrzi.rs:52-69, hdlc_framer.rs; kernels_frame.hip) ----------
@@ -534,63 +532,94 @@ const std::vector<rr_frame_record>& HdlcFramer::fetch_records() {
     return records;
 }
 
-// ---- HdlcDeframer (hdlc_deframer.rs:80-232; kernels_hdlc.hip) -----------------------------------------------------------------------
+// ---- HdlcCore: what HdlcDeframer and HdlcReceiver share (hdlc_deframer.rs:80-232; hdlc_body.hpp) -----------------------------------------
+void HdlcCore::init(size_t ns, size_t mn, size_t mx, int fl, hipStream_t s) {
+    nstreams = ns; min_size = mn; max_size = mx; flags = fl;
+    // Unsynced(0xff) (hdlc_deframer.rs:28-32): 8 ones nobody asks about in front of every stream, and every flag is seen whole
+    HdlcState init{};
+    init.count = HDLC_HALO;
+    init.state = HDLC_U;
+    const std::vector<HdlcState> all(ns, init);
+    st.upload(all.data(), ns, s);
+    const size_t cb = ns * hdlc_carry_bits(mx);
+    for (auto& b : cbits.buf) { b.reserve(cb); RR_HIP(hipMemsetAsync(b.p, 1, cb, s)); }
+    carry = HDLC_HALO;
+    etotal.reserve(ns); pstats.reserve(3 * ns); fin.reserve(ns); count.reserve(1);
+}
+HdlcRxBounds HdlcCore::plan(size_t n, HdlcArgs& a, HdlcRxArgs* rx) {
+    last_carry = carry;
+    const HdlcPlan p = hdlc_plan(carry, n, max_size);
+    const HdlcRxBounds bd = hdlcrx_bounds(nstreams, carry, n);
+    const size_t ns = nstreams;                // (a stream's share of each buffer is its pitch)
+    raw.reserve(ns * p.nwords); fl.reserve(ns * p.nwords); ab.reserve(ns * p.nwords); sf.reserve(ns * p.nwords);
+    tilecnt.reserve(ns * p.ntiles); offs.reserve(ns * p.ntiles);
+    ends.reserve(ns * p.ecap); gmap.reserve(ns * p.ecap); pmap.reserve(ns * p.ecap); bmap.reserve(ns * p.nblocks); bstate.reserve(ns * p.nblocks);
+    arena.reserve(std::max<size_t>(bd.arena, 1));
+    a.cin = cbits.in(); a.cout = cbits.out(); a.st_in = st.in(); a.st_out = st.out();
+    a.carry_cap = (long)p.carry_cap;
+    a.nv_max = (long)p.one.nv;
+    a.ntiles = (long)p.ntiles;
+    a.min_size = min_size; a.max_size = max_size;
+    a.keep = (flags & RR_HDLC_KEEP_CHECKSUM) != 0; a.fix = (flags & RR_HDLC_FIX_BITS) != 0;
+    a.raw = raw.p; a.fl = fl.p; a.ab = ab.p; a.sf = sf.p; a.tilecnt = tilecnt.p; a.offs = offs.p;
+    a.etotal = etotal.p; a.count = count.p; a.pstats = pstats.p;
+    a.ends = ends.p; a.ends_cap = (long)p.ecap; a.gmap = gmap.p; a.pmap = pmap.p; a.bmap = bmap.p; a.bstate = bstate.p; a.fin = fin.p;
+    a.arena = arena.p; a.arena_cap = (long)p.one.arena; a.rec_cap = (long)bd.frames;
+    if (rx) {
+        rx->p_words = (long)p.nwords; rx->p_tiles = (long)p.ntiles; rx->p_ends = (long)p.ecap; rx->p_blocks = (long)p.nblocks;
+        rx->p_carry = (long)p.carry_cap; rx->p_arena = (long)p.one.arena;
+    }
+    return bd;
+}
+void HdlcCore::advance(size_t n) {
+    st.flip();
+    cbits.flip();
+    carry = hdlc_next_carry(carry, n, max_size);
+    bfetched = false;
+}
+std::vector<unsigned long long> HdlcCore::fetch_stats(bool before, hipStream_t s) const {
+    std::vector<HdlcState> v(nstreams);
+    stage_download_sync(v.data(), before ? st.out() : st.in(), nstreams * sizeof(HdlcState), s);
+    std::vector<unsigned long long> out(3 * nstreams);
+    for (size_t c = 0; c < nstreams; c++) std::copy(v[c].stats, v[c].stats + 3, out.begin() + 3 * c);
+    return out;
+}
+const std::vector<unsigned char>& HdlcCore::fetch_bytes(hipStream_t s) {
+    if (!bfetched) {
+        bytes.assign(arena_len(), 0);
+        if (!bytes.empty()) stage_download_sync(bytes.data(), arena.p, bytes.size(), s);
+        bfetched = true;
+    }
+    return bytes;
+}
+
+// ---- HdlcDeframer (hdlc_deframer.rs:80-232; kernels_hdlc.hip): the one-stream case of HdlcCore over a byte per bit ---------------------
 static_assert(sizeof(HdlcRec) == sizeof(rr_hdlc_frame) && offsetof(HdlcRec, pos) == offsetof(rr_hdlc_frame, pos) &&
               offsetof(HdlcRec, start) == offsetof(rr_hdlc_frame, start) && offsetof(HdlcRec, len) == offsetof(rr_hdlc_frame, len) &&
               offsetof(HdlcRec, flags) == offsetof(rr_hdlc_frame, flags), "HdlcRec is rr_hdlc_frame");
 HdlcDeframer::HdlcDeframer(size_t mn, size_t mx, int fl)
-    : BatchBlock("HdlcDeframer", 1, 1, "HdlcDeframer delivers frames: rr_hdlc_deframer_push / rr_hdlc_deframer_push_dev"),
-      min_size(mn), max_size(mx), flags(fl) {
+    : BatchBlock("HdlcDeframer", 1, 1, "HdlcDeframer delivers frames: rr_hdlc_deframer_push / rr_hdlc_deframer_push_dev") {
     if (const char* e = hdlc_check_create(mn, mx, fl)) throw Error(e);
-    // Unsynced(0xff) (hdlc_deframer.rs:28-32): 8 ones nobody asks about in front of the stream, and every flag is seen whole
-    HdlcState init{};
-    init.count = HDLC_HALO;
-    init.state = HDLC_U;
-    st.upload(&init, 1, stream);
-    const std::vector<unsigned char> ones(hdlc_carry_bits(mx), 1);
-    cbits.upload(ones.data(), ones.size(), stream);
-    carry = HDLC_HALO;
-    scal.reserve(5);
-    fin.reserve(1);
+    core.init(1, mn, mx, fl, stream);
     RR_HIP(hipStreamSynchronize(stream));
 }
 void HdlcDeframer::push_dev(const unsigned char* d_bits, size_t n, hipStream_t s) {
     if (const char* e = hdlc_check_push(d_bits, n)) throw Error(e);
     frames.clear();
-    bytes.clear();
-    fetched = bfetched = true;                 // a push of no bits has no frames and leaves every state alone
-    last_n = n;
-    last_w0 = w0;
+    fetched = true;                            // a push of no bits has no frames and leaves every state alone
+    core.begin(n);
     if (!n) return;
-    const HdlcBounds bd = hdlc_bounds(carry, n);
-    b_nv = bd.nv; b_frames = bd.frames; b_arena = bd.arena;
     HdlcArgs a{};
-    a.bits = d_bits; a.n = (long)n;
-    a.cin = cbits.in(); a.cout = cbits.out(); a.st_in = st.in(); a.st_out = st.out();
-    a.carry_cap = (long)hdlc_carry_bits(max_size);
-    a.nv_max = (long)bd.nv;
-    a.ntiles = (long)((bd.nv + HDLC_T - 1) / HDLC_T);
-    a.w0 = w0; a.min_size = min_size; a.max_size = max_size;
-    a.keep = (flags & RR_HDLC_KEEP_CHECKSUM) != 0; a.fix = (flags & RR_HDLC_FIX_BITS) != 0;
-    const size_t nwords = (size_t)a.ntiles * (HDLC_T / 64) + 1, ecap = bd.nv / 7 + 2, nblocks = (ecap + HDLC_GB - 1) / HDLC_GB;
-    raw.reserve(nwords); fl.reserve(nwords); ab.reserve(nwords); sf.reserve(nwords);
-    tilecnt.reserve((size_t)a.ntiles); offs.reserve((size_t)a.ntiles);
-    ends.reserve(ecap); gmap.reserve(ecap); pmap.reserve(ecap); bmap.reserve(nblocks); bstate.reserve(nblocks);
-    arena.reserve(std::max<size_t>(bd.arena, 1));
+    const HdlcRxBounds bd = core.plan(n, a, nullptr);
     recs.reserve(std::max<size_t>(bd.frames, 1));
-    a.raw = raw.p; a.fl = fl.p; a.ab = ab.p; a.sf = sf.p; a.tilecnt = tilecnt.p; a.offs = offs.p;
-    a.etotal = scal.p; a.count = scal.p + 1; a.pstats = scal.p + 2;
-    a.ends = ends.p; a.ends_cap = (long)ecap; a.gmap = gmap.p; a.pmap = pmap.p; a.bmap = bmap.p; a.bstate = bstate.p; a.fin = fin.p;
-    a.arena = arena.p; a.arena_cap = (long)bd.arena; a.recs = recs.p; a.rec_cap = (long)bd.frames;
+    a.bits = d_bits; a.n = (long)n; a.w0 = w0; a.recs = recs.p;
     prof_begin(s);
-    if (bd.arena) RR_HIP(hipMemsetAsync(arena.p, 0, bd.arena, s));
+    if (bd.arena) RR_HIP(hipMemsetAsync(core.arena.p, 0, bd.arena, s));
     launch_hdlc(a, s);
     prof_end(s);
-    st.flip();
-    cbits.flip();
-    carry = hdlc_next_carry(carry, n, max_size);
+    core.advance(n);
     w0 += n;
-    fetched = bfetched = false;
+    fetched = false;
 }
 void HdlcDeframer::push_host(const unsigned char* bits, size_t n) {
     host_call([&] {
@@ -606,35 +635,27 @@ const std::vector<rr_hdlc_frame>& HdlcDeframer::fetch_frames() {
     settle();
     if (!fetched) {
         fetched = true;                        // (a refused push has no frames: the refusal is not repeated)
-        HdlcBounds bd;
-        bd.nv = b_nv; bd.frames = b_frames; bd.arena = b_arena;
+        const HdlcBounds bd = core.bounds().one;
         unsigned long long k = 0;
-        stage_download_sync(&k, scal.p + 1, sizeof k, stream);
+        stage_download_sync(&k, core.count.p, sizeof k, stream);
         if (const char* e = hdlc_check_count(k, bd)) throw Error(e);
         std::vector<rr_hdlc_frame> r((size_t)k);
         if (k) stage_download_sync(r.data(), recs.p, (size_t)k * sizeof(rr_hdlc_frame), stream);
-        HdlcState now{}, before{};
-        stage_download_sync(&now, st.in(), sizeof now, stream);
-        stage_download_sync(&before, st.out(), sizeof before, stream);       // (the pair's other half: the state the push started from)
-        if (const char* e = hdlc_validate(r, bd, max_size, last_w0, last_n, before.stats, now.stats)) throw Error(e);
+        const std::vector<unsigned long long> now = core.fetch_stats(false, stream), before = core.fetch_stats(true, stream);
+        const unsigned long long at = w0 - core.last_n;      // (w0 has moved behind the push's bits)
+        if (const char* e = hdlc_validate(r, bd, core.max_size, at, core.last_n, before.data(), now.data())) throw Error(e);
         frames.swap(r);
     }
     return frames;
 }
 const std::vector<unsigned char>& HdlcDeframer::fetch_bytes() {
     fetch_frames();                            // (waits; the arena is read only behind a push whose records stood the checks)
-    if (!bfetched) {
-        bytes.assign(b_arena, 0);
-        if (b_arena) stage_download_sync(bytes.data(), arena.p, b_arena, stream);
-        bfetched = true;
-    }
-    return bytes;
+    return core.fetch_bytes(stream);
 }
 void HdlcDeframer::fetch_stats(unsigned long long out[3]) {
     settle();
-    HdlcState now{};
-    stage_download_sync(&now, st.in(), sizeof now, stream);
-    for (int k = 0; k < 3; k++) out[k] = now.stats[k];
+    const std::vector<unsigned long long> now = core.fetch_stats(false, stream);
+    std::copy(now.begin(), now.end(), out);
 }
 
 // ---- SymbolSync (symbol_sync.rs:46-217; kernels_sync.hip) ---------------------------------------------------------------------------------
@@ -725,84 +746,47 @@ SyncState SymbolSync::fetch_state(size_t c) {
     return s;
 }
 
-// ---- HdlcReceiver (binary_slicer.rs, nrzi.rs, descrambler.rs, hdlc_deframer.rs; kernels_hdlcrx.hip) -------------------------------------
+// ---- HdlcReceiver (binary_slicer.rs, nrzi.rs, descrambler.rs, hdlc_deframer.rs; kernels_hdlcrx.hip): HdlcCore behind the bit chain ------
 static_assert(sizeof(HdlcRxRec) == sizeof(rr_hdlc_stream_frame) && offsetof(HdlcRxRec, pos) == offsetof(rr_hdlc_stream_frame, pos) &&
               offsetof(HdlcRxRec, start) == offsetof(rr_hdlc_stream_frame, start) && offsetof(HdlcRxRec, len) == offsetof(rr_hdlc_stream_frame, len) &&
               offsetof(HdlcRxRec, flags) == offsetof(rr_hdlc_stream_frame, flags) && offsetof(HdlcRxRec, stream) == offsetof(rr_hdlc_stream_frame, stream),
               "HdlcRxRec is rr_hdlc_stream_frame");
 HdlcReceiver::HdlcReceiver(size_t ns, int bit_flags, unsigned long long mask, unsigned long long seed, unsigned len, size_t mn, size_t mx,
                            int fl)
-    : BatchBlock("HdlcReceiver", 4, 1, "HdlcReceiver delivers frames: rr_hdlc_receiver_push / rr_hdlc_receiver_push_dev"),
-      nstreams(ns), min_size(mn), max_size(mx), flags(fl) {
+    : BatchBlock("HdlcReceiver", 4, 1, "HdlcReceiver delivers frames: rr_hdlc_receiver_push / rr_hdlc_receiver_push_dev") {
     if (const char* e = hdlcrx_check_create(ns, bit_flags, seed, len, mn, mx, fl)) throw Error(e);
-    cfg.invert = bit_flags & RR_BITS_INVERT ? 1 : 0;
-    cfg.nrzi = bit_flags & RR_BITS_NRZI ? 1 : 0;
     unsigned long long one[RX_ST_N] = {0, 0, 0};                      // last: 0 (nrzi.rs:32-33); no symbol taken yet
-    if (bit_flags & RR_BITS_DESCRAMBLE) {
-        cfg.dmask = rx_dmask(mask, len);
-        one[RX_ST_DHIST] = rx_dhist0(seed, len);                      // before the stream the register is the seed
-    }
+    one[RX_ST_DHIST] = bits_decode(bit_flags, mask, seed, len, cfg);
     std::vector<unsigned long long> b0(ns * RX_ST_N);
     for (size_t c = 0; c < ns; c++) std::copy(one, one + RX_ST_N, b0.begin() + c * RX_ST_N);
     bst.upload(b0.data(), b0.size(), stream);
-    // Unsynced(0xff) (hdlc_deframer.rs:28-32): 8 ones nobody asks about in front of every stream, and every flag is seen whole
-    HdlcState init{};
-    init.count = HDLC_HALO;
-    init.state = HDLC_U;
-    const std::vector<HdlcState> all(ns, init);
-    st.upload(all.data(), ns, stream);
-    const size_t cb = ns * hdlc_carry_bits(mx);
-    for (auto& b : cbits.buf) { b.reserve(cb); RR_HIP(hipMemsetAsync(b.p, 1, cb, stream)); }
-    carry = HDLC_HALO;
-    etotal.reserve(ns); pstats.reserve(3 * ns); fin.reserve(ns); count.reserve(1);
+    core.init(ns, mn, mx, fl, stream);
     RR_HIP(hipStreamSynchronize(stream));
 }
 void HdlcReceiver::push_dev(const float* d_syms, size_t stride, size_t n_cap, const unsigned long long* d_counts, hipStream_t s) {
-    if (const char* e = hdlcrx_check_push(nstreams, d_syms, stride, n_cap)) throw Error(e);
+    if (const char* e = hdlcrx_check_push(core.nstreams, d_syms, stride, n_cap)) throw Error(e);
     frames.clear();
-    bytes.clear();
-    fetched = bfetched = true;                 // a push of no symbols has no frames and leaves every state alone
-    last_cap = n_cap;
+    fetched = true;                            // a push of no symbols has no frames and leaves every state alone
+    core.begin(n_cap);
     if (!n_cap) return;
-    b_carry = carry;
-    const HdlcRxBounds bd = hdlcrx_bounds(nstreams, carry, n_cap);
     HdlcRxArgs r{};
-    r.syms = d_syms; r.stride = (long)stride; r.n_cap = (long)n_cap; r.nstreams = (long)nstreams; r.counts = d_counts;
+    const HdlcRxBounds bd = core.plan(n_cap, r.h, &r);
+    recs.reserve(std::max<size_t>(bd.frames, 1));
+    r.syms = d_syms; r.stride = (long)stride; r.n_cap = (long)n_cap; r.nstreams = (long)core.nstreams; r.counts = d_counts;
     r.invert = cfg.invert; r.nrzi = cfg.nrzi; r.dmask = cfg.dmask;
     r.bst_in = bst.in(); r.bst_out = bst.out();
-    HdlcArgs& a = r.h;
-    a.cin = cbits.in(); a.cout = cbits.out(); a.st_in = st.in(); a.st_out = st.out();
-    a.carry_cap = (long)hdlc_carry_bits(max_size);
-    a.nv_max = (long)bd.one.nv;
-    a.ntiles = (long)((bd.one.nv + HDLC_T - 1) / HDLC_T);
-    a.min_size = min_size; a.max_size = max_size;
-    a.keep = (flags & RR_HDLC_KEEP_CHECKSUM) != 0; a.fix = (flags & RR_HDLC_FIX_BITS) != 0;
-    const size_t nwords = (size_t)a.ntiles * (HDLC_T / 64) + 1, ecap = bd.one.nv / 7 + 2, nblocks = (ecap + HDLC_GB - 1) / HDLC_GB;
-    r.p_words = (long)nwords; r.p_tiles = a.ntiles; r.p_ends = (long)ecap; r.p_blocks = (long)nblocks;
-    r.p_carry = a.carry_cap; r.p_arena = (long)bd.one.arena;
-    const size_t ns = nstreams;
-    raw.reserve(ns * nwords); fl.reserve(ns * nwords); ab.reserve(ns * nwords); sf.reserve(ns * nwords);
-    tilecnt.reserve(ns * (size_t)a.ntiles); offs.reserve(ns * (size_t)a.ntiles);
-    ends.reserve(ns * ecap); gmap.reserve(ns * ecap); pmap.reserve(ns * ecap); bmap.reserve(ns * nblocks); bstate.reserve(ns * nblocks);
-    arena.reserve(std::max<size_t>(bd.arena, 1));
-    recs.reserve(std::max<size_t>(bd.frames, 1));
-    a.raw = raw.p; a.fl = fl.p; a.ab = ab.p; a.sf = sf.p; a.tilecnt = tilecnt.p; a.offs = offs.p;
-    a.etotal = etotal.p; a.count = count.p; a.pstats = pstats.p;
-    a.ends = ends.p; a.ends_cap = (long)ecap; a.gmap = gmap.p; a.pmap = pmap.p; a.bmap = bmap.p; a.bstate = bstate.p; a.fin = fin.p;
-    a.arena = arena.p; a.arena_cap = (long)bd.one.arena; a.rec_cap = (long)bd.frames;
     r.recs = recs.p;
     prof_begin(s);
-    if (bd.arena) RR_HIP(hipMemsetAsync(arena.p, 0, bd.arena, s));
+    if (bd.arena) RR_HIP(hipMemsetAsync(core.arena.p, 0, bd.arena, s));
     launch_hdlcrx(r, s);
     prof_end(s);
     bst.flip();
-    st.flip();
-    cbits.flip();
-    carry = hdlc_next_carry(carry, n_cap, max_size);
-    fetched = bfetched = false;
+    core.advance(n_cap);
+    fetched = false;
 }
 void HdlcReceiver::push_host(const float* syms, size_t stride, size_t n_cap, const size_t* counts) {
     host_call([&] {
+        const size_t nstreams = core.nstreams;
         if (const char* e = hdlcrx_check_push(nstreams, syms, stride, n_cap)) throw Error(e);
         if (n_cap) {
             // only what the counts cover is read from the caller's buffer, as on the device
@@ -820,60 +804,42 @@ void HdlcReceiver::push_host(const float* syms, size_t stride, size_t n_cap, con
         push_dev(h_syms.p, n_cap, n_cap, counts ? h_counts.p : nullptr, stream);
     });
 }
-size_t HdlcReceiver::arena_len() const { return last_cap ? hdlcrx_bounds(nstreams, b_carry, last_cap).arena : 0; }
 const std::vector<rr_hdlc_stream_frame>& HdlcReceiver::fetch_frames() {
     settle();
     if (!fetched) {
         fetched = true;                        // (a refused push has no frames: the refusal is not repeated)
-        const HdlcRxBounds bd = hdlcrx_bounds(nstreams, b_carry, last_cap);
+        const HdlcRxBounds bd = core.bounds();
         unsigned long long k = 0;
-        stage_download_sync(&k, count.p, sizeof k, stream);
+        stage_download_sync(&k, core.count.p, sizeof k, stream);
         if (const char* e = hdlcrx_check_count(k, bd)) throw Error(e);
         std::vector<rr_hdlc_stream_frame> r((size_t)k);
         if (k) stage_download_sync(r.data(), recs.p, (size_t)k * sizeof(rr_hdlc_stream_frame), stream);
         // the pairs' other halves hold what the push started from
-        std::vector<HdlcState> now(nstreams), before(nstreams);
-        stage_download_sync(now.data(), st.in(), nstreams * sizeof(HdlcState), stream);
-        stage_download_sync(before.data(), st.out(), nstreams * sizeof(HdlcState), stream);
-        std::vector<unsigned long long> bnow(nstreams * RX_ST_N), bbefore(nstreams * RX_ST_N);
-        stage_download_sync(bnow.data(), bst.in(), bnow.size() * sizeof(unsigned long long), stream);
-        stage_download_sync(bbefore.data(), bst.out(), bbefore.size() * sizeof(unsigned long long), stream);
-        std::vector<unsigned long long> p0(nstreams), p1(nstreams), s0(3 * nstreams), s1(3 * nstreams);
-        for (size_t c = 0; c < nstreams; c++) {
-            p0[c] = bbefore[c * RX_ST_N + RX_ST_POS]; p1[c] = bnow[c * RX_ST_N + RX_ST_POS];
-            for (int q = 0; q < 3; q++) { s0[3 * c + q] = before[c].stats[q]; s1[3 * c + q] = now[c].stats[q]; }
-        }
+        const std::vector<unsigned long long> s1 = core.fetch_stats(false, stream), s0 = core.fetch_stats(true, stream);
+        const std::vector<unsigned long long> p1 = positions(bst.in()), p0 = positions(bst.out());
         std::vector<size_t> moved;
-        if (const char* e = hdlcrx_clamp_consumed(p0.data(), p1.data(), nstreams, last_cap, moved)) throw Error(e);
-        if (const char* e = hdlcrx_validate(r, bd, max_size, p0.data(), moved.data(), s0.data(), s1.data())) throw Error(e);
+        if (const char* e = hdlcrx_clamp_consumed(p0.data(), p1.data(), core.nstreams, core.last_n, moved)) throw Error(e);
+        if (const char* e = hdlcrx_validate(r, bd, core.max_size, p0.data(), moved.data(), s0.data(), s1.data())) throw Error(e);
         frames.swap(r);
     }
     return frames;
 }
 const std::vector<unsigned char>& HdlcReceiver::fetch_bytes() {
     fetch_frames();                            // (waits; the arena is read only behind a push whose records stood the checks)
-    if (!bfetched) {
-        const size_t n = arena_len();
-        bytes.assign(n, 0);
-        if (n) stage_download_sync(bytes.data(), arena.p, n, stream);
-        bfetched = true;
-    }
-    return bytes;
+    return core.fetch_bytes(stream);
 }
 std::vector<unsigned long long> HdlcReceiver::fetch_stats() {
     settle();
-    std::vector<HdlcState> now(nstreams);
-    stage_download_sync(now.data(), st.in(), nstreams * sizeof(HdlcState), stream);
-    std::vector<unsigned long long> out(3 * nstreams);
-    for (size_t c = 0; c < nstreams; c++)
-        for (int q = 0; q < 3; q++) out[3 * c + q] = now[c].stats[q];
-    return out;
+    return core.fetch_stats(false, stream);
 }
 std::vector<unsigned long long> HdlcReceiver::fetch_consumed() {
     settle();
-    std::vector<unsigned long long> b(nstreams * RX_ST_N), out(nstreams);
-    stage_download_sync(b.data(), bst.in(), b.size() * sizeof(unsigned long long), stream);
-    for (size_t c = 0; c < nstreams; c++) out[c] = b[c * RX_ST_N + RX_ST_POS];
+    return positions(bst.in());
+}
+std::vector<unsigned long long> HdlcReceiver::positions(const unsigned long long* d_bst) const {
+    std::vector<unsigned long long> b(core.nstreams * RX_ST_N), out(core.nstreams);
+    stage_download_sync(b.data(), d_bst, b.size() * sizeof(unsigned long long), stream);
+    for (size_t c = 0; c < out.size(); c++) out[c] = b[c * RX_ST_N + RX_ST_POS];
     return out;
 }
 

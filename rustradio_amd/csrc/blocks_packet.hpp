@@ -1,6 +1,7 @@
 // blocks_packet.hpp — the packet-side blocks (blocks_packet.cpp) and the plumbing they share.  Part of blocks.hpp: include that.
 #pragma once
 #include "blocks.hpp"
+#include "hdlcrx_host.hpp"
 
 namespace rr {
 
@@ -261,36 +262,54 @@ struct HdlcFramer : BatchBlock {
     const std::vector<rr_frame_record>& fetch_records();      // waits for the latest push
 };
 
-// HdlcDeframer (hdlc_deframer.rs:80-232) over windows of a bit stream (kernels_hdlc.hip): no stream protocol (work_dev is an
-// error).  The state between pushes — the machine at the last flag end, the raw bits of the gap still open, the counters — stays
-// on the device; the host keeps the stream position and an upper bound of the carried bits, and sizes everything it reads back
-// from those (hdlc_host.hpp).
-struct HdlcDeframer : BatchBlock {
-    size_t min_size, max_size;
-    int flags;
-    Carried<HdlcState> st;                        // in(): what the stream so far left behind
-    Carried<unsigned char> cbits;                 // ... and its carried bits, one per byte
-    size_t carry = 0;                             // the carried bits, at most
-    unsigned long long w0 = 0;                    // bits of the stream so far
-    DevBuf<unsigned long long> raw, fl, ab, sf, offs, scal;      // scal: etotal, count, pstats[3]
+// What rr_hdlc_deframer and rr_hdlc_receiver share on the host: nstreams HdlcDeframers' state between pushes (per stream the
+// machine at the last flag end, the counters and the raw bits of the gap still open, all on the device), the workspace of a push
+// and the read-back.  Not a Block: both handles hold one, the deframer's with nstreams == 1.  The host keeps ONE upper bound of
+// the carried bits for all streams; hdlc_plan (hdlc_host.hpp) turns it and a push's length into every size here.
+struct HdlcCore {
+    size_t nstreams = 1, min_size = 0, max_size = 0;
+    int flags = 0;                                // RR_HDLC_*
+    Carried<HdlcState> st;                        // in(): what the streams so far left behind, one per stream
+    Carried<unsigned char> cbits;                 // ... and its carried bits, one per byte: hdlc_carry_bits(max_size) per stream
+    size_t carry = 0;                             // the carried bits of any stream, at most
+    DevBuf<unsigned long long> raw, fl, ab, sf, offs, etotal, pstats, count;
     DevBuf<unsigned> tilecnt, ends;
     DevBuf<unsigned char> gmap, pmap, bmap, bstate, arena;
     DevBuf<int> fin;
+    size_t last_n = 0, last_carry = 0;            // the most recent push: its bits per stream, at most; the carry bound it began with
+    bool bfetched = true;                         // `bytes` holds the most recent push's
+    std::vector<unsigned char> bytes;
+    // Unsynced(0xff) in front of every stream; the caller waits for s
+    void init(size_t nstreams, size_t min_size, size_t max_size, int flags, hipStream_t s);
+    // every push, also one of nothing: it has no bytes and leaves every state alone
+    void begin(size_t n) { bytes.clear(); bfetched = true; last_n = n; }
+    // n > 0: reserves the workspace, fills stream 0's view (all of HdlcArgs but bits, n, w0 and recs) and the pitches of the
+    // others (rx may be null) -> the bounds of the push
+    HdlcRxBounds plan(size_t n, HdlcArgs& a, HdlcRxArgs* rx);
+    void advance(size_t n);                       // behind the launches: the out halves are what the next push starts from
+    HdlcRxBounds bounds() const { return hdlcrx_bounds(nstreams, last_carry, last_n); }      // of the most recent push
+    // The read-back of a push the caller has waited for, one download each (`count` is read by the handle, in front of its
+    // records).  The counters of every stream's HdlcState, 3 per stream; before: the pair's other half, what the push started from
+    std::vector<unsigned long long> fetch_stats(bool before, hipStream_t s) const;
+    const std::vector<unsigned char>& fetch_bytes(hipStream_t s);             // only behind a push whose records stood the checks
+    size_t arena_len() const { return last_n ? bounds().arena : 0; }
+    const unsigned char* arena_dev() const { return arena_len() ? arena.p : nullptr; }
+};
+
+// HdlcDeframer (hdlc_deframer.rs:80-232) over windows of a bit stream (kernels_hdlc.hip): no stream protocol (work_dev is an
+// error).  The one-stream case of HdlcCore; the handle's own are the stream position, the byte source and the rr_hdlc_frame records.
+struct HdlcDeframer : BatchBlock {
+    HdlcCore core;
+    unsigned long long w0 = 0;                    // bits of the stream so far
     DevBuf<HdlcRec> recs;
     DevBuf<unsigned char> h_bits;                 // push_host(): the host window's device copy
-    size_t last_n = 0;                            // the most recent push: its bits, where they began, its bounds
-    unsigned long long last_w0 = 0;
-    size_t b_nv = 0, b_frames = 0, b_arena = 0;
-    bool fetched = true, bfetched = true;         // `frames` / `bytes` hold the most recent push's
-    std::vector<rr_hdlc_frame> frames;            // ... ascending by pos
-    std::vector<unsigned char> bytes;
+    bool fetched = true;                          // `frames` holds the most recent push's
+    std::vector<rr_hdlc_frame> frames;           // ... ascending by pos
     HdlcDeframer(size_t min_size, size_t max_size, int flags);
     void push_dev(const unsigned char* d_bits, size_t n, hipStream_t s);
     void push_host(const unsigned char* bits, size_t n);
     const std::vector<rr_hdlc_frame>& fetch_frames();         // waits for the most recent push
     const std::vector<unsigned char>& fetch_bytes();
-    const unsigned char* arena_dev() const { return last_n ? arena.p : nullptr; }
-    size_t arena_len() const { return last_n ? b_arena : 0; }
     void fetch_stats(unsigned long long out[3]);
 };
 
@@ -317,40 +336,26 @@ struct SymbolSync : BatchBlock {
 };
 
 // BinarySlicer -> [XorConst(1)] -> [NrziDecode] -> [Descrambler] -> HdlcDeframer x nstreams over ragged windows of nstreams f32
-// symbol streams (kernels_hdlcrx.hip): no stream protocol (work_dev is an error).  Each stream's state between pushes — the bit
-// chain's (RX_ST_*), the deframer's (HdlcState), its carried bits, its own stream position — stays on the device.  The host keeps
-// one upper bound of the carried bits for all streams and sizes everything it reads back from that, nstreams and n_cap
-// (hdlcrx_host.hpp).
+// symbol streams (kernels_hdlcrx.hip): no stream protocol (work_dev is an error).  HdlcCore with the bit chain in front: the handle's
+// own are each stream's chain state between pushes (RX_ST_*, with its position), the symbol source and the rr_hdlc_stream_frame records.
 struct HdlcReceiver : BatchBlock {
-    size_t nstreams, min_size, max_size;
-    int flags;                                    // RR_HDLC_*
+    HdlcCore core;
     BitsCfg cfg{};                                // invert, nrzi, dmask
     Carried<unsigned long long> bst;              // in(): RX_ST_N words per stream
-    Carried<HdlcState> st;                        // in(): one per stream
-    Carried<unsigned char> cbits;                 // in(): hdlc_carry_bits(max_size) bytes per stream, one carried bit each
-    size_t carry = 0;                             // the carried bits of any stream, at most
-    DevBuf<unsigned long long> raw, fl, ab, sf, offs, etotal, pstats, count;
-    DevBuf<unsigned> tilecnt, ends;
-    DevBuf<unsigned char> gmap, pmap, bmap, bstate, arena;
-    DevBuf<int> fin;
     DevBuf<HdlcRxRec> recs;
     DevBuf<float> h_syms;                         // push_host(): the host buffers' device copies
     DevBuf<unsigned long long> h_counts;
-    size_t last_cap = 0;                          // the most recent push: its n_cap and its bounds
-    size_t b_carry = 0;
-    bool fetched = true, bfetched = true;         // `frames` / `bytes` hold the most recent push's
+    bool fetched = true;                          // `frames` holds the most recent push's
     std::vector<rr_hdlc_stream_frame> frames;     // ... ascending by (stream, pos)
-    std::vector<unsigned char> bytes;
     HdlcReceiver(size_t nstreams, int bit_flags, unsigned long long mask, unsigned long long seed, unsigned len, size_t min_size,
                  size_t max_size, int hdlc_flags);
     void push_dev(const float* d_syms, size_t stride, size_t n_cap, const unsigned long long* d_counts, hipStream_t s);
     void push_host(const float* syms, size_t stride, size_t n_cap, const size_t* counts);
     const std::vector<rr_hdlc_stream_frame>& fetch_frames();  // waits for the most recent push
     const std::vector<unsigned char>& fetch_bytes();
-    size_t arena_len() const;
-    const unsigned char* arena_dev() const { return arena_len() ? arena.p : nullptr; }
     std::vector<unsigned long long> fetch_stats();            // 3 per stream
     std::vector<unsigned long long> fetch_consumed();         // 1 per stream
+    std::vector<unsigned long long> positions(const unsigned long long* d_bst) const;    // RX_ST_POS of every stream, one download
 };
 
 }  // namespace rr

@@ -1,7 +1,7 @@
 // hdlc_host.hpp — the host-only logic behind rr_hdlc_deframer_create / _push / _push_dev, rr_hdlc_frames, rr_hdlc_frame_bytes and
-// rr_hdlc_stats: the refusals, the carry bound, the bounds of a push, the validation of everything the device wrote, and the
-// clamped copy-outs.  No HIP in here, so tests/cpp/test_hdlc_hostlogic.cpp builds it with the host sanitizers and drives it without
-// a device.  Every host buffer is sized from the push length, max_size and the carry length the host tracks itself, never from a
+// rr_hdlc_stats: the refusals, the carry bound, the bounds and the workspace plan of a push (which rr_hdlc_receiver sizes its
+// streams' shares by as well), the validation of everything the device wrote, and the clamped copy-outs.  No HIP in here, so
+// tests/cpp/test_hdlc_hostlogic.cpp builds it with the host sanitizers and drives it without a device.  Every host buffer is sized from the push length, max_size and the carry length the host tracks itself, never from a
 // number the device wrote; what the device wrote is checked against those bounds BEFORE it is used as a size or an index.
 #pragma once
 #include <algorithm>
@@ -11,6 +11,7 @@
 
 #include "../../include/rustradio_amd.h"
 #include "hdlc_core.hpp"
+#include "hdlc_dims.hpp"
 
 namespace rr {
 
@@ -53,6 +54,27 @@ inline HdlcBounds hdlc_bounds(size_t carry, size_t n) {
     return b;
 }
 inline size_t hdlc_next_carry(size_t carry, size_t n, size_t max_size) { return std::min(hdlc_carry_bits(max_size), carry + n); }
+
+// The workspace of ONE stream's share of such a push, in the units the kernels index by (HdlcArgs, kernels.hpp): every buffer a
+// handle reserves and every pitch and capacity it hands to the device is one of these numbers, times its streams.
+struct HdlcPlan {
+    HdlcBounds one;       // hdlc_bounds(carry, n): nv_max, rec_cap and arena_cap
+    size_t ntiles = 0;    // tiles of HDLC_T virtual bits: tilecnt / offs
+    size_t nwords = 0;    // words of raw / fl / ab / sf: 64 per tile, and one behind the last tile's
+    size_t ecap = 0;      // flag ends at least 7 bits apart, two to spare: ends / gmap / pmap, and ends_cap
+    size_t nblocks = 0;   // blocks of HDLC_GB gaps: bmap / bstate
+    size_t carry_cap = 0; // bytes of cin / cout
+};
+inline HdlcPlan hdlc_plan(size_t carry, size_t n, size_t max_size) {
+    HdlcPlan p;
+    p.one = hdlc_bounds(carry, n);
+    p.ntiles = (p.one.nv + HDLC_T - 1) / HDLC_T;
+    p.nwords = p.ntiles * (HDLC_T / 64) + 1;
+    p.ecap = p.one.nv / 7 + 2;
+    p.nblocks = (p.ecap + HDLC_GB - 1) / HDLC_GB;
+    p.carry_cap = hdlc_carry_bits(max_size);
+    return p;
+}
 
 // The frame count the device left, before it sizes anything.
 inline const char* hdlc_check_count(unsigned long long count, const HdlcBounds& b) {

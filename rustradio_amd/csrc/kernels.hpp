@@ -1,6 +1,7 @@
 // kernels.hpp — host-callable launchers of the HIP kernels (one TU per kernel family).
 #pragma once
 #include "common.hpp"
+#include "hdlc_dims.hpp"
 #include "nan_fix.hpp"
 #include "symsync_core.hpp"
 
@@ -450,14 +451,12 @@ void launch_line(const LineArgs& a, hipStream_t s);
 // ---- kernels_hdlc.hip: HdlcDeframer (hdlc_deframer.rs:123-232) over the next n bits of a stream (hdlc_core.hpp holds the
 //      arithmetic) -------------------------------------------------------------------------------------------------------------------------
 // The VIRTUAL stream of a push: the st_in->count bits the stream so far left in cin (HDLC_HALO bits, then the raw bits of the gap
-// still open), then bits[0 .. n).  nv_max >= count + n is the host's own bound; it alone sizes the grids and the scratch:
-// nwords = 64 ntiles words each of raw / fl / ab / sf (ntiles = ceil(nv_max / HDLC_T)), ends_cap = nv_max / 7 + 2 flag ends and
-// gap maps, ceil(ends_cap / HDLC_GB) block maps and states.  Frames go to arena (arena_cap bytes, zeroed by the caller) at byte
-// floor((s + 1) / 8) of the gap's first flag end s, their records to recs in no order, *count of them; pstats: this push's share
-// of the three counters.  st_out / cout: what the next push starts from (distinct from st_in / cin).  Seven launches whatever the
-// bits hold; n == 0 launches nothing.
-constexpr int HDLC_T = 4096;                  // virtual bits of one tile
-constexpr int HDLC_GB = 256;                  // gaps of one block of the map scan
+// still open), then bits[0 .. n).  nv_max >= count + n is the host's own bound; it alone sizes the grids and the scratch, and
+// hdlc_plan (hdlc_host.hpp) is the one place that says how: the words of raw / fl / ab / sf, the tiles of tilecnt / offs, ends_cap
+// flag ends and gap maps, the block maps and states (HDLC_T and HDLC_GB: hdlc_dims.hpp).  Frames go to arena (arena_cap bytes,
+// zeroed by the caller) at byte floor((s + 1) / 8) of the gap's first flag end s, their records to recs in no order, *count of
+// them; pstats: this push's share of the three counters.  st_out / cout: what the next push starts from (distinct from st_in /
+// cin).  Seven launches whatever the bits hold; n == 0 launches nothing.
 struct HdlcState {
     unsigned long long stats[3];              // decoded, crc_error, bitfixed so far
     unsigned count;                           // carried bits
@@ -500,9 +499,10 @@ void launch_hdlc(const HdlcArgs& a, hipStream_t s);
 //      nstreams independent streams (hdlcrx_core.hpp holds the bit chain in word form, hdlc_body.hpp the deframer's kernels) -----
 // Stream c: min(counts ? counts[c] : n_cap, n_cap) f32 symbols at syms + c stride, read on the device; nothing at or beyond
 // that count is read.  `h` is stream 0's view with the HOST's bounds in nv_max / ntiles / ends_cap / arena_cap (one number serves
-// all streams) and a null `bits`; stream c's buffers stand c pitches further on: p_words words of raw / fl / ab / sf, p_tiles of
-// tilecnt / offs, p_ends of ends / gmap / pmap, p_blocks of bmap / bstate, p_carry bytes of cin / cout, p_arena bytes of arena,
-// one etotal / fin / st_in / st_out and three pstats each.  bst_in / bst_out: RX_ST_N words per stream (hdlcrx_core.hpp).
+// all streams) and a null `bits`; stream c's buffers stand c pitches further on, which are hdlc_plan's numbers: p_words words of
+// raw / fl / ab / sf, p_tiles of tilecnt / offs, p_ends of ends / gmap / pmap, p_blocks of bmap / bstate, p_carry bytes of cin /
+// cout, p_arena bytes of arena, one etotal / fin / st_in / st_out and three pstats each.  bst_in / bst_out: RX_ST_N words per
+// stream (hdlcrx_core.hpp).
 // h.count is ONE counter and recs ONE list of rec_cap records for all streams; a record's start is absolute (c p_arena + ...).
 // The seven launches of launch_hdlc with the stream as the grid's y, whatever nstreams and the symbols are; n_cap == 0 launches
 // nothing.  A stream with no symbols has its state copied from the in to the out buffers.

@@ -64,6 +64,25 @@ int main() {
         c = hdlc_next_carry(c, 0, 3);
         CHECK(c == hdlc_carry_bits(3));
     }
+    // the plan of a push at the seams the kernels index by: tiles of HDLC_T = 4096 virtual bits, 64 words each and one more word;
+    // a flag end every 7 bits and two more; blocks of HDLC_GB = 256 gaps
+    {
+        HdlcPlan p = hdlc_plan(8, 1, 50);
+        CHECK(p.one.nv == 9 && p.ntiles == 1 && p.nwords == 65 && p.ecap == 3 && p.nblocks == 1 && p.one.frames == 1 && p.one.arena == 1);
+        CHECK(p.carry_cap == hdlc_carry_bits(50));
+        p = hdlc_plan(8, 4088, 50);
+        CHECK(p.one.nv == 4096 && p.ntiles == 1);
+        p = hdlc_plan(8, 4089, 50);
+        CHECK(p.one.nv == 4097 && p.ntiles == 2 && p.nwords == 129);
+        p = hdlc_plan(8, 1776, 50);
+        CHECK(p.one.nv == 1784 && p.ecap == 256 && p.nblocks == 1);
+        p = hdlc_plan(8, 1777, 50);
+        CHECK(p.one.nv == 1785 && p.ecap == 257 && p.nblocks == 2);
+        CHECK(p.carry_cap == hdlc_carry_bits(50) && hdlc_plan(45, 4096, 0).carry_cap == hdlc_carry_bits(0));
+        const HdlcBounds b = hdlc_bounds(45, 4096);                 // `one` is hdlc_bounds of the same push
+        p = hdlc_plan(45, 4096, 1500);
+        CHECK(p.one.nv == b.nv && p.one.frames == b.frames && p.one.arena == b.arena);
+    }
     // the validation
     const u64 zero[3] = {0, 0, 0};
     {

@@ -60,6 +60,13 @@ int main() {
         CHECK(b.one.nv == 4141 && b.one.frames == 512 && b.one.arena == 517 && b.frames == 1536 && b.arena == 1551 && b.nstreams == 3);
         CHECK(hdlcrx_check_count(1536, b) == nullptr && str(hdlcrx_check_count(1537, b)) == "hdlc receiver: frame count beyond the bound");
         CHECK(str(hdlcrx_check_count(~0ull, b)) == "hdlc receiver: frame count beyond the bound");
+        // one stream's share is the plan's of the same push (hdlc_plan sizes the workspace, these bounds the read-back)
+        const size_t ns[] = {1, 4088, 4089, 1776, 1777, 1u << 20};
+        for (size_t n : ns)
+            for (size_t mx : {(size_t)0, (size_t)50, (size_t)65535}) {
+                const HdlcBounds one = hdlcrx_bounds(3, 8, n).one, p = hdlc_plan(8, n, mx).one;
+                CHECK(one.nv == p.nv && one.frames == p.frames && one.arena == p.arena);
+            }
         size_t c = 8;
         c = hdlc_next_carry(c, 100, 40);
         CHECK(c == 108);

@@ -281,6 +281,42 @@ def test_one_stream_equals_the_single_stream_handles_record_for_record():
         assert tuple(rx.stats()[0]) == one.stats()
 
 
+def test_a_workspace_grown_once_serves_smaller_pushes_in_both_handle_families():
+    """pushes of 10, 9,000, 0 and 10 symbols: the workspace both handle families now plan in one place (hdlc_plan, HdlcCore) grows
+    over two tile seams, sits out a push and is reused far larger than the last push needs.  plant() finds no room for a frame
+    around pushes of 10 symbols, so one is laid by hand: its last bit is bit 8,999, which the scrambler's 17 bits of delay put 6
+    symbols into the last push, and it is open across the empty one."""
+    cfg = (1, 50, FIX, "nrzi+g3ruh")
+    rng = np.random.default_rng(19)
+    lens = [10, 9000, 0, 10]
+    bits = hm.draw_stream(rng, sum(lens)).tolist()
+    fb = frame_bits(rng.integers(0, 256, 30, dtype=np.uint8).tobytes(), 2, 1)
+    bits[9000 - len(fb):9000] = fb
+    s = hx.line_encode(bits, *hx.LINE_CONFIGS[cfg[3]])
+    rx, one, mod = make_rx(1, cfg), Single(cfg), model(cfg)
+    at, per_push, want = 0, [], []
+    for n in lens:
+        x = s[at:at + n]
+        at += n
+        if n:
+            feed(rx, x[None, :])
+            one.push(x)
+        else:                                   # both handles are told of the empty push: it has no frames
+            rx.push_dev(0, 0, 0)
+            one.df.push(np.zeros(0, np.uint8))
+        got, ref = rx.frames(), one.df.frames()
+        assert len(got) == len(ref)
+        for k in ("pos", "start", "len", "flags"):
+            assert np.array_equal(got[k], ref[k]), (n, k)
+        assert np.array_equal(rx.frame_bytes(), one.df.frame_bytes()), n
+        assert tuple(int(v) for v in rx.stats()[0]) == one.stats(), n
+        per_push.append(rx.result()[0])
+        want.append(mod.push(x))
+    assert per_push == want and tuple(int(v) for v in rx.stats()[0]) == mod.stats()
+    assert [len(p) for p in per_push][::2] == [0, 0] and len(per_push[1]) > 10 and len(per_push[3]) == 1
+    assert len(per_push[3][0][1]) == 30 and int(rx.consumed()[0]) == sum(lens)
+
+
 def test_launch_count_does_not_depend_on_streams_or_symbols(bases):
     """seven launches and one profiling bracket for 1 and for 4,096 streams, for empty and for full streams"""
     cfg, lens, sy, _ = bases
