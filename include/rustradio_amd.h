@@ -664,6 +664,68 @@ int rr_hdlc_receiver_consumed(rr_block *b, unsigned long long *symbols, size_t c
 /* *tile_bits, *carry_bits: as rr_hdlc_deframer_dims, for every stream. */
 int rr_hdlc_receiver_dims(const rr_block *b, size_t *tile_bits, size_t *carry_bits);
 
+/* [ComplexToMag2 ->] PwmDecoder::builder(high_threshold, short_width, long_width, frame_gap, reset_gap) with every builder
+ * setting (src/pwm_decoder.rs:165-266; process :385-513): OOK power samples in, PWM frames out, the whole graph of
+ * examples/restaurant_pager.rs behind one handle.  A batch block like rr_hdlc_deframer: rr_block_work on the handle is an error.
+ * A push takes the next n samples of the stream and delivers the frames of every transmission whose reset sample lies inside it,
+ * bit-identical to the reference's machine whatever the split into pushes (comparisons and integer counts only):
+ *   the slicer (:386-424) starts low; in low p <= high_threshold stays low, in high p >= low_threshold stays high, so a NaN rises
+ *     from low and falls from high; the first sample of a run belongs to it;
+ *   a pulse is short or long when its width lies within pulse_tolerance of that nominal width, the nearer one when both do, short
+ *     on a tie (:434-446); it is data when the low run behind it is shorter than frame_gap, and, without RR_PWM_GAP_DELIMITER,
+ *     also when it is the last one in front of a frame gap (:399-402, :412-416); its bit is (short == short_is_one);
+ *   the gap events fire on the sample at which the low run EQUALS frame_gap / reset_gap (:398-409), the frame first;
+ *   a frame is accepted when every data pulse is valid, it has 1 .. max_frame_bits of them (one more rejects it up to its gap,
+ *     :447-460) and exactly frame_bits if that is not 0 (:471-481); first_sample is the rise of its first pulse;
+ *   within a transmission the first max_distinct_frames distinct patterns are the candidates, `repeats` counts the accepted
+ *     frames equal to each (:485-497); the reset event delivers those with repeats >= min_repeats in candidate order (:502-513).
+ * in_elem_size 4: the f32 power stream.  8: Complex samples, norm_sqr with the reference's three f32 roundings in front, so both
+ * see the same power bit for bit.  Both thresholds and the tolerance are explicit (the builder's defaults, high / 2 and
+ * |long - short| / 2, are the mirrors' business); frame_bits 0 is None.
+ * The state between pushes — the slicer state, the open run's length (64 bits), the pending pulse, the open frame (bits, count,
+ * invalid flag, start), the candidate table and the stream position — stays on the device and is bounded by the settings; the
+ * host never reads it to decide a size.  The reference's pending-queue back-pressure (:602-610) has no counterpart.
+ * NULL + rr_last_error, said before any device is touched: every refusal of validate() (:101-162) in its words ("PwmDecoder high
+ * threshold must be finite and greater than zero", ...), "unknown pwm decoder flags", "pwm decoder: Float (4) or Complex (8)
+ * input only", and the limits of a handle, refused, never clamped: "pwm decoder: max_frame_bits beyond 16384", "pwm decoder:
+ * max_distinct_frames beyond 1024", "pwm decoder: max_frame_bits x max_distinct_frames beyond 4194304" (the defaults, 4096 x 256,
+ * are a quarter of that), "pwm decoder: width or gap beyond 2^62", "pwm decoder: min_repeats beyond 2^32 - 1". */
+enum { RR_PWM_SHORT_IS_ZERO = 1, RR_PWM_GAP_DELIMITER = 2 };    /* short_is_one(false) / gap_pulse(PwmGapPulse::Delimiter) */
+typedef struct {
+    unsigned long long first_sample;   /* PwmFrame::first_sample: stream position of the first copy's first rise */
+    unsigned long long start;          /* first bit of the frame in the bit arena of this push */
+    unsigned len;                      /* PwmFrame::len: bits */
+    unsigned repeats;                  /* PwmFrame::repeats */
+} rr_pwm_frame;                        /* 24 bytes */
+rr_block *rr_pwm_decoder_create(float high_threshold, float low_threshold, size_t short_width, size_t long_width,
+                                size_t pulse_tolerance, size_t frame_gap, size_t reset_gap, size_t frame_bits, size_t max_frame_bits,
+                                size_t max_distinct_frames, size_t min_repeats, int flags, size_t in_elem_size);
+/* The next n samples of the stream from the device buffer d_samples.  RR_ERR before any device is touched: "pwm decoder: more
+ * than 2^30 samples in one push", "pwm decoder: null samples" (n > 0 with a null buffer), "pwm decoder: push after flush".
+ * Enqueued on hip_stream (used as given) and returns without waiting; SEVEN launches whose grids depend on n and the settings
+ * alone, never on what the samples hold (silence, one burst or an edge on every sample).  Everything is sized from n and the
+ * settings: n edges, n / 2 + 2 pulses, max_distinct_frames + n / 2 + 2 records.  n == 0 launches nothing, has no frames and
+ * leaves every state alone. */
+int rr_pwm_decoder_push_dev(rr_block *b, const void *d_samples, size_t n, void *hip_stream);
+/* The same with a host pointer: copies the samples down, runs and waits. */
+int rr_pwm_decoder_push(rr_block *b, const void *samples, size_t n);
+/* EOF (finalize_eof, :612-618): delivers the open transmission's candidates as a push of its own (two launches) and throws the
+ * open frame away.  Afterwards the handle refuses pushes and flushes ("pwm decoder: push after flush"). */
+int rr_pwm_decoder_flush(rr_block *b, void *hip_stream);
+/* The frames the most recent push or flush delivered, in the reference's delivery order.  Waits for it, writes the first
+ * min(*total, cap) records; rec == NULL with cap == 0 only counts (the contract of rr_hdlc_frames).  Everything the device wrote
+ * is checked against the bounds of the push before it is used ("pwm decoder: ..." and no frames otherwise). */
+int rr_pwm_frames(rr_block *b, rr_pwm_frame *rec, size_t cap, size_t *total);
+/* The bit arena of the most recent push or flush, which rec.start indexes: one u8 of 0 or 1 per bit (PwmFrame::bits, and what the
+ * bit blocks here take), frame behind frame.  *total bits, the first min(*total, cap) copied. */
+int rr_pwm_frame_bits(rr_block *b, unsigned char *out, size_t cap, size_t *total);
+/* The same arena on the device (ordered behind the push on its stream); valid until the next push.  Waits for the push (the
+ * arena's length is the device's own, checked count).  NULL and *n_total = 0 when nothing was delivered. */
+const void *rr_pwm_bits_dev(rr_block *b, size_t *n_total);
+/* *tile_samples = the samples of one tile of the slicer kernels; tile t of a push begins at its sample t * tile_samples.  The two
+ * one-workgroup scans take 1024 tiles in one go. */
+int rr_pwm_decoder_dims(const rr_block *b, size_t *tile_samples);
+
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)
  * as wired in examples/ax25-1200-rx.rs:238-247: f32 in, Complex out, ONE decimating FIR with the composite

@@ -142,6 +142,23 @@ unsafe extern "C" {
     fn rr_hdlc_receiver_consumed(b: *mut RrBlock, symbols: *mut u64, cap: usize, total: *mut usize) -> c_int;
     #[allow(dead_code)]
     fn rr_hdlc_receiver_dims(b: *const RrBlock, tile_bits: *mut usize, carry_bits: *mut usize) -> c_int;
+    // (declared for completeness: PwmDecoder's dst is an NCWriteStream<PwmFrame>, a message stream, so its block is not one of the
+    //  window blocks below; rr_pwm_frames (a struct) and rr_pwm_frame_bits (byte pointers) have types outside this file's FFI map;
+    //  not written yet)
+    #[allow(dead_code)]
+    fn rr_pwm_decoder_create(high_threshold: f32, low_threshold: f32, short_width: usize, long_width: usize, pulse_tolerance: usize,
+                             frame_gap: usize, reset_gap: usize, frame_bits: usize, max_frame_bits: usize, max_distinct_frames: usize,
+                             min_repeats: usize, flags: c_int, in_elem_size: usize) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_pwm_decoder_push_dev(b: *mut RrBlock, d_samples: *const c_void, n: usize, hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_pwm_decoder_push(b: *mut RrBlock, samples: *const c_void, n: usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_pwm_decoder_flush(b: *mut RrBlock, hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_pwm_bits_dev(b: *mut RrBlock, n_total: *mut usize) -> *const c_void;
+    #[allow(dead_code)]
+    fn rr_pwm_decoder_dims(b: *const RrBlock, tile_samples: *mut usize) -> c_int;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;

@@ -813,8 +813,85 @@ class HdlcDeframer(Block):
         return d.value, e.value, f.value
 
 
+PWM_SHORT_IS_ZERO, PWM_GAP_DELIMITER = 1, 2      # RR_PWM_*
+# rr_pwm_frame
+PWM_FRAME = np.dtype([("first_sample", np.uint64), ("start", np.uint64), ("len", np.uint32), ("repeats", np.uint32)], align=True)
+
+
+class PwmDecoder(Block):
+    """PwmDecoder::builder(high_threshold, short_width, long_width, frame_gap, reset_gap) with every builder setting behind one
+    handle (rr_pwm_decoder_create; src/pwm_decoder.rs:165-266, 385-513; not a stream block: work() raises): the next samples
+    of an OOK power stream in (dtype float32), or of the Complex stream in front of ComplexToMag2 (dtype complex64: the whole
+    graph of examples/restaurant_pager.rs), the frames of every transmission whose reset sample lies inside them out.  The
+    builder's defaults are supplied here: low_threshold = high_threshold / 2 in f32 and pulse_tolerance = |long - short| / 2
+    (:85-88); frame_bits None is gap-delimited.  The slicer, the open frame and the candidate table stay on the device between
+    pushes.  See include/rustradio_amd.h."""
+
+    def __init__(self, high_threshold: float, short_width: int, long_width: int, frame_gap: int, reset_gap: int, *,
+                 low_threshold=None, pulse_tolerance=None, frame_bits=None, max_frame_bits: int = 4096,
+                 max_distinct_frames: int = 256, min_repeats: int = 1, short_is_one: bool = True, delimiter: bool = False,
+                 dtype=np.float32):
+        dt = np.dtype(dtype)
+        high = np.float32(high_threshold)
+        low = np.float32(high / np.float32(2.0)) if low_threshold is None else np.float32(low_threshold)
+        tol = abs(int(long_width) - int(short_width)) // 2 if pulse_tolerance is None else int(pulse_tolerance)
+        if frame_bits is not None and int(frame_bits) == 0:      # (0 is None across the C ABI: validate()'s own refusal, :133-137)
+            raise ValueError("PwmDecoder fixed frame length must be greater than zero")
+        flags = (0 if short_is_one else PWM_SHORT_IS_ZERO) | (PWM_GAP_DELIMITER if delimiter else 0)
+        args = [int(short_width), int(long_width), tol, int(frame_gap), int(reset_gap), 0 if frame_bits is None else int(frame_bits),
+                int(max_frame_bits), int(max_distinct_frames), int(min_repeats)]
+        if any(a < 0 for a in args):
+            raise ValueError("PwmDecoder: a width, gap or count below zero")
+        super().__init__(lib().rr_pwm_decoder_create(float(high), float(low), *args, flags, dt.itemsize), dt, np.uint8)
+
+    def dims(self) -> int:
+        """-> tile_samples (rr_pwm_decoder_dims)"""
+        t = C.c_size_t(0)
+        if lib().rr_pwm_decoder_dims(self._h, C.byref(t)) != 0:
+            raise RuntimeError(last_error())
+        return t.value
+
+    def push_dev(self, d_samples: int, n: int, stream: int = 0) -> None:
+        """rr_pwm_decoder_push_dev: the next n samples from a raw device pointer; asynchronous on `stream`; frames() waits"""
+        if lib().rr_pwm_decoder_push_dev(self._h, C.c_void_p(d_samples), int(n), C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+
+    def push(self, samples):
+        """rr_pwm_decoder_push on host samples -> [(bits: uint8[], repeats, first_sample)] of the transmissions that ended inside them"""
+        x = np.ascontiguousarray(samples, self.in_dtype).ravel()
+        if lib().rr_pwm_decoder_push(self._h, _ptr(x) if len(x) else None, len(x)) != 0:
+            raise ValueError(last_error())
+        return self.result()
+
+    def flush(self, stream: int = 0):
+        """rr_pwm_decoder_flush: EOF -> the open transmission's candidates, as push() returns them; pushes are refused afterwards"""
+        if lib().rr_pwm_decoder_flush(self._h, C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+        return self.result()
+
+    def frames(self) -> np.ndarray:
+        """-> PWM_FRAME per frame of the most recent push or flush, in delivery order (rr_pwm_frames; waits)"""
+        return _fetch(lib().rr_pwm_frames, self._h, PWM_FRAME)[0]
+
+    def frame_bits(self) -> np.ndarray:
+        """-> the bit arena of the most recent push or flush, which frames()["start"] indexes (rr_pwm_frame_bits; waits)"""
+        return _fetch(lib().rr_pwm_frame_bits, self._h, np.uint8)[0]
+
+    def bits_dev(self):
+        """-> (raw device pointer or None, bits) of the same arena (rr_pwm_bits_dev; waits); valid until the next push"""
+        n = C.c_size_t(0)
+        p = lib().rr_pwm_bits_dev(self._h, C.byref(n))
+        return p, n.value
+
+    def result(self):
+        """frames() and frame_bits() of the most recent push or flush as [(bits, repeats, first_sample)]"""
+        rec = self.frames()
+        arena = self.frame_bits() if len(rec) else np.zeros(0, np.uint8)
+        return [(arena[int(r["start"]):int(r["start"]) + int(r["len"])].copy(), int(r["repeats"]), int(r["first_sample"])) for r in rec]
+
+
 # rr_hdlc_stream_frame
-HDLC_STREAM_FRAME = np.dtype([("pos", np.uint64), ("start", np.uint64), ("len", np.uint32), ("flags", np.uint32),
+HDLC_STREAM_FRAME =np.dtype([("pos", np.uint64), ("start", np.uint64), ("len", np.uint32), ("flags", np.uint32),
                               ("stream", np.uint32), ("reserved", np.uint32)], align=True)
 
 

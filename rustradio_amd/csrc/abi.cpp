@@ -83,7 +83,7 @@ template <class T> static T* as(const rr_block* b, const char* what, const char*
 }
 static const char NOT_WPCR[] = "not a wpcr handle", NOT_PDU[] = "not a stream_to_pdu handle", NOT_FRAMER[] = "not an hdlc framer handle";
 static const char NOT_DEFRAMER[] = "not an hdlc deframer handle", NOT_SYNC[] = "not a symbol sync handle";
-static const char NOT_RECEIVER[] = "not an hdlc receiver handle";
+static const char NOT_RECEIVER[] = "not an hdlc receiver handle", NOT_PWM[] = "not a pwm decoder handle";
 // a fetched list of (pos << shift) | val entries into the caller's two arrays
 template <class E> static void unpack(const std::vector<E>& e, unsigned shift, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
     *total = e.size();
@@ -490,6 +490,63 @@ int rr_hdlc_deframer_dims(const rr_block* b, size_t* tile_bits, size_t* carry_bi
     if (!d || !tile_bits || !carry_bits) { if (d) rr::set_last_error("rr_hdlc_deframer_dims: null argument"); return RR_ERR; }
     *tile_bits = rr::HDLC_T;
     *carry_bits = rr::hdlc_carry_bits(d->core.max_size);
+    return 0;
+}
+rr_block* rr_pwm_decoder_create(float high_threshold, float low_threshold, size_t short_width, size_t long_width, size_t pulse_tolerance,
+                                size_t frame_gap, size_t reset_gap, size_t frame_bits, size_t max_frame_bits, size_t max_distinct_frames,
+                                size_t min_repeats, int flags, size_t in_elem_size) {
+    if (const char* e = rr::pwm_check_create(high_threshold, low_threshold, short_width, long_width, pulse_tolerance, frame_gap, reset_gap,
+                                             frame_bits, max_frame_bits, max_distinct_frames, min_repeats, flags, in_elem_size))
+        return refuse_create(e);
+    const rr::PwmCfg c = rr::pwm_cfg(high_threshold, low_threshold, short_width, long_width, pulse_tolerance, frame_gap, reset_gap, frame_bits,
+                                     max_frame_bits, max_distinct_frames, min_repeats, flags);
+    return make_block([&] { return new rr::PwmDecoder(c, in_elem_size); });
+}
+int rr_pwm_decoder_push_dev(rr_block* b, const void* d_samples, size_t n, void* hip_stream) {
+    auto* d = as<rr::PwmDecoder>(b, "rr_pwm_decoder_push_dev", NOT_PWM);
+    if (!d) return RR_ERR;
+    if (const char* e = rr::pwm_check_push(d_samples, n, d->flushed)) { rr::set_last_error(e); return RR_ERR; }     // before any device is touched
+    return on_device(d, hip_stream, [&](hipStream_t s) { d->push_dev(d_samples, n, s); });
+}
+int rr_pwm_decoder_push(rr_block* b, const void* samples, size_t n) {
+    auto* d = as<rr::PwmDecoder>(b, "rr_pwm_decoder_push", NOT_PWM);
+    if (!d) return RR_ERR;
+    if (const char* e = rr::pwm_check_push(samples, n, d->flushed)) { rr::set_last_error(e); return RR_ERR; }
+    return guarded([&] { d->push_host(samples, n); });
+}
+int rr_pwm_decoder_flush(rr_block* b, void* hip_stream) {
+    auto* d = as<rr::PwmDecoder>(b, "rr_pwm_decoder_flush", NOT_PWM);
+    if (!d) return RR_ERR;
+    if (const char* e = rr::pwm_check_push(nullptr, 0, d->flushed)) { rr::set_last_error(e); return RR_ERR; }
+    return on_device(d, hip_stream, [&](hipStream_t s) { d->flush(s); });
+}
+int rr_pwm_frames(rr_block* b, rr_pwm_frame* rec, size_t cap, size_t* total) {
+    auto* d = as<rr::PwmDecoder>(b, "rr_pwm_frames", NOT_PWM);
+    if (!d) return RR_ERR;
+    if (!total || (cap && !rec)) { rr::set_last_error("rr_pwm_frames: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] { rr::pwm_copy_frames(d->fetch_frames(), rec, cap, total); });
+}
+int rr_pwm_frame_bits(rr_block* b, unsigned char* out, size_t cap, size_t* total) {
+    auto* d = as<rr::PwmDecoder>(b, "rr_pwm_frame_bits", NOT_PWM);
+    if (!d) return RR_ERR;
+    if (!total || (cap && !out)) { rr::set_last_error("rr_pwm_frame_bits: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] { rr::pwm_copy_bits(d->fetch_bits(), out, cap, total); });
+}
+const void* rr_pwm_bits_dev(rr_block* b, size_t* n_total) {
+    auto* d = as<rr::PwmDecoder>(b, "rr_pwm_bits_dev", NOT_PWM);
+    if (n_total) *n_total = 0;
+    if (!d) return nullptr;
+    size_t k = 0;
+    if (on_device(d, [&] { k = d->fetch_bits().size(); }) != 0) return nullptr;
+    if (n_total) *n_total = k;
+    return k ? d->arena.p : nullptr;
+}
+int rr_pwm_decoder_dims(const rr_block* b, size_t* tile_samples) {
+    auto* d = as<rr::PwmDecoder>(b, "rr_pwm_decoder_dims", NOT_PWM);
+    if (!d || !tile_samples) { if (d) rr::set_last_error("rr_pwm_decoder_dims: null argument"); return RR_ERR; }
+    *tile_samples = rr::PWM_T;
     return 0;
 }
 rr_block* rr_hdlc_receiver_create(size_t nstreams, int bit_flags, unsigned long long mask, unsigned long long seed, unsigned len,

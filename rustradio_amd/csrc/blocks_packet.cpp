@@ -1,5 +1,5 @@
 // blocks_packet.cpp — host side of the packet-side blocks (blocks_packet.hpp): the sync blocks, the burst and bit blocks, and the
-// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, SymbolSync, HdlcReceiver).  Citations are to the reference's src, as in blocks.cpp.
+// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver).  Citations are to the reference's src, as in blocks.cpp.
 #include "blocks_packet.hpp"
 
 #include <algorithm>
@@ -656,6 +656,94 @@ void HdlcDeframer::fetch_stats(unsigned long long out[3]) {
     settle();
     const std::vector<unsigned long long> now = core.fetch_stats(false, stream);
     std::copy(now.begin(), now.end(), out);
+}
+
+// ---- PwmDecoder (pwm_decoder.rs:385-513; kernels_pwm.hip) -------------------------------------------------------------------------------
+PwmDecoder::PwmDecoder(const PwmCfg& c, size_t es)
+    : BatchBlock(es == 8 ? "ComplexToMag2>PwmDecoder" : "PwmDecoder", es, 1,
+                 "PwmDecoder delivers frames: rr_pwm_decoder_push / rr_pwm_decoder_push_dev"),
+      cfg(c), pitch((size_t)pwm_pitch(c.max_bits)) {
+    st.zero(1, stream);                        // low, no run, no pulse, no frame, no candidates at sample 0 (:365-382)
+    fbits.zero(pitch, stream);
+    cand.zero(pitch * cfg.max_distinct, stream);
+    meta.zero(cfg.max_distinct, stream);
+    etotal.reserve(1);
+    count.reserve(2);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void PwmDecoder::run(const void* d_samples, size_t n, bool eof, hipStream_t s) {
+    last = pwm_plan(n, cfg.max_bits, cfg.max_distinct);
+    cls.reserve(std::max<size_t>(last.nthreads, 1)); ebits.reserve(std::max<size_t>(last.nthreads, 1));
+    tmap.reserve(std::max<size_t>(last.ntiles, 1)); tstate.reserve(std::max<size_t>(last.ntiles, 1));
+    tilecnt.reserve(std::max<size_t>(last.ntiles, 1)); offs.reserve(std::max<size_t>(last.ntiles, 1));
+    edges.reserve(std::max<size_t>(last.ecap, 1));
+    recs.reserve(last.frames);
+    arena.reserve(last.arena);
+    PwmArgs a{};
+    a.in = d_samples; a.es = (int)in_es; a.eof = eof ? 1 : 0;
+    a.n = (long)n; a.ntiles = (long)last.ntiles; a.ecap = (long)last.ecap;
+    a.cfg = cfg; a.pitch = pitch;
+    a.st_in = st.in(); a.st_out = st.out();
+    a.fbits_in = fbits.in(); a.fbits_out = fbits.out();
+    a.meta_in = meta.in(); a.meta_out = meta.out();
+    a.cand_in = cand.in(); a.cand_out = cand.out();
+    a.cls = cls.p; a.tmap = tmap.p; a.tstate = tstate.p; a.ebits = ebits.p;
+    a.tilecnt = tilecnt.p; a.offs = offs.p; a.edges = edges.p; a.etotal = etotal.p;
+    a.recs = recs.p; a.rec_cap = (long)last.frames; a.arena = arena.p; a.arena_cap = (long)last.arena; a.count = count.p;
+    prof_begin(s);
+    launch_pwm(a, s);
+    prof_end(s);
+    st.flip(); fbits.flip(); meta.flip(); cand.flip();
+    w0 += n;
+    fetched = false;
+}
+void PwmDecoder::push_dev(const void* d_samples, size_t n, hipStream_t s) {
+    if (const char* e = pwm_check_push(d_samples, n, flushed)) throw Error(e);
+    frames.clear();
+    bits.clear();
+    fetched = true;                            // a push of no samples has no frames and leaves every state alone
+    last = PwmPlan{};
+    if (!n) return;
+    run(d_samples, n, false, s);
+}
+void PwmDecoder::push_host(const void* samples, size_t n) {
+    host_call([&] {
+        if (const char* e = pwm_check_push(samples, n, flushed)) throw Error(e);
+        if (n) {
+            h_in.reserve(n * in_es);
+            hstage().h2d(h_in.p, samples, n * in_es, stream);
+        }
+        push_dev(h_in.p, n, stream);
+    });
+}
+void PwmDecoder::flush(hipStream_t s) {
+    if (const char* e = pwm_check_push(nullptr, 0, flushed)) throw Error(e);
+    frames.clear();
+    bits.clear();
+    flushed = true;
+    run(nullptr, 0, true, s);
+}
+const std::vector<rr_pwm_frame>& PwmDecoder::fetch_frames() {
+    settle();
+    if (!fetched) {
+        fetched = true;                        // (a refused push has no frames: the refusal is not repeated)
+        unsigned long long k[2] = {0, 0};
+        stage_download_sync(k, count.p, sizeof k, stream);
+        if (const char* e = pwm_check_counts(k[0], k[1], last)) throw Error(e);
+        std::vector<rr_pwm_frame> r((size_t)k[0]);
+        if (k[0]) stage_download_sync(r.data(), recs.p, (size_t)k[0] * sizeof(rr_pwm_frame), stream);
+        if (const char* e = pwm_validate(r, k[1], last, cfg.max_bits, cfg.min_repeats, w0)) throw Error(e);
+        std::vector<unsigned char> b((size_t)k[1]);
+        if (k[1]) stage_download_sync(b.data(), arena.p, (size_t)k[1], stream);
+        if (const char* e = pwm_validate_bits(b)) throw Error(e);
+        frames.swap(r);
+        bits.swap(b);
+    }
+    return frames;
+}
+const std::vector<unsigned char>& PwmDecoder::fetch_bits() {
+    fetch_frames();
+    return bits;
 }
 
 // ---- SymbolSync (symbol_sync.rs:46-217; kernels_sync.hip) ---------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 #pragma once
 #include "blocks.hpp"
 #include "hdlcrx_host.hpp"
+#include "pwm_host.hpp"
 
 namespace rr {
 
@@ -311,6 +312,37 @@ struct HdlcDeframer : BatchBlock {
     const std::vector<rr_hdlc_frame>& fetch_frames();         // waits for the most recent push
     const std::vector<unsigned char>& fetch_bytes();
     void fetch_stats(unsigned long long out[3]);
+};
+
+// [ComplexToMag2 ->] PwmDecoder (pwm_decoder.rs:385-513) over windows of a power or Complex stream (kernels_pwm.hip): no stream
+// protocol (work_dev is an error).  Everything between pushes (PwmState, the open frame's bits, the candidate table) stays on the
+// device in pairs; the host keeps the stream position, which bounds first_sample, and the plan of the most recent push.
+struct PwmDecoder : BatchBlock {
+    PwmCfg cfg{};
+    size_t pitch;                                 // bytes of a candidate row
+    Carried<PwmState> st;                         // in(): what the stream so far left behind
+    Carried<unsigned char> fbits, cand;           // ... the open frame's bits; the candidates' bits
+    Carried<PwmCand> meta;                        // ... and their numbers
+    DevBuf<unsigned short> cls;
+    DevBuf<unsigned char> tmap, tstate, ebits, arena;
+    DevBuf<unsigned> tilecnt, offs, edges;
+    DevBuf<unsigned long long> etotal, count;
+    DevBuf<PwmRec> recs;
+    DevBuf<unsigned char> h_in;                   // push_host(): the host window's device copy
+    unsigned long long w0 = 0;                    // samples of the stream so far
+    PwmPlan last{};                               // the most recent push's
+    bool flushed = false;
+    bool fetched = true;                          // `frames` / `bits` hold the most recent push's
+    std::vector<rr_pwm_frame> frames;
+    std::vector<unsigned char> bits;
+    PwmDecoder(const PwmCfg& cfg, size_t es);
+    void push_dev(const void* d_samples, size_t n, hipStream_t s);
+    void push_host(const void* samples, size_t n);
+    void flush(hipStream_t s);
+    const std::vector<rr_pwm_frame>& fetch_frames();          // waits for the most recent push
+    const std::vector<unsigned char>& fetch_bits();
+private:
+    void run(const void* d_samples, size_t n, bool eof, hipStream_t s);
 };
 
 // SymbolSync (symbol_sync.rs:46-217) x nstreams over windows of nstreams f32 streams (kernels_sync.hip): no stream protocol

@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "hdlc_dims.hpp"
 #include "nan_fix.hpp"
+#include "pwm_core.hpp"
 #include "symsync_core.hpp"
 
 namespace rr {
@@ -547,6 +548,42 @@ struct SyncArgs {
     int spw;
 };
 void launch_sync(const SyncArgs& a, int which, hipStream_t s);
+
+// ---- kernels_pwm.hip: [ComplexToMag2 ->] PwmDecoder (pwm_decoder.rs:385-513) over the next n samples of a stream (pwm_core.hpp
+//      holds the arithmetic) -----------------------------------------------------------------------------------------------------------
+// in: n f32 power samples (es 4) or n Complex samples (es 8: norm_sqr with the reference's three roundings in front).  Scratch,
+// all sized from n by pwm_plan (pwm_host.hpp): cls / ebits one word / byte per thread of every tile, tmap / tstate / tilecnt /
+// offs one per tile, edges ecap >= n entries.  The carried halves (st, fbits, meta, cand: in and out distinct) hold the slicer
+// state, the open frame and the candidate table, `pitch` bytes per candidate row.  Deliveries: recs in delivery order, their bits
+// in arena at rec.start; count[0] = records, count[1] = arena bytes, both counted on past the capacities (the host refuses such a
+// push).  Seven launches whatever the samples hold; n == 0 launches nothing.  eof: no samples — the candidates are delivered
+// (two launches).
+struct PwmArgs {
+    const void* in;
+    int es, eof;
+    long n, ntiles, ecap;
+    PwmCfg cfg;
+    unsigned long long pitch;
+    const PwmState* st_in;
+    PwmState* st_out;
+    const unsigned char* fbits_in;
+    unsigned char* fbits_out;
+    const PwmCand* meta_in;
+    PwmCand* meta_out;
+    const unsigned char* cand_in;
+    unsigned char* cand_out;
+    unsigned short* cls;
+    unsigned char *tmap, *tstate, *ebits;
+    unsigned *tilecnt, *offs, *edges;
+    unsigned long long* etotal;
+    PwmRec* recs;
+    long rec_cap;
+    unsigned char* arena;
+    long arena_cap;
+    unsigned long long* count;
+};
+constexpr int PWM_LAUNCHES = 7;
+void launch_pwm(const PwmArgs& a, hipStream_t s);
 
 // ---- head fix of the fused FirFilter -> FftFilter blocks (stream start only, a few hundred samples) ----------------
 // z[m] = sum_k t1[k] V[voff + m + L1 - 1 - k], m < n: the front FirFilter's first outputs (fir.rs:166-177) from the virtual stream

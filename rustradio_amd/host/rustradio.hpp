@@ -936,6 +936,94 @@ public:
     }
 };
 
+// ---- PwmDecoder (src/pwm_decoder.rs:165-266, 385-513): the builder and the frames of its NCWriteStream<PwmFrame> ------------------------
+// (rr_pwm_decoder_create / rr_pwm_decoder_push / rr_pwm_decoder_flush / rr_pwm_frames / rr_pwm_frame_bits).  The builder holds the
+// reference's defaults (:76-98) and build<T>() refuses what validate() refuses, in its words.  push() takes the next samples of the
+// power stream (T = Float) or of the Complex stream in front of ComplexToMag2 (T = Complex, examples/restaurant_pager.rs) and
+// returns the frames of every transmission whose reset sample lies inside them; finish() is EOF.  The slicer, the open frame and
+// the candidates stay in the block from push to push; the pending queue's back-pressure (:602-610) has no counterpart.
+enum class PwmGapPulse { Data, Delimiter };
+struct PwmFrame {
+    std::vector<uint8_t> bits_;
+    size_t repeats_ = 0;
+    uint64_t first_sample_ = 0;
+    const std::vector<uint8_t>& bits() const { return bits_; }
+    size_t repeats() const { return repeats_; }
+    uint64_t first_sample() const { return first_sample_; }
+    size_t len() const { return bits_.size(); }
+    bool is_empty() const { return bits_.empty(); }
+};
+template <class T> class PwmDecoder;
+class PwmDecoderBuilder {
+    float high_, low_;
+    size_t short_, long_, tol_, fgap_, rgap_, frame_bits_ = 0, max_frame_bits_ = 4096, max_distinct_ = 256, min_repeats_ = 1;
+    bool fixed_ = false, short_is_one_ = true;
+    PwmGapPulse gap_pulse_ = PwmGapPulse::Data;
+    template <class T> friend class PwmDecoder;
+public:
+    PwmDecoderBuilder(float high_threshold, size_t short_width, size_t long_width, size_t frame_gap, size_t reset_gap)
+        : high_(high_threshold), low_(high_threshold / 2.0f), short_(short_width), long_(long_width),
+          tol_((long_width > short_width ? long_width - short_width : short_width - long_width) / 2), fgap_(frame_gap), rgap_(reset_gap) {}
+    PwmDecoderBuilder& low_threshold(float v) { low_ = v; return *this; }
+    PwmDecoderBuilder& pulse_tolerance(size_t v) { tol_ = v; return *this; }
+    PwmDecoderBuilder& frame_bits(size_t bits) { fixed_ = true; frame_bits_ = bits; return *this; }      // Some(bits)
+    PwmDecoderBuilder& any_frame_bits() { fixed_ = false; frame_bits_ = 0; return *this; }               // None
+    PwmDecoderBuilder& max_frame_bits(size_t v) { max_frame_bits_ = v; return *this; }
+    PwmDecoderBuilder& max_distinct_frames(size_t v) { max_distinct_ = v; return *this; }
+    PwmDecoderBuilder& min_repeats(size_t v) { min_repeats_ = v; return *this; }
+    PwmDecoderBuilder& short_is_one(bool v) { short_is_one_ = v; return *this; }
+    PwmDecoderBuilder& gap_pulse(PwmGapPulse v) { gap_pulse_ = v; return *this; }
+    template <class T = Float> PwmDecoder<T> build() const { return PwmDecoder<T>(*this); }
+};
+template <class T = Float> class PwmDecoder {
+    static_assert(std::is_same<T, Float>::value || std::is_same<T, Complex>::value, "PwmDecoder: Float (power) or Complex samples");
+    detail::Handle h_;
+    static rr_block* make(const PwmDecoderBuilder& b) {
+        // Some(0) cannot cross the C ABI (0 is None): validate()'s own refusal (:133-137)
+        if (b.fixed_ && b.frame_bits_ == 0) throw Error("PwmDecoder fixed frame length must be greater than zero");
+        return rr_pwm_decoder_create(b.high_, b.low_, b.short_, b.long_, b.tol_, b.fgap_, b.rgap_, b.fixed_ ? b.frame_bits_ : 0, b.max_frame_bits_,
+                                     b.max_distinct_, b.min_repeats_,
+                                     (b.short_is_one_ ? 0 : RR_PWM_SHORT_IS_ZERO) | (b.gap_pulse_ == PwmGapPulse::Delimiter ? RR_PWM_GAP_DELIMITER : 0),
+                                     sizeof(T));
+    }
+    std::vector<PwmFrame> fetch() {
+        size_t n = 0, nb = 0;
+        if (rr_pwm_frames(h_.h, nullptr, 0, &n) != 0) throw Error(rr_last_error());
+        std::vector<rr_pwm_frame> rec(n + 1);
+        if (n && rr_pwm_frames(h_.h, rec.data(), n, &n) != 0) throw Error(rr_last_error());
+        if (rr_pwm_frame_bits(h_.h, nullptr, 0, &nb) != 0) throw Error(rr_last_error());
+        std::vector<uint8_t> arena(nb + 1);
+        if (n && nb && rr_pwm_frame_bits(h_.h, arena.data(), nb, &nb) != 0) throw Error(rr_last_error());
+        std::vector<PwmFrame> out(n);
+        for (size_t i = 0; i < n; i++) {
+            if (rec[i].start > nb || rec[i].len > nb - rec[i].start) throw Error("PwmDecoder: frame outside the arena");
+            out[i].bits_.assign(arena.begin() + (long)rec[i].start, arena.begin() + (long)(rec[i].start + rec[i].len));
+            out[i].repeats_ = rec[i].repeats;
+            out[i].first_sample_ = rec[i].first_sample;
+        }
+        return out;
+    }
+public:
+    static PwmDecoderBuilder builder(float high_threshold, size_t short_width, size_t long_width, size_t frame_gap, size_t reset_gap) {
+        return PwmDecoderBuilder(high_threshold, short_width, long_width, frame_gap, reset_gap);
+    }
+    explicit PwmDecoder(const PwmDecoderBuilder& b) : h_(make(b)) {}
+    rr_block* handle() const { return h_.h; }
+    std::vector<PwmFrame> push(const std::vector<T>& samples) {
+        if (rr_pwm_decoder_push(h_.h, samples.data(), samples.size()) != 0) throw Error(rr_last_error());
+        return fetch();
+    }
+    std::vector<PwmFrame> finish() {
+        if (rr_pwm_decoder_flush(h_.h, nullptr) != 0) throw Error(rr_last_error());
+        return fetch();
+    }
+    size_t tile_samples() const {
+        size_t t = 0;
+        if (rr_pwm_decoder_dims(h_.h, &t) != 0) throw Error(rr_last_error());
+        return t;
+    }
+};
+
 // ---- SymbolSync (src/symbol_sync.rs:46-217) x nstreams: the window form of its streams ---------------------------------------------
 // (rr_symbol_sync_create / rr_symbol_sync_push / rr_symbol_sync_push_dev / rr_symbol_sync_produced).  push() takes the next samples
 // of every stream and returns what the block's dst (and out_clock(), when asked for) receive for them; each stream's clock state
