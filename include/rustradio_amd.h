@@ -181,6 +181,10 @@ int rr_fft_process(rr_block *fftstream, const rr_c32 *msg, size_t n, rr_c32 *out
 rr_block *rr_multiply_const_f32_create(float val);
 rr_block *rr_multiply_const_c32_create(float re, float im);
 rr_block *rr_fastfm_create(void);
+/* AddConst::<Float|Complex>::new(src, val) (src/add_const.rs:51-68): a #[rustradio(sync)] block like MultiplyConst, same
+ * protocol, tags kept; out = in + val, one f32 add per component.  Bit-exact. */
+rr_block *rr_add_const_f32_create(float val);
+rr_block *rr_add_const_c32_create(float re, float im);
 /* Hilbert::new(src, ntaps, &window_type) (src/hilbert.rs:38-61); ntaps odd > 1. */
 rr_block *rr_hilbert_create(size_t ntaps, int window, float window_parm);
 /* Vco::new(src, k) (src/vco.rs:9-37): Float in, Complex out.  Per sample a: phase += k * a in f64, one wrap by 2 pi when the
@@ -725,6 +729,43 @@ const void *rr_pwm_bits_dev(rr_block *b, size_t *n_total);
 /* *tile_samples = the samples of one tile of the slicer kernels; tile t of a push begins at its sample t * tile_samples.  The two
  * one-workgroup scans take 1024 tiles in one go. */
 int rr_pwm_decoder_dims(const rr_block *b, size_t *tile_samples);
+
+/* The tone demodulator of the 1200-baud AFSK receivers (examples/ax25-1200-rx.rs:238-247, il2p-1200-rx.rs:81-89),
+ *   Hilbert::new(_, hilbert_ntaps, window) -> QuadratureDemod::new(_, gain) -> FftFilterFloat::new(_, taps) -> AddConst::new(_, offset)
+ * x nstreams behind one handle, between the audio of rr_fm_multi / rr_fm_receiver and rr_symbol_sync, with the samples and every
+ * stream's state staying on the device.  A batch block like rr_symbol_sync: rr_block_work on the handle is an error.
+ * DEFINITION, per stream (x = every sample pushed so far, H = hilbert_ntaps, L = ntaps, hil = hilbert_taps(make_window(window, H, parm))):
+ *   xp     = H zeros ++ x
+ *   a[m]   = (xp[m + H/2], sum_j hil[H-1-j] xp[m + j])        j = 0 .. H-1
+ *   d[m]   = gain * atan2(Im, Re) of a[m+1] conj(a[m])        d[<0] = 0
+ *   out[i] = (sum_j taps[j] d[i - j]) + offset                one f32 add, last
+ * After T samples in all a stream has delivered exactly max(T - 1, 0) outputs, the reference's whole-stream count.  The bits of
+ * out do not depend on how the stream was cut into pushes, on where a tile starts or on what the other streams hold: every output
+ * is one fixed sequence of f32 operations (afsk_core.hpp), and stream c of an N-stream handle equals a 1-stream handle fed row c.
+ * Against the float64 form of the definition the error is within sum_j |taps[j]| b[i-j] + 1e-5 max|y|, b the bound of an angle
+ * whose two samples are 1e-5 max|a| off (tests/afsk_model.py).
+ * ONE launch per push whatever nstreams and n are: the low-pass is a direct sum (L multiply-adds per output), not the reference's
+ * overlap-save transform.  A handle carries the latest L + H samples of every stream on the device (rr_afsk_demod_dims).
+ * DEVIATIONS: the reference's FftFilterFloat withholds a partial block and never flushes it; this delivers every output whose
+ * inputs exist (same values, a later tail).  A NaN at x[k] makes exactly outputs k .. k + H + L - 1 NaN and touches no other bit
+ * (the reference poisons whole transform blocks, a superset); after +-Inf the set is not pinned.
+ * NULL + rr_last_error, said before any device is touched: "nstreams out of range" (0 or above 4096), "hilbert filter len must be
+ * odd and greater than 1" (hilbert.rs:48), "hilbert filter len above 1023", "unknown window, or a non-finite window parameter",
+ * "AfskDemod needs 1 to 4096 finite taps" (refused beyond, never clamped), "gain and offset must be finite". */
+rr_block *rr_afsk_demod_create(size_t nstreams, size_t hilbert_ntaps, int window, float window_parm, float gain,
+                               const float *taps, size_t ntaps, float offset);
+/* stream c: its next n samples at d_in + c*in_stride, its *produced outputs at d_out + c*out_stride (f32 elements): the layout
+ * rr_fm_multi_create writes and rr_symbol_sync_push_dev reads.  *produced (may be NULL) depends on lengths only, is the same for
+ * every stream and is written before the call returns: n, or n - 1 for the push that starts the streams; it is the n of the
+ * following rr_symbol_sync_push_dev.  Nothing at or beyond a stream's count is written.  RR_ERR before any device is touched: a
+ * stride below n, nstreams * n above 2^30, a null buffer with n > 0.  n == 0 launches nothing and leaves every state alone.
+ * Asynchronous on hip_stream. */
+int rr_afsk_demod_push_dev(rr_block *b, const void *d_in, size_t in_stride, size_t n,
+                           void *d_out, size_t out_stride, size_t *produced, void *hip_stream);
+/* The same with host pointers: copies the samples down, runs, waits and copies each stream's outputs back. */
+int rr_afsk_demod_push(rr_block *b, const float *in, size_t in_stride, size_t n, float *out, size_t out_stride, size_t *produced);
+/* *tile_samples = outputs of one workgroup (2048), *carry_samples = samples of a stream a handle carries (L + H) */
+int rr_afsk_demod_dims(const rr_block *b, size_t *tile_samples, size_t *carry_samples);
 
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)

@@ -159,6 +159,23 @@ unsafe extern "C" {
     fn rr_pwm_bits_dev(b: *mut RrBlock, n_total: *mut usize) -> *const c_void;
     #[allow(dead_code)]
     fn rr_pwm_decoder_dims(b: *const RrBlock, tile_samples: *mut usize) -> c_int;
+    // (declared for completeness: AddConst is a sync block like MultiplyConst and fits GpuMap; the N-stream tone demodulator belongs
+    //  with the N-channel blocks; neither typed block is written yet)
+    #[allow(dead_code)]
+    fn rr_add_const_f32_create(val: f32) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_add_const_c32_create(re: f32, im: f32) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_afsk_demod_create(nstreams: usize, hilbert_ntaps: usize, window: c_int, window_parm: f32, gain: f32, taps: *const f32,
+                            ntaps: usize, offset: f32) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_afsk_demod_push_dev(b: *mut RrBlock, d_in: *const c_void, in_stride: usize, n: usize, d_out: *mut c_void, out_stride: usize,
+                              produced: *mut usize, hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_afsk_demod_push(b: *mut RrBlock, input: *const f32, in_stride: usize, n: usize, out: *mut f32, out_stride: usize,
+                          produced: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_afsk_demod_dims(b: *const RrBlock, tile_samples: *mut usize, carry_samples: *mut usize) -> c_int;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;

@@ -16,6 +16,8 @@ what the reference would pass to `consume()`/`produce()`.
     Wpcr                 src/wpcr.rs:84-239      (message form: a batch of bursts per call)
     StreamToPdu          src/burst_tagger.rs:68-85, src/stream_to_pdu.rs:198-275, src/wpcr.rs:44-82 (BurstTagger -> StreamToPdu -> Midpointer)
     SymbolSync           src/symbol_sync.rs:46-217, src/iir_filter.rs:104-125   (N streams per handle, a window of each per call)
+    AddConst             src/add_const.rs:51-68
+    AfskDemod            Hilbert -> QuadratureDemod -> FftFilterFloat -> AddConst, examples/ax25-1200-rx.rs:238-247 (N streams per handle)
     low_pass / low_pass_complex / hilbert_taps / make_window   src/fir.rs:594-680, src/window.rs
 
 All sample arithmetic runs in HIP kernels on the GPU; nothing here computes samples.
@@ -485,6 +487,14 @@ def MultiplyConst(val, dtype=np.float32) -> Block:
         v = complex(val)
         return Block(lib().rr_multiply_const_c32_create(v.real, v.imag), np.complex64, np.complex64)
     return Block(lib().rr_multiply_const_f32_create(float(val)), np.float32, np.float32)
+
+
+def AddConst(val, dtype=np.float32) -> Block:
+    """AddConst::new(src, val) (src/add_const.rs:51-68), Float or Complex: one f32 add per component, bit-exact."""
+    if np.dtype(dtype) == np.complex64:
+        v = complex(val)
+        return Block(lib().rr_add_const_c32_create(v.real, v.imag), np.complex64, np.complex64)
+    return Block(lib().rr_add_const_f32_create(float(val)), np.float32, np.float32)
 
 
 def FastFM() -> Block:
@@ -1043,6 +1053,49 @@ class SymbolSync(Block):
             raise ValueError(last_error())
         return {"clock": four[0], "stream_pos": four[1], "last_sym_boundary_pos": four[2], "next_sym_middle": four[3],
                 "last_sign": bool(sign.value), "hist": hist[:nh.value].copy()}
+
+
+class AfskDemod(Block):
+    """Hilbert(hilbert_ntaps, window) -> QuadratureDemod(gain) -> FftFilterFloat(taps) -> AddConst(offset) x nstreams behind one
+    handle (rr_afsk_demod_create; examples/ax25-1200-rx.rs:238-247; not a stream block: work() raises): the next n samples of
+    each stream in, the soft samples they complete out — n of each, n - 1 for the push that starts the streams.  The bits do not
+    depend on how a stream is cut into pushes.  Every stream's latest samples stay on the device.  See include/rustradio_amd.h."""
+
+    def __init__(self, nstreams: int, hilbert_ntaps: int, taps, gain: float = 1.0, offset: float = 0.0,
+                 window: int = WIN_HAMMING, window_parm: float = 0.0):
+        t = np.ascontiguousarray(taps, np.float32).ravel()
+        super().__init__(lib().rr_afsk_demod_create(int(nstreams), int(hilbert_ntaps), int(window), float(window_parm), float(gain),
+                                                    _ptr(t) if len(t) else None, len(t), float(offset)), np.float32, np.float32)
+        self.nstreams, self.ntaps, self.hilbert_ntaps = int(nstreams), len(t), int(hilbert_ntaps)
+
+    def dims(self):
+        """-> (tile_samples, carry_samples) (rr_afsk_demod_dims)"""
+        t, c = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_afsk_demod_dims(self._h, C.byref(t), C.byref(c)) != 0:
+            raise RuntimeError(last_error())
+        return t.value, c.value
+
+    def push_dev(self, d_in: int, in_stride: int, n: int, d_out: int, out_stride: int, stream: int = 0) -> int:
+        """rr_afsk_demod_push_dev: stream c's next n samples at d_in + c * in_stride (raw device pointers, f32 elements), its
+        outputs to d_out + c * out_stride; asynchronous on `stream` -> produced, the n of the following SymbolSync.push_dev"""
+        k = C.c_size_t(0)
+        if lib().rr_afsk_demod_push_dev(self._h, C.c_void_p(d_in), int(in_stride), int(n), C.c_void_p(d_out), int(out_stride),
+                                        C.byref(k), C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+        return k.value
+
+    def push(self, x) -> np.ndarray:
+        """rr_afsk_demod_push on a host array of shape (nstreams, n) (or (n,) for one stream) -> float32 (nstreams, produced)"""
+        a = np.ascontiguousarray(x, np.float32)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        if a.ndim != 2 or a.shape[0] != self.nstreams:
+            raise ValueError("AfskDemod.push: one row per stream")
+        n = a.shape[1]
+        out = np.zeros((self.nstreams, max(n, 1)), np.float32)
+        k = C.c_size_t(0)
+        if lib().rr_afsk_demod_push(self._h, _ptr(a) if n else None, n, n, _ptr(out) if n else None, n, C.byref(k)) != 0:
+            raise ValueError(last_error())
+        return out[:, :k.value].copy()
 
 
 WPCR_MAX_LEN = 512_000     # samples of one burst: the reference's stream capacity in f32

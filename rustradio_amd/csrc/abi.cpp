@@ -82,7 +82,7 @@ template <class T> static T* as(const rr_block* b, const char* what, const char*
     return p;
 }
 static const char NOT_WPCR[] = "not a wpcr handle", NOT_PDU[] = "not a stream_to_pdu handle", NOT_FRAMER[] = "not an hdlc framer handle";
-static const char NOT_DEFRAMER[] = "not an hdlc deframer handle", NOT_SYNC[] = "not a symbol sync handle";
+static const char NOT_DEFRAMER[] = "not an hdlc deframer handle", NOT_SYNC[] = "not a symbol sync handle", NOT_AFSK[] = "not an afsk demod handle";
 static const char NOT_RECEIVER[] = "not an hdlc receiver handle", NOT_PWM[] = "not a pwm decoder handle";
 // a fetched list of (pos << shift) | val entries into the caller's two arrays
 template <class E> static void unpack(const std::vector<E>& e, unsigned shift, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
@@ -213,6 +213,12 @@ rr_block* rr_multiply_const_f32_create(float val) {
 }
 rr_block* rr_multiply_const_c32_create(float re, float im) {
     return make_block([&] { return new rr::MultiplyConst(8, re, im); }, RR_TAGS_FORWARD, 1);
+}
+rr_block* rr_add_const_f32_create(float val) {
+    return make_block([&] { return new rr::AddConst(4, val, 0.0f); }, RR_TAGS_FORWARD, 1);
+}
+rr_block* rr_add_const_c32_create(float re, float im) {
+    return make_block([&] { return new rr::AddConst(8, re, im); }, RR_TAGS_FORWARD, 1);
 }
 rr_block* rr_fastfm_create(void) {
     return make_block([&] { return new rr::FastFM(); }, RR_TAGS_FORWARD, 1);
@@ -664,6 +670,39 @@ int rr_debug_symbol_sync_state(rr_block* b, size_t stream, float* four, int* las
         *nhist = nh;
         for (size_t i = 0; i < nh && i < cap; i++) hist[i] = s.hist[nh - 1 - i];       // (the device keeps it newest first)
     });
+}
+rr_block* rr_afsk_demod_create(size_t nstreams, size_t hilbert_ntaps, int window, float window_parm, float gain, const float* taps,
+                               size_t ntaps, float offset) {
+    if (const char* e = rr::afsk_check(nstreams, hilbert_ntaps, window, window_parm, gain, taps, ntaps, offset)) return refuse_create(e);
+    return make_block([&] { return new rr::AfskDemod(nstreams, hilbert_ntaps, window, window_parm, gain, taps, ntaps, offset); });
+}
+int rr_afsk_demod_push_dev(rr_block* b, const void* d_in, size_t in_stride, size_t n, void* d_out, size_t out_stride, size_t* produced,
+                           void* hip_stream) {
+    auto* y = as<rr::AfskDemod>(b, "rr_afsk_demod_push_dev", NOT_AFSK);
+    if (!y) return RR_ERR;
+    if (produced) *produced = 0;
+    if (const char* e = rr::afsk_check_push(y->nstreams, d_in, in_stride, n, d_out, out_stride)) { rr::set_last_error(e); return RR_ERR; }
+    return on_device(y, hip_stream, [&](hipStream_t s) {
+        const size_t k = y->push_dev(static_cast<const float*>(d_in), in_stride, n, static_cast<float*>(d_out), out_stride, s);
+        if (produced) *produced = k;
+    });
+}
+int rr_afsk_demod_push(rr_block* b, const float* in, size_t in_stride, size_t n, float* out, size_t out_stride, size_t* produced) {
+    auto* y = as<rr::AfskDemod>(b, "rr_afsk_demod_push", NOT_AFSK);
+    if (!y) return RR_ERR;
+    if (produced) *produced = 0;
+    if (const char* e = rr::afsk_check_push(y->nstreams, in, in_stride, n, out, out_stride)) { rr::set_last_error(e); return RR_ERR; }
+    return guarded([&] {
+        const size_t k = y->push_host(in, in_stride, n, out, out_stride);
+        if (produced) *produced = k;
+    });
+}
+int rr_afsk_demod_dims(const rr_block* b, size_t* tile_samples, size_t* carry_samples) {
+    auto* y = as<rr::AfskDemod>(b, "rr_afsk_demod_dims", NOT_AFSK);
+    if (!y || !tile_samples || !carry_samples) { if (y) rr::set_last_error("rr_afsk_demod_dims: null argument"); return RR_ERR; }
+    *tile_samples = (size_t)rr::AFSK_TILE;
+    *carry_samples = (size_t)y->g.C;
+    return 0;
 }
 rr_block* rr_rtlsdr_decode_create(void) {
     return make_block([&] { return new rr::RtlSdrDecode(); });

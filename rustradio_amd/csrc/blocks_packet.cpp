@@ -1,5 +1,5 @@
 // blocks_packet.cpp — host side of the packet-side blocks (blocks_packet.hpp): the sync blocks, the burst and bit blocks, and the
-// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver).  Citations are to the reference's src, as in blocks.cpp.
+// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver, AfskDemod).  Citations are to the reference's src, as in blocks.cpp.
 #include "blocks_packet.hpp"
 
 #include <algorithm>
@@ -12,6 +12,7 @@
 #include "hdlcrx_core.hpp"
 #include "pdu_host.hpp"
 #include "symsync_host.hpp"
+#include "taps.hpp"
 
 namespace rr {
 
@@ -42,6 +43,13 @@ MultiplyConst::MultiplyConst(size_t es, float re, float im) : SyncBlock("Multipl
 void MultiplyConst::run(const void* in, void* out, size_t n, hipStream_t s) {
     if (in_es == 4) launch_mulconst_f32(static_cast<const float*>(in), static_cast<float*>(out), (long)n, vr, s);
     else launch_mulconst_c32(static_cast<const cf*>(in), static_cast<cf*>(out), (long)n, vr, vi, s);
+}
+AddConst::AddConst(size_t es, float re, float im) : SyncBlock("AddConst", es, es), vr(re), vi(im) {
+    if (es != 4 && es != 8) throw Error("AddConst: Float or Complex only");
+}
+void AddConst::run(const void* in, void* out, size_t n, hipStream_t s) {
+    if (in_es == 4) launch_addconst_f32(static_cast<const float*>(in), static_cast<float*>(out), (long)n, vr, s);
+    else launch_addconst_c32(static_cast<const cf*>(in), static_cast<cf*>(out), (long)n, vr, vi, s);
 }
 FastFM::FastFM() : SyncBlock("FastFM", 8, 4) {
     hist.zero(2, stream);
@@ -929,6 +937,56 @@ std::vector<unsigned long long> HdlcReceiver::positions(const unsigned long long
     stage_download_sync(b.data(), d_bst, b.size() * sizeof(unsigned long long), stream);
     for (size_t c = 0; c < out.size(); c++) out[c] = b[c * RX_ST_N + RX_ST_POS];
     return out;
+}
+
+// ---- AfskDemod (hilbert.rs:38-61, quadrature_demod.rs:65-109, fft_filter.rs:365-491, add_const.rs:51-68; kernels_afsk.hip) ---------------
+AfskDemod::AfskDemod(size_t ns, size_t hilbert_ntaps, int window, float window_parm, float gn, const float* taps, size_t ntaps, float off)
+    : BatchBlock("Hilbert>QuadratureDemod>FftFilterFloat>AddConst", 4, 4,
+                 "AfskDemod runs nstreams streams: rr_afsk_demod_push / rr_afsk_demod_push_dev"),
+      nstreams(ns), gain(gn), offset(off) {
+    if (const char* e = afsk_check(ns, hilbert_ntaps, window, window_parm, gn, taps, ntaps, off)) throw Error(e);
+    std::vector<float> win, hil;
+    if (!make_window(window, window_parm, hilbert_ntaps, win) || !hilbert_taps(win.data(), hilbert_ntaps, hil))
+        throw Error("hilbert filter len must be odd and greater than 1");
+    g = afsk_geom((int)hilbert_ntaps, (int)ntaps);
+    const std::vector<float> hr = afsk_reversed(hil);
+    d_hr.upload(hr.data(), hr.size(), stream);
+    d_taps.upload(taps, ntaps, stream);
+    carry.zero(ns * (size_t)g.C, stream);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+size_t AfskDemod::push_dev(const float* d_in, size_t in_stride, size_t n, float* d_out, size_t out_stride, hipStream_t s) {
+    if (const char* e = afsk_check_push(nstreams, d_in, in_stride, n, d_out, out_stride)) throw Error(e);
+    if (!n) return 0;                          // a push of no samples launches nothing and leaves every state alone
+    AfskArgs a{};
+    a.g = g;
+    a.in = d_in; a.in_stride = (long)in_stride;
+    a.out = d_out; a.out_stride = (long)out_stride;
+    a.carry_in = carry.in(); a.carry_out = carry.out();
+    a.taps = d_taps.p; a.hr = d_hr.p;
+    a.gain = gain; a.offset = offset;
+    afsk_plan(a, total, (long)n);
+    prof_begin(s);
+    launch_afsk(a, (long)nstreams, s);
+    prof_end(s);
+    carry.flip();
+    total += n;
+    return (size_t)a.produced;
+}
+size_t AfskDemod::push_host(const float* in, size_t in_stride, size_t n, float* out, size_t out_stride) {
+    size_t produced = 0;
+    host_call([&] {
+        if (const char* e = afsk_check_push(nstreams, in, in_stride, n, out, out_stride)) throw Error(e);
+        if (!n) return;
+        const size_t span = afsk_span(nstreams, in_stride, n);
+        h_in.reserve(span);
+        h_out.reserve(nstreams * n);
+        hstage().h2d(h_in.p, in, span * sizeof(float), stream);
+        produced = push_dev(h_in.p, in_stride, n, h_out.p, n, stream);
+        for (size_t c = 0; c < nstreams && produced; c++)
+            hstage().d2h(out + c * out_stride, h_out.p + c * n, produced * sizeof(float), stream);
+    });
+    return produced;
 }
 
 }  // namespace rr

@@ -3,6 +3,7 @@
 #include "blocks.hpp"
 #include "hdlcrx_host.hpp"
 #include "pwm_host.hpp"
+#include "afsk_host.hpp"
 
 namespace rr {
 
@@ -47,6 +48,11 @@ protected:
 struct MultiplyConst : SyncBlock {        // multiply_const.rs:6-23, T = Float (es 4) or Complex (es 8)
     float vr, vi;
     MultiplyConst(size_t es, float re, float im);
+    void run(const void* in, void* out, size_t n, hipStream_t s) override;
+};
+struct AddConst : SyncBlock {             // add_const.rs:51-68, T = Float (es 4) or Complex (es 8): one f32 add per component
+    float vr, vi;
+    AddConst(size_t es, float re, float im);
     void run(const void* in, void* out, size_t n, hipStream_t s) override;
 };
 struct FastFM : SyncBlock {           // quadrature_demod.rs:144-165; q2, q1 = the two previous samples (zeros at start)
@@ -388,6 +394,23 @@ struct HdlcReceiver : BatchBlock {
     std::vector<unsigned long long> fetch_stats();            // 3 per stream
     std::vector<unsigned long long> fetch_consumed();         // 1 per stream
     std::vector<unsigned long long> positions(const unsigned long long* d_bst) const;    // RX_ST_POS of every stream, one download
+};
+
+// Hilbert -> QuadratureDemod -> FftFilterFloat -> AddConst x nstreams over windows of nstreams f32 streams (kernels_afsk.hip,
+// afsk_core.hpp): no stream protocol (work_dev is an error).  Each stream's latest L + H samples stay on the device between pushes;
+// the host keeps only how many samples the streams have taken, which is all a push's counts depend on.
+struct AfskDemod : BatchBlock {
+    size_t nstreams;
+    AfskGeom g{};
+    float gain, offset;
+    DevBuf<float> d_taps, d_hr;
+    Carried<float> carry;                         // in(): nstreams x C, the streams' latest samples (zeros before their start)
+    unsigned long long total = 0;                 // samples every stream has taken
+    DevBuf<float> h_in, h_out;                    // push_host(): the host buffers' device copies
+    AfskDemod(size_t nstreams, size_t hilbert_ntaps, int window, float window_parm, float gain, const float* taps, size_t ntaps,
+              float offset);
+    size_t push_dev(const float* d_in, size_t in_stride, size_t n, float* d_out, size_t out_stride, hipStream_t s);   // -> produced
+    size_t push_host(const float* in, size_t in_stride, size_t n, float* out, size_t out_stride);
 };
 
 }  // namespace rr

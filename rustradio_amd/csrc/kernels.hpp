@@ -5,6 +5,7 @@
 #include "nan_fix.hpp"
 #include "pwm_core.hpp"
 #include "symsync_core.hpp"
+#include "afsk_core.hpp"
 
 namespace rr {
 
@@ -217,6 +218,9 @@ void launch_resample(const void* in, void* out, size_t es, long r, const void* p
 void launch_quaddemod(const cf* in, float* out, long n_out, float gain, int mode, hipStream_t s);
 void launch_mulconst_f32(const float* in, float* out, long n, float v, hipStream_t s);
 void launch_mulconst_c32(const cf* in, cf* out, long n, float vr, float vi, hipStream_t s);
+// AddConst (add_const.rs:51-68): out[i] = in[i] + v, per component for Complex; bit-exact
+void launch_addconst_f32(const float* in, float* out, long n, float v, hipStream_t s);
+void launch_addconst_c32(const cf* in, cf* out, long n, float vr, float vi, hipStream_t s);
 // FastFM over src = (q2, q1) || window: n outputs
 void launch_fastfm(VSrc<cf> src, float* out, long n, hipStream_t s);
 // RtlSdrDecode: out[i] = ((in[2i] - 127) * 0.008, (in[2i+1] - 127) * 0.008)
@@ -548,6 +552,12 @@ struct SyncArgs {
     int spw;
 };
 void launch_sync(const SyncArgs& a, int which, hipStream_t s);
+
+// ---- kernels_afsk.hip: Hilbert -> QuadratureDemod -> FftFilterFloat (direct form) -> AddConst over the next a.n samples of
+//      nstreams independent streams (afsk_core.hpp holds AfskArgs, the arithmetic and the indexing).  ONE launch whatever nstreams
+//      and n are (none for n == 0): grid (tiles of AFSK_TILE outputs, at least one; nstreams).  a.carry_in and a.carry_out are
+//      distinct; a.taps and a.hr are device pointers.
+void launch_afsk(const AfskArgs& a, long nstreams, hipStream_t s);
 
 // ---- kernels_pwm.hip: [ComplexToMag2 ->] PwmDecoder (pwm_decoder.rs:385-513) over the next n samples of a stream (pwm_core.hpp
 //      holds the arithmetic) -----------------------------------------------------------------------------------------------------------

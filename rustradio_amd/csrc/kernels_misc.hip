@@ -150,6 +150,27 @@ void launch_mulconst_c32(const cf* in, cf* out, long n, float vr, float vi, hipS
     hipLaunchKernelGGL(k_mulconst_c32, dim3(grid_for(n, 256)), dim3(256), 0, s, in, out, n, vr, vi);
     RR_HIP(hipGetLastError());
 }
+// ---- AddConst (src/add_const.rs:51-68): one f32 add per component, bit-exact ------------------------------------------------------
+__global__ __launch_bounds__(256) void k_addconst_f32(const float* __restrict__ in, float* __restrict__ out, long n, float v) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        out[i] = add_rn(in[i], v);
+}
+__global__ __launch_bounds__(256) void k_addconst_c32(const cf* __restrict__ in, cf* __restrict__ out, long n, float vr, float vi) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const cf a = in[i];
+        out[i] = mkcf(add_rn(a.x, vr), add_rn(a.y, vi));
+    }
+}
+void launch_addconst_f32(const float* in, float* out, long n, float v, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_addconst_f32, dim3(grid_for(n, 256)), dim3(256), 0, s, in, out, n, v);
+    RR_HIP(hipGetLastError());
+}
+void launch_addconst_c32(const cf* in, cf* out, long n, float vr, float vi, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_addconst_c32, dim3(grid_for(n, 256)), dim3(256), 0, s, in, out, n, vr, vi);
+    RR_HIP(hipGetLastError());
+}
 // out[n] = (s[n].im - s[n-2].im) * s[n-1].re - (s[n].re - s[n-2].re) * s[n-1].im over the virtual stream
 // src = (q2, q1) || window: the sequential q1/q2 update of the reference is just a 2-sample history.
 __global__ __launch_bounds__(256) void k_fastfm(VSrc<cf> src, float* __restrict__ out, long n) {

@@ -1152,6 +1152,47 @@ public:
     }
 };
 
+// ---- AfskDemod: Hilbert -> QuadratureDemod -> FftFilterFloat -> AddConst (examples/ax25-1200-rx.rs:238-247) x nstreams ------------
+// (rr_afsk_demod_create / rr_afsk_demod_push / rr_afsk_demod_push_dev / rr_afsk_demod_dims).  push() takes the next samples of
+// every stream and returns the soft samples they complete: one fewer than pushed for the push that starts the streams, as many
+// as pushed after it.  Each stream's latest samples stay in the block from push to push.
+class AfskDemod {
+    detail::Handle h_;
+    size_t nstreams_;
+public:
+    AfskDemod(size_t nstreams, size_t hilbert_ntaps, int window, float window_parm, float gain, const std::vector<float>& taps,
+              float offset)
+        : h_(rr_afsk_demod_create(nstreams, hilbert_ntaps, window, window_parm, gain, taps.data(), taps.size(), offset)),
+          nstreams_(nstreams) {}
+    rr_block* handle() const { return h_.h; }
+    size_t nstreams() const { return nstreams_; }
+    // rows[c] = the next samples of stream c, all of one length -> the outputs of stream c, all of one length
+    std::vector<std::vector<float>> push(const std::vector<std::vector<float>>& rows) {
+        if (rows.size() != nstreams_) throw Error("AfskDemod: one row per stream");
+        const size_t n = rows.empty() ? 0 : rows[0].size();
+        std::vector<float> in(nstreams_ * n + 1), out(nstreams_ * n + 1);
+        for (size_t c = 0; c < nstreams_; c++) {
+            if (rows[c].size() != n) throw Error("AfskDemod: rows of one length");
+            std::copy(rows[c].begin(), rows[c].end(), in.begin() + (long)(c * n));
+        }
+        size_t produced = 0;
+        if (rr_afsk_demod_push(h_.h, in.data(), n, n, out.data(), n, &produced) != 0) throw Error(rr_last_error());
+        produced = std::min(produced, n);
+        std::vector<std::vector<float>> res(nstreams_);
+        for (size_t c = 0; c < nstreams_; c++) res[c].assign(out.begin() + (long)(c * n), out.begin() + (long)(c * n + produced));
+        return res;
+    }
+    // device windows in the layout of rr_fm_multi_create's output; asynchronous on hip_stream -> produced, the n of the
+    // following SymbolSync::push_dev
+    size_t push_dev(const void* d_in, size_t in_stride, size_t n, void* d_out, size_t out_stride, void* hip_stream = nullptr) {
+        size_t produced = 0;
+        if (rr_afsk_demod_push_dev(h_.h, d_in, in_stride, n, d_out, out_stride, &produced, hip_stream) != 0) throw Error(rr_last_error());
+        return produced;
+    }
+    size_t tile_samples() const { size_t t = 0, c = 0; if (rr_afsk_demod_dims(h_.h, &t, &c) != 0) throw Error(rr_last_error()); return t; }
+    size_t carry_samples() const { size_t t = 0, c = 0; if (rr_afsk_demod_dims(h_.h, &t, &c) != 0) throw Error(rr_last_error()); return c; }
+};
+
 // ---- #[rustradio(sync)] blocks: MultiplyConst (src/multiply_const.rs), FastFM (src/quadrature_demod.rs:144-165) ----------
 // work() per rustradio_macros_code/src/lib.rs:458-515; a tag at position pos < n passes through at pos.
 template <class In, class Out> class SyncBlock : public Block {
@@ -1184,6 +1225,19 @@ public:
     static std::pair<std::unique_ptr<MultiplyConst<T>>, ReadStream<T>> new_(ReadStream<T> src, T val) {
         auto [w, r] = new_stream<T>();
         return {std::make_unique<MultiplyConst<T>>(make(val), std::move(src), std::move(w)), std::move(r)};
+    }
+};
+// AddConst (src/add_const.rs:51-68): out = in + val, one f32 add per component
+template <class T> class AddConst : public SyncBlock<T, T> {
+    static rr_block* make(T val) {
+        if constexpr (std::is_same<T, Complex>::value) return rr_add_const_c32_create(val.real(), val.imag());
+        else return rr_add_const_f32_create(val);
+    }
+public:
+    using SyncBlock<T, T>::SyncBlock;
+    static std::pair<std::unique_ptr<AddConst<T>>, ReadStream<T>> new_(ReadStream<T> src, T val) {
+        auto [w, r] = new_stream<T>();
+        return {std::make_unique<AddConst<T>>(make(val), std::move(src), std::move(w)), std::move(r)};
     }
 };
 class FastFM : public SyncBlock<Complex, Float> {
