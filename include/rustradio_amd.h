@@ -767,6 +767,47 @@ int rr_afsk_demod_push(rr_block *b, const float *in, size_t in_stride, size_t n,
 /* *tile_samples = outputs of one workgroup (2048), *carry_samples = samples of a stream a handle carries (L + H) */
 int rr_afsk_demod_dims(const rr_block *b, size_t *tile_samples, size_t *carry_samples);
 
+/* The modulators of the reference's two packet transmitters, line bits in, baseband out, in PDU form (rr_block_work on the handle
+ * is an error).  Bits are u8 as rr_hdlc_framer_push_dev writes them without RR_FRAME_SYMBOLS; a byte is 1 when it is nonzero (the
+ * reference's `s > 0`).  Both ratios are gcd-reduced; a RationalResampler is out[m] = in[floor(m D / I)] and has made ceil(N I / D)
+ * outputs after N inputs (src/rational_resampler.rs:183-198).
+ *   RR_FSK_TX_AFSK    examples/bell202.rs:166-183 behind its NrziEncode: RationalResampler(interp1, deci1) -> Map(bit > 0 ? hi : lo)
+ *                     -> Vco(k1) -> Map(.re) -> MultiplyConst(gain) -> RationalResampler(interp2, deci2) -> Vco(k2)
+ *                       a[m]   = fl32(fl32(sin p1[m]) * gain), p1 the f64 phase of Vco(k1) over level[m] = bit[floor(m D1 / I1)] ? hi : lo
+ *                       out[o] = (sin p2, cos p2), p2 += k2 * a[floor(o D2 / I2)] once per OUTPUT sample (src/vco.rs:9-37)
+ *   RR_FSK_TX_DIRECT  examples/g3ruh.rs:256-272 behind its NrziEncode and in front of its FftFilter: RationalResampler -> Map ->
+ *                     Vco(k1) -> MultiplyConst(gain) -> RationalResampler
+ *                       out[o] = gain * (sin, cos)(p1[floor(o D2 / I2)]); k2_bits is ignored
+ * A push of n bits behind N0 earlier ones makes the audio samples [A(N0), A(N0 + n)), A(N) = ceil(N I1 / D1), and the outputs
+ * [O(A(N0)), O(A(N0 + n))), O(A) = ceil(A I2 / D2): everything its bits produce, no run split across pushes.  Both phases stay
+ * on the device; counts depend on lengths only.  Every scan runs at the audio rate and the output-rate kernel is a map (kernels_tx.hip
+ * has the launch counts).  Accuracy, against the exact phase in long double (tests/tx_model.py), sample indices
+ * from the stream's start: audio and DIRECT components within |gain| (2^-24 + (m + 1)(2^-48 + d1 2^-52)), d1 = max |k1 level|; AFSK
+ * components within 2^-25 + (o + 1)(2^-48 + d2 2^-52), d2 = |k2| max |a|, of the truth computed from the a[] the same push wrote.
+ * Different splits into pushes are each within the bound, not bit-identical; the same pushes twice give the same bits.
+ * NULL + rr_last_error, said before any device is touched: "fsk tx: unknown mode", "interpolation and decimation must be nonzero"
+ * (the reference's Err), "fsk tx: reduced ratio part above 2^31", "fsk tx: lo and hi must be finite", "fsk tx: gain must be
+ * finite", "fsk tx: k1 and k2 must be finite". */
+enum { RR_FSK_TX_DIRECT = 0, RR_FSK_TX_AFSK = 1 };
+rr_block *rr_fsk_tx_create(int mode, size_t interp1, size_t deci1, float lo, float hi, unsigned long long k1_bits, float gain,
+                           size_t interp2, size_t deci2, unsigned long long k2_bits);
+/* What the NEXT push of n_bits makes (either pointer may be NULL).  RR_ERR where that push would be refused for its length. */
+int rr_fsk_tx_count(const rr_block *b, size_t n_bits, size_t *n_audio, size_t *n_out);
+/* d_out: *n_out Complex (re = sin, im = cos); d_audio: f32, may be NULL, must be NULL in DIRECT mode, receives the *n_audio
+ * samples a[] (the sound-card signal of bell202.rs).  The counts (pointers may be NULL) are written before the call returns;
+ * nothing at or beyond them is written.  RR_ERR before any device is touched, each with its own sentence: a d_audio in DIRECT
+ * mode, more than 2^30 bits, audio samples or outputs in one push, an output position beyond 2^62, a null buffer on a push that
+ * needs it, out_cap or audio_cap below the counts.  n_bits == 0 launches nothing and leaves every state alone.  Asynchronous on
+ * hip_stream. */
+int rr_fsk_tx_push_dev(rr_block *b, const void *d_bits, size_t n_bits, void *d_out, size_t out_cap, void *d_audio, size_t audio_cap,
+                       size_t *n_out, size_t *n_audio, void *hip_stream);
+/* The same with host pointers: copies the bits down, runs, waits and copies the produced elements back. */
+int rr_fsk_tx_push(rr_block *b, const void *bits, size_t n_bits, rr_c32 *out, size_t out_cap, float *audio, size_t audio_cap,
+                   size_t *n_out, size_t *n_audio);
+/* *audio_tile = audio samples of one scan tile (2048), *out_tile = outputs of one workgroup of the map kernel (2048),
+ * *scan_chunk_tiles = audio tiles one pass of the tile-level scans takes (4096) */
+int rr_fsk_tx_dims(const rr_block *b, size_t *audio_tile, size_t *out_tile, size_t *scan_chunk_tiles);
+
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)
  * as wired in examples/ax25-1200-rx.rs:238-247: f32 in, Complex out, ONE decimating FIR with the composite

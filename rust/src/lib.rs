@@ -176,6 +176,22 @@ unsafe extern "C" {
                           produced: *mut usize) -> c_int;
     #[allow(dead_code)]
     fn rr_afsk_demod_dims(b: *const RrBlock, tile_samples: *mut usize, carry_samples: *mut usize) -> c_int;
+    // (declared for completeness: the PDU-form modulator of examples/bell202.rs:166-183 and g3ruh.rs:256-272 takes pushes of line
+    //  bits, not a stream; its typed block is not written yet)
+    #[allow(dead_code)]
+    fn rr_fsk_tx_create(mode: c_int, interp1: usize, deci1: usize, lo: f32, hi: f32, k1_bits: u64, gain: f32, interp2: usize,
+                        deci2: usize, k2_bits: u64) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_fsk_tx_count(b: *const RrBlock, n_bits: usize, n_audio: *mut usize, n_out: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_fsk_tx_push_dev(b: *mut RrBlock, d_bits: *const c_void, n_bits: usize, d_out: *mut c_void, out_cap: usize,
+                          d_audio: *mut c_void, audio_cap: usize, n_out: *mut usize, n_audio: *mut usize,
+                          hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_fsk_tx_push(b: *mut RrBlock, bits: *const c_void, n_bits: usize, out: *mut Complex, out_cap: usize, audio: *mut f32,
+                      audio_cap: usize, n_out: *mut usize, n_audio: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_fsk_tx_dims(b: *const RrBlock, audio_tile: *mut usize, out_tile: *mut usize, scan_chunk_tiles: *mut usize) -> c_int;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;

@@ -18,6 +18,7 @@ what the reference would pass to `consume()`/`produce()`.
     SymbolSync           src/symbol_sync.rs:46-217, src/iir_filter.rs:104-125   (N streams per handle, a window of each per call)
     AddConst             src/add_const.rs:51-68
     AfskDemod            Hilbert -> QuadratureDemod -> FftFilterFloat -> AddConst, examples/ax25-1200-rx.rs:238-247 (N streams per handle)
+    FskTx                line bits -> AFSK / FSK baseband, examples/bell202.rs:166-183, examples/g3ruh.rs:256-272 (a push of bits per call)
     low_pass / low_pass_complex / hilbert_taps / make_window   src/fir.rs:594-680, src/window.rs
 
 All sample arithmetic runs in HIP kernels on the GPU; nothing here computes samples.
@@ -1096,6 +1097,58 @@ class AfskDemod(Block):
         if lib().rr_afsk_demod_push(self._h, _ptr(a) if n else None, n, n, _ptr(out) if n else None, n, C.byref(k)) != 0:
             raise ValueError(last_error())
         return out[:, :k.value].copy()
+
+
+FSK_TX_DIRECT, FSK_TX_AFSK = 0, 1      # RR_FSK_TX_*
+
+
+class FskTx(Block):
+    """The modulators of the reference's packet transmitters in PDU form (rr_fsk_tx_create; not a stream block: work() raises):
+    u8 line bits in (HdlcFramer's, without FRAME_SYMBOLS; nonzero = 1), Complex baseband out.
+      FSK_TX_AFSK    RationalResampler(interp1, deci1) -> Map(bit ? hi : lo) -> Vco(k1) -> .re -> MultiplyConst(gain) ->
+                     RationalResampler(interp2, deci2) -> Vco(k2)          (examples/bell202.rs:166-183); the audio is an output too
+      FSK_TX_DIRECT  RationalResampler -> Map -> Vco(k1) -> MultiplyConst(gain) -> RationalResampler   (examples/g3ruh.rs:256-272)
+    Every push emits everything its bits produce; both phases stay on the device.  See include/rustradio_amd.h."""
+
+    def __init__(self, mode: int, interp1: int, deci1: int, lo: float, hi: float, k1: float, gain: float, interp2: int = 1,
+                 deci2: int = 1, k2: float = 0.0):
+        super().__init__(lib().rr_fsk_tx_create(int(mode), int(interp1), int(deci1), float(lo), float(hi), _f64_bits(float(k1)),
+                                                float(gain), int(interp2), int(deci2), _f64_bits(float(k2))), np.uint8, np.complex64)
+        self.mode = int(mode)
+
+    def dims(self):
+        """-> (audio_tile, out_tile, scan_chunk_tiles) (rr_fsk_tx_dims)"""
+        a, o, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_fsk_tx_dims(self._h, C.byref(a), C.byref(o), C.byref(c)) != 0:
+            raise RuntimeError(last_error())
+        return a.value, o.value, c.value
+
+    def count(self, n_bits: int):
+        """-> (n_audio, n_out) of the NEXT push of n_bits (rr_fsk_tx_count)"""
+        a, o = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_fsk_tx_count(self._h, int(n_bits), C.byref(a), C.byref(o)) != 0:
+            raise ValueError(last_error())
+        return a.value, o.value
+
+    def push_dev(self, d_bits: int, n_bits: int, d_out: int, out_cap: int, d_audio: int = 0, audio_cap: int = 0, stream: int = 0):
+        """rr_fsk_tx_push_dev on raw device pointers (d_audio 0: no audio output); asynchronous on `stream` -> (n_out, n_audio)"""
+        o, a = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_fsk_tx_push_dev(self._h, C.c_void_p(d_bits), int(n_bits), C.c_void_p(d_out), int(out_cap), C.c_void_p(d_audio),
+                                    int(audio_cap), C.byref(o), C.byref(a), C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+        return o.value, a.value
+
+    def push(self, bits, audio: bool = False):
+        """rr_fsk_tx_push on a host array of u8 bits -> complex64 out, or (out, float32 audio) with audio=True (AFSK mode)"""
+        b = np.ascontiguousarray(bits, np.uint8).ravel()
+        na, no = self.count(len(b))
+        out = np.zeros(max(no, 1), np.complex64)
+        aud = np.zeros(max(na, 1), np.float32) if audio else None
+        o, a = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_fsk_tx_push(self._h, _ptr(b) if len(b) else None, len(b), _ptr(out), no, _ptr(aud) if audio else None,
+                                na if audio else 0, C.byref(o), C.byref(a)) != 0:
+            raise ValueError(last_error())
+        return (out[:o.value].copy(), aud[:a.value].copy()) if audio else out[:o.value].copy()
 
 
 WPCR_MAX_LEN = 512_000     # samples of one burst: the reference's stream capacity in f32

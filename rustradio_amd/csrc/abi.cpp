@@ -84,6 +84,7 @@ template <class T> static T* as(const rr_block* b, const char* what, const char*
 static const char NOT_WPCR[] = "not a wpcr handle", NOT_PDU[] = "not a stream_to_pdu handle", NOT_FRAMER[] = "not an hdlc framer handle";
 static const char NOT_DEFRAMER[] = "not an hdlc deframer handle", NOT_SYNC[] = "not a symbol sync handle", NOT_AFSK[] = "not an afsk demod handle";
 static const char NOT_RECEIVER[] = "not an hdlc receiver handle", NOT_PWM[] = "not a pwm decoder handle";
+static const char NOT_FSK[] = "not an fsk tx handle";
 // a fetched list of (pos << shift) | val entries into the caller's two arrays
 template <class E> static void unpack(const std::vector<E>& e, unsigned shift, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
     *total = e.size();
@@ -702,6 +703,62 @@ int rr_afsk_demod_dims(const rr_block* b, size_t* tile_samples, size_t* carry_sa
     if (!y || !tile_samples || !carry_samples) { if (y) rr::set_last_error("rr_afsk_demod_dims: null argument"); return RR_ERR; }
     *tile_samples = (size_t)rr::AFSK_TILE;
     *carry_samples = (size_t)y->g.C;
+    return 0;
+}
+rr_block* rr_fsk_tx_create(int mode, size_t interp1, size_t deci1, float lo, float hi, unsigned long long k1_bits, float gain,
+                           size_t interp2, size_t deci2, unsigned long long k2_bits) {
+    const double k1 = f64_from_bits(k1_bits), k2 = f64_from_bits(k2_bits);
+    if (const char* e = rr::fsk_check(mode, interp1, deci1, lo, hi, k1, gain, interp2, deci2, k2)) return refuse_create(e);
+    return make_block([&] { return new rr::FskTx(mode, interp1, deci1, lo, hi, k1, gain, interp2, deci2, k2); });
+}
+int rr_fsk_tx_count(const rr_block* b, size_t n_bits, size_t* n_audio, size_t* n_out) {
+    auto* y = as<rr::FskTx>(b, "rr_fsk_tx_count", NOT_FSK);
+    if (!y) return RR_ERR;
+    return guarded([&] {
+        const rr::FskPush u = y->count(n_bits);
+        if (n_audio) *n_audio = (size_t)u.na;
+        if (n_out) *n_out = (size_t)u.no;
+    });
+}
+int rr_fsk_tx_push_dev(rr_block* b, const void* d_bits, size_t n_bits, void* d_out, size_t out_cap, void* d_audio, size_t audio_cap,
+                       size_t* n_out, size_t* n_audio, void* hip_stream) {
+    auto* y = as<rr::FskTx>(b, "rr_fsk_tx_push_dev", NOT_FSK);
+    if (!y) return RR_ERR;
+    if (n_out) *n_out = 0;
+    if (n_audio) *n_audio = 0;
+    if (const char* e = rr::fsk_check_push(y->mode, y->pos, y->r1, y->r2, d_bits, n_bits, d_out, out_cap, d_audio, audio_cap, nullptr)) {
+        rr::set_last_error(e);
+        return RR_ERR;
+    }
+    return on_device(y, hip_stream, [&](hipStream_t s) {
+        const rr::FskPush u = y->push_dev(static_cast<const unsigned char*>(d_bits), n_bits, static_cast<rr::cf*>(d_out), out_cap,
+                                          static_cast<float*>(d_audio), audio_cap, s);
+        if (n_out) *n_out = (size_t)u.no;
+        if (n_audio) *n_audio = (size_t)u.na;
+    });
+}
+int rr_fsk_tx_push(rr_block* b, const void* bits, size_t n_bits, rr_c32* out, size_t out_cap, float* audio, size_t audio_cap,
+                   size_t* n_out, size_t* n_audio) {
+    auto* y = as<rr::FskTx>(b, "rr_fsk_tx_push", NOT_FSK);
+    if (!y) return RR_ERR;
+    if (n_out) *n_out = 0;
+    if (n_audio) *n_audio = 0;
+    if (const char* e = rr::fsk_check_push(y->mode, y->pos, y->r1, y->r2, bits, n_bits, out, out_cap, audio, audio_cap, nullptr)) {
+        rr::set_last_error(e);
+        return RR_ERR;
+    }
+    return guarded([&] {
+        const rr::FskPush u = y->push_host(static_cast<const unsigned char*>(bits), n_bits, reinterpret_cast<rr::cf*>(out), out_cap, audio, audio_cap);
+        if (n_out) *n_out = (size_t)u.no;
+        if (n_audio) *n_audio = (size_t)u.na;
+    });
+}
+int rr_fsk_tx_dims(const rr_block* b, size_t* audio_tile, size_t* out_tile, size_t* scan_chunk_tiles) {
+    auto* y = as<rr::FskTx>(b, "rr_fsk_tx_dims", NOT_FSK);
+    if (!y || !audio_tile || !out_tile || !scan_chunk_tiles) { if (y) rr::set_last_error("rr_fsk_tx_dims: null argument"); return RR_ERR; }
+    *audio_tile = (size_t)rr::FSK_T;
+    *out_tile = (size_t)rr::FSK_OT;
+    *scan_chunk_tiles = (size_t)rr::FSK_SCAN_CHUNK;
     return 0;
 }
 rr_block* rr_rtlsdr_decode_create(void) {

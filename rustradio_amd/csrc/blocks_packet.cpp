@@ -1,5 +1,5 @@
 // blocks_packet.cpp — host side of the packet-side blocks (blocks_packet.hpp): the sync blocks, the burst and bit blocks, and the
-// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver, AfskDemod).  Citations are to the reference's src, as in blocks.cpp.
+// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver, AfskDemod, FskTx).  Citations are to the reference's src, as in blocks.cpp.
 #include "blocks_packet.hpp"
 
 #include <algorithm>
@@ -987,6 +987,74 @@ size_t AfskDemod::push_host(const float* in, size_t in_stride, size_t n, float* 
             hstage().d2h(out + c * out_stride, h_out.p + c * n, produced * sizeof(float), stream);
     });
     return produced;
+}
+
+// ---- FskTx (examples/bell202.rs:166-183, g3ruh.rs:256-272; rational_resampler.rs:183-198, vco.rs:9-37; kernels_tx.hip) ------------
+FskTx::FskTx(int md, size_t interp1, size_t deci1, float l, float h, double kk1, float g, size_t interp2, size_t deci2, double kk2)
+    : BatchBlock(md == FSK_AFSK ? "Resampler>Map>Vco>Re>MultiplyConst>Resampler>Vco" : "Resampler>Map>Vco>MultiplyConst>Resampler", 1, 8,
+                 "FskTx takes pushes of line bits: rr_fsk_tx_push / rr_fsk_tx_push_dev"),
+      mode(md), lo(l), hi(h), gain(g), k1(kk1), k2(md == FSK_AFSK ? kk2 : 0.0) {
+    if (const char* e = fsk_check(md, interp1, deci1, l, h, kk1, g, interp2, deci2, kk2)) throw Error(e);
+    r1 = fsk_ratio((long)interp1, (long)deci1);
+    r2 = fsk_ratio((long)interp2, (long)deci2);
+    phase.zero(2, stream);                           // phase: 0.0 (vco.rs:18), both
+    RR_HIP(hipStreamSynchronize(stream));
+}
+FskPush FskTx::count(size_t n_bits) const {
+    static const char some = 0;                      // (only the lengths are asked about)
+    FskPush u{};
+    if (const char* e = fsk_check_push(mode, pos, r1, r2, &some, n_bits, &some, (size_t)-1, nullptr, 0, &u)) throw Error(e);
+    return u;
+}
+FskPush FskTx::push_dev(const unsigned char* d_bits, size_t n_bits, cf* d_out, size_t out_cap, float* d_audio, size_t audio_cap,
+                        hipStream_t s) {
+    FskPush u{};
+    if (const char* e = fsk_check_push(mode, pos, r1, r2, d_bits, n_bits, d_out, out_cap, d_audio, audio_cap, &u)) throw Error(e);
+    if (!n_bits) return u;                           // an empty push launches nothing and leaves every state alone
+    if (u.na) {                                      // (bits that make no audio sample move the first resampler only)
+        const size_t na = (size_t)u.na, ntiles = (na + FSK_T - 1) / FSK_T;
+        FskTxArgs a{};
+        a.bits = d_bits;
+        a.n = u.n; a.na = u.na; a.no = u.no;
+        a.r1 = r1; a.r2 = r2; a.e1 = u.e1; a.e2 = u.e2;
+        a.map_dq = ((long)FSK_B * r2.D) / r2.I; a.map_dr = ((long)FSK_B * r2.D) % r2.I;
+        a.dhi = k1 * (double)hi; a.dlo = k1 * (double)lo; a.k2 = k2;
+        a.gain = gain;
+        a.carry_in = phase.in(); a.carry_out = phase.out();
+        tilecnt.reserve(ntiles);
+        a.tilecnt = tilecnt.p;
+        if (mode == FSK_AFSK) {
+            tiles2.reserve(ntiles);
+            pre2.reserve(na);
+            if (!d_audio) audio.reserve(na);
+            a.tiles2 = tiles2.p; a.pre2 = pre2.p; a.audio = d_audio ? d_audio : audio.p;
+        } else {
+            val.reserve(na);
+            a.val = val.p;
+        }
+        a.out = d_out;
+        prof_begin(s);
+        launch_fsk_tx(a, mode == FSK_AFSK, s);
+        prof_end(s);
+        phase.flip();
+    }
+    pos = u.next;
+    return u;
+}
+FskPush FskTx::push_host(const unsigned char* bits, size_t n_bits, cf* out, size_t out_cap, float* audio_out, size_t audio_cap) {
+    FskPush u{};
+    host_call([&] {
+        if (const char* e = fsk_check_push(mode, pos, r1, r2, bits, n_bits, out, out_cap, audio_out, audio_cap, &u)) throw Error(e);
+        if (!n_bits) return;
+        h_bits.reserve(n_bits);
+        h_out.reserve((size_t)u.no);
+        if (audio_out) h_audio.reserve((size_t)u.na);
+        hstage().h2d(h_bits.p, bits, n_bits, stream);
+        u = push_dev(h_bits.p, n_bits, h_out.p, (size_t)u.no, audio_out ? h_audio.p : nullptr, (size_t)u.na, stream);
+        if (u.no) hstage().d2h(out, h_out.p, (size_t)u.no * sizeof(cf), stream);
+        if (audio_out && u.na) hstage().d2h(audio_out, h_audio.p, (size_t)u.na * sizeof(float), stream);
+    });
+    return u;
 }
 
 }  // namespace rr

@@ -4,6 +4,7 @@
 #include "hdlcrx_host.hpp"
 #include "pwm_host.hpp"
 #include "afsk_host.hpp"
+#include "fsk_host.hpp"
 
 namespace rr {
 
@@ -411,6 +412,34 @@ struct AfskDemod : BatchBlock {
               float offset);
     size_t push_dev(const float* d_in, size_t in_stride, size_t n, float* d_out, size_t out_stride, hipStream_t s);   // -> produced
     size_t push_host(const float* in, size_t in_stride, size_t n, float* out, size_t out_stride);
+};
+
+// The modulators of the two packet transmitters over pushes of u8 line bits (kernels_tx.hip, fsk_core.hpp): no stream protocol
+// (work_dev is an error).
+//   AFSK    RationalResampler -> Map(bit > 0 ? hi : lo) -> Vco(k1) -> .re -> MultiplyConst(gain) -> RationalResampler -> Vco(k2)
+//           (examples/bell202.rs:166-183)
+//   DIRECT  RationalResampler -> Map -> Vco(k1) -> MultiplyConst(gain) -> RationalResampler (examples/g3ruh.rs:256-272)
+// The two phases stay on the device between pushes; the host keeps where the two resamplers stand (FskPos), which is all a push's
+// counts depend on.
+struct FskTx : BatchBlock {
+    int mode;
+    FskRatio r1, r2;
+    float lo, hi, gain;
+    double k1, k2;
+    FskPos pos;
+    Carried<double> phase;                        // in(): phase 1, phase 2 behind the previous push's last sample (0 at start)
+    DevBuf<unsigned> tilecnt;
+    DevBuf<double> tiles2, pre2;
+    DevBuf<float> audio;                          // a[] of a push that was given no d_audio
+    DevBuf<cf> val;
+    DevBuf<unsigned char> h_bits;                 // push_host(): the host buffers' device copies
+    DevBuf<cf> h_out;
+    DevBuf<float> h_audio;
+    FskTx(int mode, size_t interp1, size_t deci1, float lo, float hi, double k1, float gain, size_t interp2, size_t deci2, double k2);
+    FskPush count(size_t n_bits) const;           // the next push of n_bits; throws what that push would refuse for its length
+    FskPush push_dev(const unsigned char* d_bits, size_t n_bits, cf* d_out, size_t out_cap, float* d_audio, size_t audio_cap,
+                     hipStream_t s);
+    FskPush push_host(const unsigned char* bits, size_t n_bits, cf* out, size_t out_cap, float* audio, size_t audio_cap);
 };
 
 }  // namespace rr

@@ -6,6 +6,7 @@
 #include "pwm_core.hpp"
 #include "symsync_core.hpp"
 #include "afsk_core.hpp"
+#include "fsk_core.hpp"
 
 namespace rr {
 
@@ -263,6 +264,30 @@ void launch_vco(const float* in, cf* out, long n, double k, const double* carry_
 // ... reading its samples through the resampler's index map (launch_resample's r, pending, n_gather, I, D, c0): n = r + n_gather
 void launch_fm_tx(const float* in, cf* out, long r, const float* pending, long n_gather, long I, long D, long c0, double k,
                   const double* carry_in, double* carry_out, double* tiles, hipStream_t s);
+
+// ---- kernels_tx.hip: rr_fsk_tx, line bits -> [Vco -> .re -> gain -> RationalResampler ->] Vco (examples/bell202.rs:166-183,
+//      g3ruh.rs:256-272).  One push of a.n bits that makes a.na audio samples and a.no outputs (fsk_core.hpp: fsk_plan), all
+//      indices relative to the push.  carry_in / carry_out: two device doubles each (phase 1, phase 2), distinct buffers.
+//      Scratch, sized by the caller: tilecnt and tiles2 one entry per audio tile of FSK_T; AFSK: audio (the caller's d_audio or
+//      scratch) and pre2, na entries; DIRECT: val, na entries.  Launches: the header of kernels_tx.hip.  na == 0 launches nothing.
+struct FskTxArgs {
+    const unsigned char* bits;
+    long n, na, no;
+    FskRatio r1, r2;
+    long e1, e2;
+    long map_dq, map_dr;                      // (FSK_B * D2) / I2 and % I2: what src2 moves by over FSK_B outputs
+    double dhi, dlo, k2;                      // k1 * hi, k1 * lo
+    float gain;
+    const double* carry_in;
+    double* carry_out;
+    unsigned* tilecnt;
+    double* tiles2;
+    float* audio;
+    double* pre2;
+    cf* val;
+    cf* out;
+};
+void launch_fsk_tx(const FskTxArgs& a, bool afsk, hipStream_t s);
 
 // ---- kernels_burst.hip: ComplexToMag2, SinglePoleIirFilter and the burst detector as a tiled f64 scan ------------------------
 // out[i] = (f32) y_i, y_i = a x_i + b y_(i-1) in f64 fma, y_(-1) = *y_in, i < n; *y_out <- y_(n-1).  y_in and y_out are distinct

@@ -14,6 +14,19 @@
 // addition costs at most half an ulp of 4 pi, as in the sequential form (DESIGN.md "Vco").  A non-finite sample makes its
 // own prefix sum and every later one NaN or +-Inf, whose sin and cos are NaN: the reference's behaviour with no pass for it.
 // Exclusive prefixes are built from the earlier elements only (never inclusive minus own), so the samples before stay clean.
+//
+// rr_fsk_tx (examples/bell202.rs:166-183, g3ruh.rs:256-272): both VCOs of the packet transmitters with every scan
+// at the AUDIO rate.  Stage 1 has two levels, so its phase at audio sample m is k1 hi c1 + k1 lo c0 with c1 / c0 the one- and
+// zero-samples up to m: an integer scan, and the phase is formed from the counts directly (fsk_phase1), no f64 sum at all.
+// Stage 2's input is constant over the rep2(m) outputs of an audio sample, so its f64 scan runs over rep2(m) * (k2 a[m]) per
+// audio sample and the output-rate kernel is a map.  Launches of a push (na audio samples, no outputs; never a matter of the bits):
+//                                      AFSK                                          DIRECT
+//   na == 0                            0                                             0
+//   na <= FSK_T (one audio tile)       2: k_fsk_audio, k_fsk_map                     2: k_fsk_audio, k_fsk_map
+//   na >  FSK_T                        5: k_fsk_count, k_fsk_scan1, k_fsk_audio,     4: k_fsk_count, k_fsk_scan1, k_fsk_audio,
+//                                         k_vco_scan, k_fsk_map                         k_fsk_map
+// and one fewer where no == 0 (every audio sample of the push is one the second resampler drops: k_fsk_map has nothing to do).
+// As above, no workgroup waits on another one and there is no atomic.
 #include "kernels.hpp"
 #include "packet_common.hpp"
 
@@ -210,6 +223,199 @@ void launch_vco(const float* in, cf* out, long n, double k, const double* carry_
 void launch_fm_tx(const float* in, cf* out, long r, const float* pending, long n_gather, long I, long D, long c0, double k,
                   const double* carry_in, double* carry_out, double* tiles, hipStream_t s) {
     vco_launch(VcoSrc<true>{in, pending, r, I, D, c0}, out, r + n_gather, k, carry_in, carry_out, tiles, s);
+}
+
+// ---- rr_fsk_tx (see the header comment; fsk_core.hpp has the index maps and the phase arithmetic) ---------------------------------
+static_assert(FSK_T == FSK_B * FSK_PER && FSK_OT == FSK_B * FSK_PER && FSK_B == VCO_B, "8 audio samples / 8 outputs per thread");
+static_assert(FSK_MX == VCO_MX && FSK_SCAN_CHUNK == VCO_SCHUNK, "one 2 pi, one scan chunk");
+
+// Exclusive scan of one count per thread over a workgroup of NW waves; total = the sum of all.  s_w: NW unsigneds.
+template <int NW> __device__ __forceinline__ unsigned fsk_block_scan(unsigned v, unsigned* s_w, unsigned& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned u = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += u;
+    }
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    unsigned woff = 0, tot = 0;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        const unsigned t = s_w[j];
+        if (j < w) woff += t;
+        tot += t;
+    }
+    __syncthreads();                          // s_w is free again
+    total = tot;
+    return woff + inc - v;
+}
+
+// bit j of the result: audio sample m0 + j of the push is a one-sample (its bit is nonzero: the reference's s > 0), j < cnt <= 8
+__device__ __forceinline__ unsigned fsk_ones8(const FskTxArgs& a, long m0, int cnt) {
+    unsigned mask = 0;
+    if (cnt <= 0) return 0;
+    FskWalk w = fsk_walk_src(a.r1, a.e1, m0);
+#pragma unroll
+    for (int j = 0; j < FSK_PER; ++j) {
+        if (j < cnt) {
+            mask |= (a.bits[w.q] != 0 ? 1u : 0u) << j;
+            w.next();
+        }
+    }
+    return mask;
+}
+
+// the one-samples of every audio tile
+__global__ __launch_bounds__(FSK_B) void k_fsk_count(FskTxArgs a) {
+    __shared__ unsigned s_w[FSK_B / 64];
+    const long ntiles = (a.na + FSK_T - 1) / FSK_T;
+    for (long tile = blockIdx.x; tile < ntiles; tile += (long)gridDim.x) {
+        const long m0 = tile * FSK_T + (long)threadIdx.x * FSK_PER;
+        const long left = a.na - m0;
+        const unsigned mask = fsk_ones8(a, m0, (int)(left < FSK_PER ? left : FSK_PER));
+        unsigned total;
+        (void)fsk_block_scan<FSK_B / 64>((unsigned)__popc(mask), s_w, total);
+        if (threadIdx.x == 0) a.tilecnt[tile] = total;
+    }
+}
+
+// tilecnt[i] <- tilecnt[0] + ... + tilecnt[i - 1] (at most 2^30: the audio samples of a push).  One workgroup, chunks of
+// VCO_SCHUNK tiles, as k_vco_scan.
+__global__ __launch_bounds__(VCO_SB) void k_fsk_scan1(unsigned* __restrict__ tilecnt, long ntiles) {
+    __shared__ unsigned s_w[VCO_SB / 64];
+    unsigned base = 0;
+    for (long c0 = 0; c0 < ntiles; c0 += VCO_SCHUNK) {
+        const long j0 = c0 + (long)threadIdx.x * VCO_SPER;
+        unsigned v[VCO_SPER], run = 0;
+#pragma unroll
+        for (int i = 0; i < VCO_SPER; ++i) { v[i] = j0 + i < ntiles ? tilecnt[j0 + i] : 0u; run += v[i]; }
+        unsigned total;
+        unsigned p = base + fsk_block_scan<VCO_SB / 64>(run, s_w, total);
+#pragma unroll
+        for (int i = 0; i < VCO_SPER; ++i) {
+            if (j0 + i < ntiles) tilecnt[j0 + i] = p;
+            p += v[i];
+        }
+        base += total;
+    }
+}
+
+// Stage 1, and in AFSK mode the audio-rate half of stage 2.  Per audio sample m of the push: its phase from the count of
+// one-samples up to it (fsk_phase1), then
+//   DIRECT  val[m] = gain * (sin, cos), what the map kernel copies to the sample's outputs
+//   AFSK    audio[m] = fl32(fl32(sin) * gain); pre2[m] = the wrapped sum of rep2(m') * (k2 * audio[m']) over the tile's m' < m
+//           (SINGLE: on top of the carried phase 2), and the tile's sum to tiles2[tile] (SINGLE: phase 2 carried out)
+// The thread that owns the push's last sample writes phase 1 carried out.
+template <bool AFSK, bool SINGLE>
+__global__ __launch_bounds__(FSK_B) void k_fsk_audio(FskTxArgs a) {
+    __shared__ unsigned s_c[FSK_B / 64];
+    __shared__ double s_w[FSK_B / 64];
+    const long ntiles = (a.na + FSK_T - 1) / FSK_T;
+    const double carried1 = a.carry_in[0];
+    for (long tile = blockIdx.x; tile < ntiles; tile += (long)gridDim.x) {
+        const long m0 = tile * FSK_T + (long)threadIdx.x * FSK_PER;
+        const long left = a.na - m0;
+        const int cnt = (int)(left < 0 ? 0 : left < FSK_PER ? left : FSK_PER);
+        const unsigned mask = fsk_ones8(a, m0, cnt);
+        unsigned total1;
+        long c1 = (long)fsk_block_scan<FSK_B / 64>((unsigned)__popc(mask), s_c, total1);
+        if (!SINGLE) c1 += (long)a.tilecnt[tile];
+        FskWalk f2{};
+        if (AFSK && cnt > 0) f2 = fsk_walk_first(a.r2, a.e2, m0);
+        double e[FSK_PER], run = 0.0;
+#pragma unroll
+        for (int i = 0; i < FSK_PER; ++i) {
+            e[i] = run;
+            if (i < cnt) {
+                const long m = m0 + i;
+                c1 += (mask >> i) & 1u;
+                const double ph = fsk_phase1(carried1, c1, m + 1 - c1, a.dhi, a.dlo);
+                double sn, cs;
+                vco_sincos(ph, &sn, &cs);
+                if (m == a.na - 1) a.carry_out[0] = ph;
+                if (AFSK) {
+                    const float au = (float)sn * a.gain;
+                    a.audio[m] = au;
+                    const long o0 = f2.q;
+                    f2.next();
+                    run = vco_wrap(run + fsk_red(f2.q - o0, fsk_step(a.k2, au)));
+                } else {
+                    a.val[m] = mkcf((float)sn * a.gain, (float)cs * a.gain);
+                }
+            }
+        }
+        if (AFSK) {
+            double total2;
+            double p0 = vco_block_scan<FSK_B / 64>(run, s_w, total2);
+            if (SINGLE) p0 = vco_wrap(a.carry_in[1] + p0);
+#pragma unroll
+            for (int i = 0; i < FSK_PER; ++i)
+                if (i < cnt) a.pre2[m0 + i] = vco_wrap(p0 + e[i]);
+            if (threadIdx.x == 0) {
+                if (SINGLE) a.carry_out[1] = vco_wrap(a.carry_in[1] + total2);
+                else a.tiles2[tile] = total2;
+            }
+        }
+    }
+}
+
+// The output-rate kernel: a map.  Output o of the push belongs to audio sample m = src2(o) and is the j-th of its run, j - 1 =
+// floor(rem / D2) with rem what the division left; thread t takes o = tile * FSK_OT + t + 256 i, so a wave's stores are one run
+// of 512 bytes and m moves by a fixed step: one 64-bit division per thread and tile.
+//   DIRECT  out[o] = val[m]
+//   AFSK    out[o] = (sin, cos)(base + pre2[m] + j * (k2 * audio[m])), base = tiles2[m's tile] (SINGLE: pre2 holds it already)
+template <bool AFSK, bool SINGLE>
+__global__ __launch_bounds__(FSK_B) void k_fsk_map(FskTxArgs a) {
+    const long ntiles = (a.no + FSK_OT - 1) / FSK_OT;
+    for (long tile = blockIdx.x; tile < ntiles; tile += (long)gridDim.x) {
+        const long o0 = tile * FSK_OT + threadIdx.x;
+        if (o0 >= a.no) continue;             // (no barrier in this kernel)
+        FskWalk w = fsk_walk(a.e2 + o0 * a.r2.D, a.map_dq, a.map_dr, a.r2.I);
+#pragma unroll
+        for (int i = 0; i < FSK_PER; ++i) {
+            const long o = o0 + (long)i * FSK_B;
+            if (o < a.no) {
+                const long m = w.q;
+                if (AFSK) {
+                    const long j = (long)((unsigned)w.r / (unsigned)a.r2.D) + 1;      // both below 2^32: I2, D2 <= 2^31
+                    double p = a.pre2[m];
+                    if (!SINGLE) p = vco_wrap(a.tiles2[m / FSK_T] + p);
+                    p = vco_wrap(p + fsk_red(j, fsk_step(a.k2, a.audio[m])));
+                    double sn, cs;
+                    vco_sincos(p, &sn, &cs);
+                    a.out[o] = mkcf((float)sn, (float)cs);
+                } else {
+                    a.out[o] = a.val[m];
+                }
+                w.next();
+            }
+        }
+    }
+}
+
+template <bool AFSK> static void fsk_launch(const FskTxArgs& a, hipStream_t s) {
+    const long ntiles = (a.na + FSK_T - 1) / FSK_T;
+    const unsigned go = tiles_grid((a.no + FSK_OT - 1) / FSK_OT);
+    if (ntiles == 1) {
+        hipLaunchKernelGGL((k_fsk_audio<AFSK, true>), dim3(1), dim3(FSK_B), 0, s, a);
+        if (a.no > 0) hipLaunchKernelGGL((k_fsk_map<AFSK, true>), dim3(go), dim3(FSK_B), 0, s, a);
+        RR_HIP(hipGetLastError());
+        return;
+    }
+    const unsigned g = tiles_grid(ntiles);
+    hipLaunchKernelGGL(k_fsk_count, dim3(g), dim3(FSK_B), 0, s, a);
+    hipLaunchKernelGGL(k_fsk_scan1, dim3(1), dim3(VCO_SB), 0, s, a.tilecnt, ntiles);
+    hipLaunchKernelGGL((k_fsk_audio<AFSK, false>), dim3(g), dim3(FSK_B), 0, s, a);
+    if (AFSK) hipLaunchKernelGGL(k_vco_scan, dim3(1), dim3(VCO_SB), 0, s, a.tiles2, ntiles, a.carry_in + 1, a.carry_out + 1);
+    if (a.no > 0) hipLaunchKernelGGL((k_fsk_map<AFSK, false>), dim3(go), dim3(FSK_B), 0, s, a);
+    RR_HIP(hipGetLastError());
+}
+void launch_fsk_tx(const FskTxArgs& a, bool afsk, hipStream_t s) {
+    if (a.na <= 0) return;
+    if (afsk) fsk_launch<true>(a, s);
+    else fsk_launch<false>(a, s);
 }
 
 }  // namespace rr

@@ -1258,6 +1258,53 @@ inline unsigned long long f64_bits(double k) {
     return b;
 }
 }  // namespace detail
+
+// ---- FskTx: the modulators of examples/bell202.rs:166-183 (AFSK) and examples/g3ruh.rs:256-272 (DIRECT) in PDU form --------------
+// (rr_fsk_tx_create / rr_fsk_tx_count / rr_fsk_tx_push / rr_fsk_tx_push_dev / rr_fsk_tx_dims).  push() takes the next line bits
+// (HdlcFramer's u8, nonzero = 1) and returns everything they produce; both phases stay in the block from push to push.
+class FskTx {
+    detail::Handle h_;
+public:
+    enum Mode { Direct = RR_FSK_TX_DIRECT, Afsk = RR_FSK_TX_AFSK };
+    struct Pushed {
+        std::vector<Complex> out;
+        std::vector<float> audio;             // AFSK mode with audio asked for: a[] of this push
+    };
+    FskTx(int mode, size_t interp1, size_t deci1, float lo, float hi, double k1, float gain, size_t interp2 = 1, size_t deci2 = 1,
+          double k2 = 0.0)
+        : h_(rr_fsk_tx_create(mode, interp1, deci1, lo, hi, detail::f64_bits(k1), gain, interp2, deci2, detail::f64_bits(k2))) {}
+    rr_block* handle() const { return h_.h; }
+    // (n_audio, n_out) of the NEXT push of n_bits
+    std::pair<size_t, size_t> count(size_t n_bits) const {
+        size_t a = 0, o = 0;
+        if (rr_fsk_tx_count(h_.h, n_bits, &a, &o) != 0) throw Error(rr_last_error());
+        return {a, o};
+    }
+    Pushed push(const std::vector<unsigned char>& bits, bool want_audio = false) {
+        const auto [na, no] = count(bits.size());
+        Pushed p;
+        p.out.resize(no + 1);
+        if (want_audio) p.audio.resize(na + 1);
+        size_t o = 0, a = 0;
+        if (rr_fsk_tx_push(h_.h, bits.data(), bits.size(), reinterpret_cast<rr_c32*>(p.out.data()), no,
+                           want_audio ? p.audio.data() : nullptr, want_audio ? na : 0, &o, &a) != 0)
+            throw Error(rr_last_error());
+        p.out.resize(std::min(o, no));
+        if (want_audio) p.audio.resize(std::min(a, na));
+        return p;
+    }
+    // device pointers; asynchronous on hip_stream -> (n_out, n_audio), there when the call returns
+    std::pair<size_t, size_t> push_dev(const void* d_bits, size_t n_bits, void* d_out, size_t out_cap, void* d_audio = nullptr,
+                                       size_t audio_cap = 0, void* hip_stream = nullptr) {
+        size_t o = 0, a = 0;
+        if (rr_fsk_tx_push_dev(h_.h, d_bits, n_bits, d_out, out_cap, d_audio, audio_cap, &o, &a, hip_stream) != 0) throw Error(rr_last_error());
+        return {o, a};
+    }
+    size_t audio_tile() const { size_t a = 0, o = 0, c = 0; if (rr_fsk_tx_dims(h_.h, &a, &o, &c) != 0) throw Error(rr_last_error()); return a; }
+    size_t out_tile() const { size_t a = 0, o = 0, c = 0; if (rr_fsk_tx_dims(h_.h, &a, &o, &c) != 0) throw Error(rr_last_error()); return o; }
+    size_t scan_chunk_tiles() const { size_t a = 0, o = 0, c = 0; if (rr_fsk_tx_dims(h_.h, &a, &o, &c) != 0) throw Error(rr_last_error()); return c; }
+};
+
 class Vco : public SyncBlock<Float, Complex> {
 public:
     using SyncBlock<Float, Complex>::SyncBlock;
