@@ -517,6 +517,12 @@ int rr_hdlc_framer_records(rr_block *b, rr_frame_record *rec, size_t cap, size_t
 /* *tile_bits = the payload bits of one tile of the stuffing scan, which is also the tile of the line coder (tests aim at the
  * seams with it). */
 int rr_hdlc_framer_dims(const rr_block *b, size_t *tile_bits);
+/* The elements the most recent push of at least one packet produced, where the next device stage can read them: ONE unsigned long
+ * long on the device, the word rr_hdlc_framer_records downloads, ordered behind that push on its stream and valid until the next
+ * push (the counterpart of rr_symbol_sync_counts_dev).  As the d_counts of rr_fsk_tx_multi_push_dev it takes the host read out of
+ * framer -> modulator; for N framers, gather their words with 8-byte device-to-device copies on the same stream.  A push of no
+ * packets leaves the word as it was.  NULL for a handle that is no framer. */
+const void *rr_hdlc_framer_produced_dev(rr_block *b);
 
 /* HdlcDeframer::new(src, min_size, max_size) (src/hdlc_deframer.rs:80-101) with set_keep_checksum (:119-121) and set_fix_bits
  * (:114-116) as flags: line bits in, checked frames out, the last block of the packet receivers (examples/ax25-9600-rx.rs,
@@ -807,6 +813,57 @@ int rr_fsk_tx_push(rr_block *b, const void *bits, size_t n_bits, rr_c32 *out, si
 /* *audio_tile = audio samples of one scan tile (2048), *out_tile = outputs of one workgroup of the map kernel (2048),
  * *scan_chunk_tiles = audio tiles one pass of the tile-level scans takes (4096) */
 int rr_fsk_tx_dims(const rr_block *b, size_t *audio_tile, size_t *out_tile, size_t *scan_chunk_tiles);
+
+/* rr_fsk_tx for nstreams streams that share one parameter set, behind one handle: the transmit counterpart of rr_afsk_demod ->
+ * rr_symbol_sync -> rr_hdlc_receiver.  Every stream's state (where its two resamplers stand, both phases) stays on the device, and
+ * the ragged bit counts of a push are read there under the contract of rr_hdlc_receiver_push_dev, so rr_hdlc_framer_push_dev ->
+ * rr_fsk_tx_multi_push_dev needs no host read (rr_hdlc_framer_produced_dev).  A batch block: rr_block_work on the handle is an error.
+ * Each stream's push is planned on the device from its own carried position and count, and runs the general path of rr_fsk_tx
+ * (the kernels' bodies are shared) with tiles that start at the stream's own push start: a stream's out, audio and counts are
+ * bit-identical to an rr_fsk_tx handle given the same pushes wherever each of those pushes makes no audio sample or more than
+ * one audio tile (rr_fsk_tx_multi_dims), and do not depend on n_cap, the strides, nstreams or the other streams.  A push of 1 ..
+ * audio_tile audio samples takes rr_fsk_tx's one-tile path there and the general path here: both inside the bounds of rr_fsk_tx,
+ * not bit-identical.  Launches of a push: 6 (AFSK) or 5 (DIRECT) whatever the counts, the bits and nstreams are; 0 for n_cap == 0.
+ * NULL + rr_last_error, said before any device is touched: the refusals of rr_fsk_tx_create, then "nstreams out of range" (0 or
+ * above 65535, the grid's y as in rr_afsk_demod_create).
+ * NOT TESTED: more than 64 streams except in the timing probe; pushes near 2^30 elements; positions near 2^62. */
+rr_block *rr_fsk_tx_multi_create(size_t nstreams, int mode, size_t interp1, size_t deci1, float lo, float hi,
+                                 unsigned long long k1_bits, float gain, size_t interp2, size_t deci2, unsigned long long k2_bits);
+/* The most ONE stream can make from n_cap bits whatever its residues: *audio_cap = ceil(n_cap I1 / D1), *out_cap = ceil(*audio_cap
+ * I2 / D2) on the reduced ratios, saturated at the largest size_t (either pointer may be NULL).  What the strides of a push must
+ * hold, and what its scratch and grids are sized from (the role rr_hdlc_framer_bound has for the framer). */
+int rr_fsk_tx_multi_bound(const rr_block *b, size_t n_cap, size_t *audio_cap, size_t *out_cap);
+/* stream c: the next min(d_counts[c], n_cap) u8 bits at d_bits + c*bits_stride; its outputs (Complex) to d_out + c*out_stride; in
+ * AFSK mode with d_audio non-NULL its audio (f32) to d_audio + c*audio_stride.  d_counts: unsigned long long[nstreams] on the
+ * device, read there and clamped to n_cap before it is used (the contract of rr_hdlc_receiver_push_dev); NULL: every stream has
+ * n_cap.  Bits at and beyond a stream's count are never read; outputs and audio at and beyond a stream's own counts are never
+ * written.  A stream whose count is 0 keeps every piece of its state; one whose bits make no audio sample moves only its first
+ * resampler.  RR_ERR before any device is touched, nothing launched: "fsk tx multi: DIRECT mode has no audio output", "... more than
+ * 2^30 bits of a stream in one push" (n_cap), "... more than 2^30 audio samples of all streams in one push" / "... outputs ..."
+ * (nstreams times the bound), "... output position beyond 2^62" (judged from the sum of the n_cap of all pushes, an upper bound of
+ * every stream's bit position: the host does not know the device's), "... bits_stride below n_cap", "... out_stride below the outputs
+ * a stream can make", "... audio_stride below the audio samples a stream can make", "... null bit buffer", "... null output buffer".
+ * n_cap == 0 launches nothing, makes nothing and leaves every state alone.  Asynchronous on hip_stream (used as given). */
+int rr_fsk_tx_multi_push_dev(rr_block *b, const void *d_bits, size_t bits_stride, size_t n_cap, const void *d_counts,
+                             void *d_out, size_t out_stride, void *d_audio, size_t audio_stride, void *hip_stream);
+/* The same with host pointers (counts, audio, n_out and n_audio may be NULL): copies the bits the counts cover and the counts
+ * down, runs, waits and copies what each stream made back (the shape of rr_symbol_sync_push). */
+int rr_fsk_tx_multi_push(rr_block *b, const unsigned char *bits, size_t bits_stride, size_t n_cap, const size_t *counts,
+                         rr_c32 *out, size_t out_stride, float *audio, size_t audio_stride,
+                         size_t *n_out /* [nstreams] */, size_t *n_audio /* [nstreams] */);
+/* What each stream made in the most recent push; waits for it (one download of 16*nstreams bytes).  *total = nstreams, the first
+ * min(*total, cap) of each array written, an array may be NULL (the contract of rr_symbol_sync_produced); every value is checked
+ * against the bound of the push before anybody sees it ("fsk tx multi: the device's counts exceed the bound of the push"). */
+int rr_fsk_tx_multi_counts(rr_block *b, size_t *n_audio, size_t *n_out, size_t cap, size_t *total);
+/* the same counts where the next device stage can read them: unsigned long long[2][nstreams], audio counts then output counts,
+ * valid until the next push (as rr_symbol_sync_counts_dev) */
+const void *rr_fsk_tx_multi_counts_dev(rr_block *b);
+/* Each stream's bits taken, audio samples and outputs made so far; waits for the most recent push (the shape of
+ * rr_hdlc_receiver_consumed; an array may be NULL).  For the tests: nothing else needs the positions on the host. */
+int rr_fsk_tx_multi_positions(rr_block *b, unsigned long long *bits, unsigned long long *audio, unsigned long long *out,
+                              size_t cap, size_t *total);
+/* as rr_fsk_tx_dims */
+int rr_fsk_tx_multi_dims(const rr_block *b, size_t *audio_tile, size_t *out_tile, size_t *scan_chunk_tiles);
 
 /* Graph-level fusion of Hilbert::new(src, hilbert_ntaps, &window) (src/hilbert.rs:38-61) ->
  * FirFilter::<Complex>::builder(taps).deci(deci)[.translate(samp_rate, freq)].build(_) (src/fir.rs:303-386,476-486)

@@ -192,6 +192,27 @@ unsafe extern "C" {
                       audio_cap: usize, n_out: *mut usize, n_audio: *mut usize) -> c_int;
     #[allow(dead_code)]
     fn rr_fsk_tx_dims(b: *const RrBlock, audio_tile: *mut usize, out_tile: *mut usize, scan_chunk_tiles: *mut usize) -> c_int;
+    // (declared for completeness, as rr_fsk_tx above: nstreams modulators behind one handle, the counts of a push read on the device;
+    //  the device-pointer side only, as for rr_hdlc_receiver)
+    #[allow(dead_code)]
+    fn rr_fsk_tx_multi_create(nstreams: usize, mode: c_int, interp1: usize, deci1: usize, lo: f32, hi: f32, k1_bits: u64, gain: f32,
+                              interp2: usize, deci2: usize, k2_bits: u64) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_fsk_tx_multi_bound(b: *const RrBlock, n_cap: usize, audio_cap: *mut usize, out_cap: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_fsk_tx_multi_push_dev(b: *mut RrBlock, d_bits: *const c_void, bits_stride: usize, n_cap: usize, d_counts: *const c_void,
+                                d_out: *mut c_void, out_stride: usize, d_audio: *mut c_void, audio_stride: usize,
+                                hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_fsk_tx_multi_counts(b: *mut RrBlock, n_audio: *mut usize, n_out: *mut usize, cap: usize, total: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_fsk_tx_multi_counts_dev(b: *mut RrBlock) -> *const c_void;
+    #[allow(dead_code)]
+    fn rr_fsk_tx_multi_positions(b: *mut RrBlock, bits: *mut u64, audio: *mut u64, out: *mut u64, cap: usize, total: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_fsk_tx_multi_dims(b: *const RrBlock, audio_tile: *mut usize, out_tile: *mut usize, scan_chunk_tiles: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_hdlc_framer_produced_dev(b: *mut RrBlock) -> *const c_void;
     fn rr_fm_chain_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_fm_chain_u8_create(taps: *const Complex, ntaps: usize, interp: usize, deci: usize, gain: f32, atan2_mode: c_int) -> *mut RrBlock;
     fn rr_audio_chain_create(taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;

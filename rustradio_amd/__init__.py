@@ -761,6 +761,11 @@ class HdlcFramer(Block):
         rec, = _fetch(lib().rr_hdlc_framer_records, self._h, FRAME_RECORD, tail=(C.byref(produced),))
         return rec, produced.value
 
+    def produced_dev(self) -> int:
+        """-> raw device pointer to the elements the most recent push produced, one unsigned long long
+        (rr_hdlc_framer_produced_dev): the d_counts of FskTxMulti.push_dev; valid until the next push"""
+        return lib().rr_hdlc_framer_produced_dev(self._h)
+
 
 HDLC_KEEP_CHECKSUM, HDLC_FIX_BITS = 1, 2      # RR_HDLC_*
 # rr_hdlc_frame
@@ -1149,6 +1154,84 @@ class FskTx(Block):
                                 na if audio else 0, C.byref(o), C.byref(a)) != 0:
             raise ValueError(last_error())
         return (out[:o.value].copy(), aud[:a.value].copy()) if audio else out[:o.value].copy()
+
+
+class FskTxMulti(Block):
+    """FskTx x nstreams of one parameter set behind one handle (rr_fsk_tx_multi_create; not a stream block: work() raises): ragged
+    pushes of u8 line bits in, each stream's Complex baseband (and, in AFSK mode, its audio) out.  Every stream's state stays on
+    the device and the bit counts of a push are read there, so HdlcFramer.push_dev -> FskTxMulti.push_dev needs no host read
+    (HdlcFramer.produced_dev).  See include/rustradio_amd.h."""
+
+    def __init__(self, nstreams: int, mode: int, interp1: int, deci1: int, lo: float, hi: float, k1: float, gain: float,
+                 interp2: int = 1, deci2: int = 1, k2: float = 0.0):
+        super().__init__(lib().rr_fsk_tx_multi_create(int(nstreams), int(mode), int(interp1), int(deci1), float(lo), float(hi),
+                                                      _f64_bits(float(k1)), float(gain), int(interp2), int(deci2),
+                                                      _f64_bits(float(k2))), np.uint8, np.complex64)
+        self.nstreams, self.mode = int(nstreams), int(mode)
+
+    def dims(self):
+        """-> (audio_tile, out_tile, scan_chunk_tiles) (rr_fsk_tx_multi_dims)"""
+        a, o, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_fsk_tx_multi_dims(self._h, C.byref(a), C.byref(o), C.byref(c)) != 0:
+            raise RuntimeError(last_error())
+        return a.value, o.value, c.value
+
+    def bound(self, n_cap: int):
+        """-> (audio_cap, out_cap): the most one stream makes from n_cap bits (rr_fsk_tx_multi_bound)"""
+        a, o = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_fsk_tx_multi_bound(self._h, int(n_cap), C.byref(a), C.byref(o)) != 0:
+            raise RuntimeError(last_error())
+        return a.value, o.value
+
+    def push_dev(self, d_bits: int, bits_stride: int, n_cap: int, d_counts, d_out: int, out_stride: int, d_audio: int = 0,
+                 audio_stride: int = 0, stream: int = 0) -> None:
+        """rr_fsk_tx_multi_push_dev: stream c's next min(d_counts[c], n_cap) bits at d_bits + c * bits_stride (raw device pointers;
+        d_counts: unsigned long long[nstreams], e.g. HdlcFramer.produced_dev(), or None: n_cap each), its outputs to d_out + c *
+        out_stride, its audio to d_audio + c * audio_stride (0: not wanted); asynchronous on `stream`; counts() waits"""
+        if lib().rr_fsk_tx_multi_push_dev(self._h, C.c_void_p(d_bits) if d_bits else None, int(bits_stride), int(n_cap),
+                                          C.c_void_p(d_counts) if d_counts else None, C.c_void_p(d_out) if d_out else None,
+                                          int(out_stride), C.c_void_p(d_audio) if d_audio else None, int(audio_stride),
+                                          C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+
+    def push(self, bits, counts=None, audio: bool = False):
+        """rr_fsk_tx_multi_push on a host array of shape (nstreams, n_cap) (or (n_cap,) for one stream), of which stream c holds
+        counts[c] bits (None: n_cap) -> [complex64 out of stream c], or ([out], [float32 audio]) with audio=True (AFSK mode)"""
+        b = np.ascontiguousarray(bits, np.uint8)
+        b = b.reshape(1, -1) if b.ndim == 1 else b
+        if b.ndim != 2 or b.shape[0] != self.nstreams:
+            raise ValueError("FskTxMulti.push: one row per stream")
+        n = b.shape[1]
+        k = None
+        if counts is not None:
+            if len(counts) != self.nstreams:
+                raise ValueError("FskTxMulti.push: one count per stream")
+            k = (C.c_size_t * self.nstreams)(*[int(v) for v in counts])
+        ac, oc = self.bound(n)
+        out = np.zeros((self.nstreams, max(oc, 1)), np.complex64)
+        aud = np.zeros((self.nstreams, max(ac, 1)), np.float32) if audio else None
+        no, na = (C.c_size_t * self.nstreams)(), (C.c_size_t * self.nstreams)()
+        if lib().rr_fsk_tx_multi_push(self._h, _ptr(b) if n else None, n, n, k, _ptr(out), out.shape[1], _ptr(aud) if audio else None,
+                                      aud.shape[1] if audio else 0, no, na) != 0:
+            raise ValueError(last_error())
+        outs = [out[c, :no[c]].copy() for c in range(self.nstreams)]
+        return (outs, [aud[c, :na[c]].copy() for c in range(self.nstreams)]) if audio else outs
+
+    def counts(self) -> np.ndarray:
+        """-> uint64[nstreams, 2]: (n_audio, n_out) of each stream in the most recent push (rr_fsk_tx_multi_counts; waits)"""
+        a, o = _fetch(lib().rr_fsk_tx_multi_counts, self._h, np.uintp, np.uintp)
+        return np.stack([a, o], axis=1).astype(np.uint64)
+
+    def counts_dev(self) -> int:
+        """-> raw device pointer to the same counts, unsigned long long[2][nstreams], audio counts then output counts
+        (rr_fsk_tx_multi_counts_dev); valid until the next push"""
+        return lib().rr_fsk_tx_multi_counts_dev(self._h)
+
+    def positions(self) -> np.ndarray:
+        """-> uint64[nstreams, 3]: bits taken, audio samples and outputs made by each stream so far (rr_fsk_tx_multi_positions;
+        waits)"""
+        b, a, o = _fetch(lib().rr_fsk_tx_multi_positions, self._h, np.uint64, np.uint64, np.uint64)
+        return np.stack([b, a, o], axis=1)
 
 
 WPCR_MAX_LEN = 512_000     # samples of one burst: the reference's stream capacity in f32

@@ -84,7 +84,7 @@ template <class T> static T* as(const rr_block* b, const char* what, const char*
 static const char NOT_WPCR[] = "not a wpcr handle", NOT_PDU[] = "not a stream_to_pdu handle", NOT_FRAMER[] = "not an hdlc framer handle";
 static const char NOT_DEFRAMER[] = "not an hdlc deframer handle", NOT_SYNC[] = "not a symbol sync handle", NOT_AFSK[] = "not an afsk demod handle";
 static const char NOT_RECEIVER[] = "not an hdlc receiver handle", NOT_PWM[] = "not a pwm decoder handle";
-static const char NOT_FSK[] = "not an fsk tx handle";
+static const char NOT_FSK[] = "not an fsk tx handle", NOT_FSKM[] = "not an fsk tx multi handle";
 // a fetched list of (pos << shift) | val entries into the caller's two arrays
 template <class E> static void unpack(const std::vector<E>& e, unsigned shift, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
     *total = e.size();
@@ -447,6 +447,10 @@ int rr_hdlc_framer_dims(const rr_block* b, size_t* tile_bits) {
     *tile_bits = rr::FRAME_T;
     return 0;
 }
+const void* rr_hdlc_framer_produced_dev(rr_block* b) {
+    auto* f = as<rr::HdlcFramer>(b, "rr_hdlc_framer_produced_dev", NOT_FRAMER);
+    return f ? f->total.p : nullptr;
+}
 rr_block* rr_hdlc_deframer_create(size_t min_size, size_t max_size, int flags) {
     if (const char* e = rr::hdlc_check_create(min_size, max_size, flags)) return refuse_create(e);
     return make_block([&] { return new rr::HdlcDeframer(min_size, max_size, flags); });
@@ -756,6 +760,92 @@ int rr_fsk_tx_push(rr_block* b, const void* bits, size_t n_bits, rr_c32* out, si
 int rr_fsk_tx_dims(const rr_block* b, size_t* audio_tile, size_t* out_tile, size_t* scan_chunk_tiles) {
     auto* y = as<rr::FskTx>(b, "rr_fsk_tx_dims", NOT_FSK);
     if (!y || !audio_tile || !out_tile || !scan_chunk_tiles) { if (y) rr::set_last_error("rr_fsk_tx_dims: null argument"); return RR_ERR; }
+    *audio_tile = (size_t)rr::FSK_T;
+    *out_tile = (size_t)rr::FSK_OT;
+    *scan_chunk_tiles = (size_t)rr::FSK_SCAN_CHUNK;
+    return 0;
+}
+rr_block* rr_fsk_tx_multi_create(size_t nstreams, int mode, size_t interp1, size_t deci1, float lo, float hi, unsigned long long k1_bits,
+                                 float gain, size_t interp2, size_t deci2, unsigned long long k2_bits) {
+    const double k1 = f64_from_bits(k1_bits), k2 = f64_from_bits(k2_bits);
+    if (const char* e = rr::fsk_multi_check(nstreams, mode, interp1, deci1, lo, hi, k1, gain, interp2, deci2, k2)) return refuse_create(e);
+    return make_block([&] { return new rr::FskTxMulti(nstreams, mode, interp1, deci1, lo, hi, k1, gain, interp2, deci2, k2); });
+}
+int rr_fsk_tx_multi_bound(const rr_block* b, size_t n_cap, size_t* audio_cap, size_t* out_cap) {
+    auto* y = as<rr::FskTxMulti>(b, "rr_fsk_tx_multi_bound", NOT_FSKM);
+    if (!y) return RR_ERR;
+    size_t ac = 0, oc = 0;
+    rr::fsk_multi_bound(y->r1, y->r2, n_cap, &ac, &oc);
+    if (audio_cap) *audio_cap = ac;
+    if (out_cap) *out_cap = oc;
+    return 0;
+}
+int rr_fsk_tx_multi_push_dev(rr_block* b, const void* d_bits, size_t bits_stride, size_t n_cap, const void* d_counts, void* d_out,
+                             size_t out_stride, void* d_audio, size_t audio_stride, void* hip_stream) {
+    auto* y = as<rr::FskTxMulti>(b, "rr_fsk_tx_multi_push_dev", NOT_FSKM);
+    if (!y) return RR_ERR;
+    if (const char* e = rr::fsk_multi_check_push(y->mode, y->nstreams, y->r1, y->r2, y->bits_bound, d_bits, bits_stride, n_cap, d_out,
+                                                 out_stride, d_audio, audio_stride, nullptr, nullptr)) {   // before any device is touched
+        rr::set_last_error(e);
+        return RR_ERR;
+    }
+    return on_device(y, hip_stream, [&](hipStream_t s) {
+        y->push_dev(static_cast<const unsigned char*>(d_bits), bits_stride, n_cap, static_cast<const unsigned long long*>(d_counts),
+                    static_cast<rr::cf*>(d_out), out_stride, static_cast<float*>(d_audio), audio_stride, s);
+    });
+}
+int rr_fsk_tx_multi_push(rr_block* b, const unsigned char* bits, size_t bits_stride, size_t n_cap, const size_t* counts, rr_c32* out,
+                         size_t out_stride, float* audio, size_t audio_stride, size_t* n_out, size_t* n_audio) {
+    auto* y = as<rr::FskTxMulti>(b, "rr_fsk_tx_multi_push", NOT_FSKM);
+    if (!y) return RR_ERR;
+    for (size_t c = 0; c < y->nstreams; c++) {
+        if (n_out) n_out[c] = 0;
+        if (n_audio) n_audio[c] = 0;
+    }
+    if (const char* e = rr::fsk_multi_check_push(y->mode, y->nstreams, y->r1, y->r2, y->bits_bound, bits, bits_stride, n_cap, out, out_stride,
+                                                 audio, audio_stride, nullptr, nullptr)) {
+        rr::set_last_error(e);
+        return RR_ERR;
+    }
+    return guarded([&] { y->push_host(bits, bits_stride, n_cap, counts, reinterpret_cast<rr::cf*>(out), out_stride, audio, audio_stride, n_out, n_audio); });
+}
+int rr_fsk_tx_multi_counts(rr_block* b, size_t* n_audio, size_t* n_out, size_t cap, size_t* total) {
+    auto* y = as<rr::FskTxMulti>(b, "rr_fsk_tx_multi_counts", NOT_FSKM);
+    if (!y) return RR_ERR;
+    if (!total) { rr::set_last_error("rr_fsk_tx_multi_counts: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(y, [&] {
+        const std::vector<unsigned long long>& k = y->fetch_counts();
+        *total = y->nstreams;
+        for (size_t c = 0; c < y->nstreams && c < cap; c++) {
+            if (n_audio) n_audio[c] = (size_t)k[c];
+            if (n_out) n_out[c] = (size_t)k[y->nstreams + c];
+        }
+    });
+}
+const void* rr_fsk_tx_multi_counts_dev(rr_block* b) {
+    auto* y = as<rr::FskTxMulti>(b, "rr_fsk_tx_multi_counts_dev", NOT_FSKM);
+    return y ? y->made.p : nullptr;
+}
+int rr_fsk_tx_multi_positions(rr_block* b, unsigned long long* bits, unsigned long long* audio, unsigned long long* out, size_t cap,
+                              size_t* total) {
+    auto* y = as<rr::FskTxMulti>(b, "rr_fsk_tx_multi_positions", NOT_FSKM);
+    if (!y) return RR_ERR;
+    if (!total) { rr::set_last_error("rr_fsk_tx_multi_positions: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(y, [&] {
+        const std::vector<rr::FskStream> st = y->fetch_state();
+        *total = st.size();
+        for (size_t c = 0; c < st.size() && c < cap; c++) {
+            if (bits) bits[c] = st[c].pos.bits;
+            if (audio) audio[c] = st[c].pos.audio;
+            if (out) out[c] = st[c].pos.out;
+        }
+    });
+}
+int rr_fsk_tx_multi_dims(const rr_block* b, size_t* audio_tile, size_t* out_tile, size_t* scan_chunk_tiles) {
+    auto* y = as<rr::FskTxMulti>(b, "rr_fsk_tx_multi_dims", NOT_FSKM);
+    if (!y || !audio_tile || !out_tile || !scan_chunk_tiles) { if (y) rr::set_last_error("rr_fsk_tx_multi_dims: null argument"); return RR_ERR; }
     *audio_tile = (size_t)rr::FSK_T;
     *out_tile = (size_t)rr::FSK_OT;
     *scan_chunk_tiles = (size_t)rr::FSK_SCAN_CHUNK;

@@ -1,5 +1,5 @@
 // blocks_packet.cpp — host side of the packet-side blocks (blocks_packet.hpp): the sync blocks, the burst and bit blocks, and the
-// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver, AfskDemod, FskTx).  Citations are to the reference's src, as in blocks.cpp.
+// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver, AfskDemod, FskTx, FskTxMulti).  Citations are to the reference's src, as in blocks.cpp.
 #include "blocks_packet.hpp"
 
 #include <algorithm>
@@ -1055,6 +1055,117 @@ FskPush FskTx::push_host(const unsigned char* bits, size_t n_bits, cf* out, size
         if (audio_out && u.na) hstage().d2h(audio_out, h_audio.p, (size_t)u.na * sizeof(float), stream);
     });
     return u;
+}
+
+// ---- FskTxMulti: FskTx x nstreams, every stream's state and count on the device (kernels_tx.hip) ------------------------
+FskTxMulti::FskTxMulti(size_t ns, int md, size_t interp1, size_t deci1, float l, float h, double kk1, float g, size_t interp2, size_t deci2,
+                       double kk2)
+    : BatchBlock(md == FSK_AFSK ? "Resampler>Map>Vco>Re>MultiplyConst>Resampler>Vco" : "Resampler>Map>Vco>MultiplyConst>Resampler", 1, 8,
+                 "FskTxMulti takes pushes of line bits of nstreams streams: rr_fsk_tx_multi_push / rr_fsk_tx_multi_push_dev"),
+      nstreams(ns), mode(md), lo(l), hi(h), gain(g), k1(kk1), k2(md == FSK_AFSK ? kk2 : 0.0) {
+    if (const char* e = fsk_multi_check(ns, md, interp1, deci1, l, h, kk1, g, interp2, deci2, kk2)) throw Error(e);
+    r1 = fsk_ratio((long)interp1, (long)deci1);
+    r2 = fsk_ratio((long)interp2, (long)deci2);
+    st.zero(ns, stream);                             // every FskPos at the stream's start, both phases 0.0 (vco.rs:18)
+    plan.reserve(ns);
+    made.reserve(2 * ns);
+    RR_HIP(hipMemsetAsync(made.p, 0, 2 * ns * sizeof(unsigned long long), stream));
+    counts.assign(2 * ns, 0);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void FskTxMulti::push_dev(const unsigned char* d_bits, size_t bits_stride, size_t n_cap, const unsigned long long* d_counts, cf* d_out,
+                          size_t out_stride, float* d_audio, size_t audio_stride, hipStream_t s) {
+    size_t ac = 0, oc = 0;
+    if (const char* e = fsk_multi_check_push(mode, nstreams, r1, r2, bits_bound, d_bits, bits_stride, n_cap, d_out, out_stride, d_audio,
+                                             audio_stride, &ac, &oc))
+        throw Error(e);
+    counts.assign(2 * nstreams, 0);
+    last_audio_cap = ac; last_out_cap = oc;
+    if (!n_cap) {                                    // a push of no bits makes nothing and leaves every state alone
+        RR_HIP(hipMemsetAsync(made.p, 0, 2 * nstreams * sizeof(unsigned long long), s));
+        fetched = true;
+        return;
+    }
+    const bool afsk = mode == FSK_AFSK;
+    FskTxMultiArgs m{};
+    m.bits = d_bits; m.bits_stride = (long)bits_stride; m.n_cap = (long)n_cap; m.nstreams = (long)nstreams;
+    m.counts = d_counts;
+    m.r1 = r1; m.r2 = r2;
+    m.map_dq = ((long)FSK_B * r2.D) / r2.I; m.map_dr = ((long)FSK_B * r2.D) % r2.I;
+    m.dhi = k1 * (double)hi; m.dlo = k1 * (double)lo; m.k2 = k2;
+    m.gain = gain;
+    m.st_in = st.in(); m.st_out = st.out();
+    m.plan = plan.p; m.made = made.p;
+    m.audio_cap = (long)ac; m.out_cap = (long)oc; m.tpitch = (long)((ac + FSK_T - 1) / FSK_T);
+    tilecnt.reserve(nstreams * (size_t)m.tpitch);
+    m.tilecnt = tilecnt.p;
+    if (afsk) {
+        tiles2.reserve(nstreams * (size_t)m.tpitch);
+        pre2.reserve(nstreams * ac);
+        if (!d_audio) audio.reserve(nstreams * ac);
+        m.tiles2 = tiles2.p; m.pre2 = pre2.p;
+        m.audio = d_audio ? d_audio : audio.p; m.audio_stride = (long)(d_audio ? audio_stride : ac);
+    } else {
+        val.reserve(nstreams * ac);
+        m.val = val.p;
+    }
+    m.out = d_out; m.out_stride = (long)out_stride;
+    prof_begin(s);
+    launch_fsk_tx_multi(m, afsk, s);
+    prof_end(s);
+    st.flip();
+    bits_bound += n_cap;
+    fetched = false;
+}
+void FskTxMulti::push_host(const unsigned char* bits, size_t bits_stride, size_t n_cap, const size_t* cnt, cf* out, size_t out_stride,
+                           float* audio_out, size_t audio_stride, size_t* n_out, size_t* n_audio) {
+    host_call([&] {
+        size_t ac = 0, oc = 0;
+        if (const char* e = fsk_multi_check_push(mode, nstreams, r1, r2, bits_bound, bits, bits_stride, n_cap, out, out_stride, audio_out,
+                                                 audio_stride, &ac, &oc))
+            throw Error(e);
+        if (n_cap) {
+            // only what the counts cover is read from the caller's buffer, as on the device
+            h_bits.reserve(nstreams * n_cap);
+            h_out.reserve(nstreams * oc);
+            if (audio_out) h_audio.reserve(nstreams * ac);
+            std::vector<unsigned long long> k(nstreams, n_cap);
+            for (size_t c = 0; c < nstreams; c++) {
+                if (cnt) k[c] = std::min<unsigned long long>(cnt[c], n_cap);
+                if (k[c]) hstage().h2d(h_bits.p + c * n_cap, bits + c * bits_stride, (size_t)k[c], stream);
+            }
+            if (cnt) {
+                h_counts.reserve(nstreams);
+                hstage().h2d(h_counts.p, k.data(), nstreams * sizeof(unsigned long long), stream);
+            }
+        }
+        push_dev(h_bits.p, n_cap, n_cap, cnt ? h_counts.p : nullptr, h_out.p, oc, audio_out ? h_audio.p : nullptr, ac, stream);
+        const std::vector<unsigned long long>& k = fetch_counts();       // waits; checked against the bound
+        for (size_t c = 0; c < nstreams; c++) {
+            const size_t na = (size_t)k[c], no = (size_t)k[nstreams + c];
+            if (no) hstage().d2h(out + c * out_stride, h_out.p + c * oc, no * sizeof(cf), stream);
+            if (audio_out && na) hstage().d2h(audio_out + c * audio_stride, h_audio.p + c * ac, na * sizeof(float), stream);
+            if (n_out) n_out[c] = no;
+            if (n_audio) n_audio[c] = na;
+        }
+    });
+}
+const std::vector<unsigned long long>& FskTxMulti::fetch_counts() {
+    settle();
+    if (!fetched) {
+        fetched = true;                              // (a refused read-back is not repeated: the counts stay 0)
+        std::vector<unsigned long long> raw(2 * nstreams);
+        stage_download_sync(raw.data(), made.p, raw.size() * sizeof(unsigned long long), stream);
+        if (const char* e = fsk_multi_check_counts(raw.data(), nstreams, last_audio_cap, last_out_cap)) throw Error(e);
+        counts = raw;
+    }
+    return counts;
+}
+std::vector<FskStream> FskTxMulti::fetch_state() {
+    settle();
+    std::vector<FskStream> all(nstreams);
+    stage_download_sync(all.data(), st.in(), all.size() * sizeof(FskStream), stream);
+    return all;
 }
 
 }  // namespace rr

@@ -442,4 +442,38 @@ struct FskTx : BatchBlock {
     FskPush push_host(const unsigned char* bits, size_t n_bits, cf* out, size_t out_cap, float* audio, size_t audio_cap);
 };
 
+// FskTx x nstreams of one parameter set over ragged pushes of u8 line bits, the counts read on the device (kernels_tx.hip,
+// DESIGN.md 4.21): no stream protocol (work_dev is an error).  Every stream's FskPos and both its phases stay on the device; the
+// host keeps the geometry of the most recent push and the sum of all n_cap, an upper bound of every stream's bit position.
+struct FskTxMulti : BatchBlock {
+    size_t nstreams;
+    int mode;
+    FskRatio r1, r2;
+    float lo, hi, gain;
+    double k1, k2;
+    Carried<FskStream> st;                        // in(): what the streams so far left behind, one per stream
+    DevBuf<FskPush> plan;                         // the most recent push of every stream, as the device planned it
+    DevBuf<unsigned long long> made;              // [2][nstreams]: audio samples, then outputs, of every stream in it
+    DevBuf<unsigned> tilecnt;
+    DevBuf<double> tiles2, pre2;
+    DevBuf<float> audio;                          // a[] of a push that was given no d_audio
+    DevBuf<cf> val;
+    DevBuf<unsigned char> h_bits;                 // push_host(): the host buffers' device copies
+    DevBuf<unsigned long long> h_counts;
+    DevBuf<cf> h_out;
+    DevBuf<float> h_audio;
+    unsigned long long bits_bound = 0;            // the sum of the n_cap of all pushes
+    size_t last_audio_cap = 0, last_out_cap = 0;  // the bound of the most recent push
+    bool fetched = true;                          // `counts` holds the most recent push's
+    std::vector<unsigned long long> counts;       // [2][nstreams], checked against the bound
+    FskTxMulti(size_t nstreams, int mode, size_t interp1, size_t deci1, float lo, float hi, double k1, float gain, size_t interp2,
+               size_t deci2, double k2);
+    void push_dev(const unsigned char* d_bits, size_t bits_stride, size_t n_cap, const unsigned long long* d_counts, cf* d_out,
+                  size_t out_stride, float* d_audio, size_t audio_stride, hipStream_t s);
+    void push_host(const unsigned char* bits, size_t bits_stride, size_t n_cap, const size_t* counts, cf* out, size_t out_stride,
+                   float* audio, size_t audio_stride, size_t* n_out, size_t* n_audio);
+    const std::vector<unsigned long long>& fetch_counts();    // waits for the most recent push
+    std::vector<FskStream> fetch_state();                     // ... and downloads every stream's state
+};
+
 }  // namespace rr

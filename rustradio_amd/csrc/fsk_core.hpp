@@ -1,5 +1,5 @@
-// fsk_core.hpp — the index arithmetic of rr_fsk_tx (kernels_tx.hip) shared by kernels and host: plain functions,
-// no HIP types, so tests/cpp/test_fsk_hostlogic.cpp and emu_fsk.cpp compile them with g++.
+// fsk_core.hpp — the index arithmetic of rr_fsk_tx and rr_fsk_tx_multi (kernels_tx.hip) shared by kernels and
+// host: plain functions, no HIP types, so tests/cpp/test_fsk_hostlogic.cpp, emu_fsk.cpp and emu_fsk_multi.cpp compile them with g++.
 //
 // A RationalResampler (rational_resampler.rs:183-198) with the reduced ratio I : D is out[m] = in[floor(m D / I)] and has made
 // ceil(N I / D) outputs after N inputs.  Input i owns the outputs [first(i), first(i + 1)), first(i) = ceil(i I / D), and
@@ -86,6 +86,12 @@ RR_FSK_HD FskPush fsk_plan(const FskPos& p, const FskRatio& r1, const FskRatio& 
     u.next.e2 = fsk_next_e(r2, p.e2, u.na, u.no);
     return u;
 }
+// What one stream of rr_fsk_tx_multi carries between pushes, all of it on the device: where its two resamplers
+// stand and the two phases behind its last sample.  All zero at the start, as FskTx's FskPos and phases are.
+struct FskStream {
+    FskPos pos;
+    double ph[2];                             // phase 1, phase 2
+};
 // ---- the phase arithmetic (DESIGN.md 4.20 has the error account) -------------------------------------------------------------
 constexpr double FSK_MX = 2.0 * 3.14159265358979323846;   // vco.rs: 2.0 * f64::consts::PI
 

@@ -288,6 +288,36 @@ struct FskTxArgs {
     cf* out;
 };
 void launch_fsk_tx(const FskTxArgs& a, bool afsk, hipStream_t s);
+// ---- kernels_tx.hip: rr_fsk_tx_multi, the same chain for nstreams streams of one parameter set.  Stream c takes
+//      the next min(counts[c], n_cap) bits at bits + c * bits_stride (counts: device, may be null = n_cap each); its push is planned
+//      on the device from st_in[c] (fsk_plan) into plan[c], its next state goes to st_out[c] and what it made to made[c] (audio)
+//      and made[nstreams + c] (outputs).  Every kernel below the plan is a body of rr_fsk_tx's general path over the view of stream
+//      blockIdx.y.  Scratch per stream: tilecnt and tiles2 tpitch = ceil(audio_cap / FSK_T) entries, pre2 / val audio_cap entries;
+//      audio is the caller's (audio_stride) or scratch (audio_stride = audio_cap).  Launches: 6 (AFSK) or 5 (DIRECT) whatever the
+//      counts and nstreams are; n_cap == 0 launches nothing.
+struct FskTxMultiArgs {
+    const unsigned char* bits;
+    long bits_stride, n_cap, nstreams;
+    const unsigned long long* counts;
+    FskRatio r1, r2;
+    long map_dq, map_dr;
+    double dhi, dlo, k2;
+    float gain;
+    const FskStream* st_in;
+    FskStream* st_out;
+    FskPush* plan;
+    unsigned long long* made;
+    long audio_cap, out_cap, tpitch;
+    unsigned* tilecnt;
+    double* tiles2;
+    float* audio;
+    long audio_stride;
+    double* pre2;
+    cf* val;
+    cf* out;
+    long out_stride;
+};
+void launch_fsk_tx_multi(const FskTxMultiArgs& m, bool afsk, hipStream_t s);
 
 // ---- kernels_burst.hip: ComplexToMag2, SinglePoleIirFilter and the burst detector as a tiled f64 scan ------------------------
 // out[i] = (f32) y_i, y_i = a x_i + b y_(i-1) in f64 fma, y_(-1) = *y_in, i < n; *y_out <- y_(n-1).  y_in and y_out are distinct

@@ -27,6 +27,11 @@
 //                                         k_vco_scan, k_fsk_map                         k_fsk_map
 // and one fewer where no == 0 (every audio sample of the push is one the second resampler drops: k_fsk_map has nothing to do).
 // As above, no workgroup waits on another one and there is no atomic.
+//
+// rr_fsk_tx_multi: the same chain for nstreams streams of one parameter set, the counts of a push read on the
+// device.  k_fskm_plan plans every stream's push from the FskPos it carries; the five kernels of the na > FSK_T column run as
+// k_fskm_* over the view of stream blockIdx.y (the bodies are shared with the kernels above), always, since the host does not
+// know the counts: 6 launches in AFSK mode, 5 in DIRECT, whatever the counts, the bits and nstreams are; none for n_cap == 0.
 #include "kernels.hpp"
 #include "packet_common.hpp"
 
@@ -133,8 +138,8 @@ __global__ __launch_bounds__(VCO_B) void k_vco_sums(VcoSrc<FUSED> src, long n, d
 // tiles[i] <- carried phase + tiles[0] + ... + tiles[i - 1]; *carry_out <- carried phase + all of them.  One workgroup of
 // VCO_SB threads walks the tile sums in chunks of VCO_SB * 4 through LDS (coalesced both ways; 1e8 samples are 12 chunks).
 constexpr int VCO_SB = 1024, VCO_SPER = 4, VCO_SCHUNK = VCO_SB * VCO_SPER;
-__global__ __launch_bounds__(VCO_SB) void k_vco_scan(double* __restrict__ tiles, long ntiles, const double* __restrict__ carry_in,
-                                                     double* __restrict__ carry_out) {
+__device__ __forceinline__ void vco_scan_body(double* __restrict__ tiles, long ntiles, const double* __restrict__ carry_in,
+                                              double* __restrict__ carry_out) {
     __shared__ double s_t[VCO_SCHUNK];
     __shared__ double s_w[VCO_SB / 64];
     double base = carry_in[0];
@@ -157,6 +162,10 @@ __global__ __launch_bounds__(VCO_SB) void k_vco_scan(double* __restrict__ tiles,
         __syncthreads();                      // the next chunk overwrites s_t
     }
     if (threadIdx.x == 0) carry_out[0] = base;
+}
+__global__ __launch_bounds__(VCO_SB) void k_vco_scan(double* __restrict__ tiles, long ntiles, const double* __restrict__ carry_in,
+                                                     double* __restrict__ carry_out) {
+    vco_scan_body(tiles, ntiles, carry_in, carry_out);
 }
 
 // SINGLE: the window is one tile — base[0] is the carried phase and the kernel writes the phase carried out itself.
@@ -267,8 +276,11 @@ __device__ __forceinline__ unsigned fsk_ones8(const FskTxArgs& a, long m0, int c
     return mask;
 }
 
+// The kernels' bodies are device functions over one stream's FskTxArgs: rr_fsk_tx's kernels pass their own argument, rr_fsk_tx_multi's
+// the view of stream blockIdx.y (fskm_view below), the way hdlc_body.hpp serves k_hdlc_* and k_rx_*.  Tiles are taken from
+// blockIdx.x in steps of gridDim.x, so a workgroup whose tiles lie beyond the stream's own count does nothing.
 // the one-samples of every audio tile
-__global__ __launch_bounds__(FSK_B) void k_fsk_count(FskTxArgs a) {
+__device__ __forceinline__ void fsk_count_body(const FskTxArgs& a) {
     __shared__ unsigned s_w[FSK_B / 64];
     const long ntiles = (a.na + FSK_T - 1) / FSK_T;
     for (long tile = blockIdx.x; tile < ntiles; tile += (long)gridDim.x) {
@@ -280,10 +292,11 @@ __global__ __launch_bounds__(FSK_B) void k_fsk_count(FskTxArgs a) {
         if (threadIdx.x == 0) a.tilecnt[tile] = total;
     }
 }
+__global__ __launch_bounds__(FSK_B) void k_fsk_count(FskTxArgs a) { fsk_count_body(a); }
 
 // tilecnt[i] <- tilecnt[0] + ... + tilecnt[i - 1] (at most 2^30: the audio samples of a push).  One workgroup, chunks of
 // VCO_SCHUNK tiles, as k_vco_scan.
-__global__ __launch_bounds__(VCO_SB) void k_fsk_scan1(unsigned* __restrict__ tilecnt, long ntiles) {
+__device__ __forceinline__ void fsk_scan1_body(unsigned* __restrict__ tilecnt, long ntiles) {
     __shared__ unsigned s_w[VCO_SB / 64];
     unsigned base = 0;
     for (long c0 = 0; c0 < ntiles; c0 += VCO_SCHUNK) {
@@ -301,6 +314,7 @@ __global__ __launch_bounds__(VCO_SB) void k_fsk_scan1(unsigned* __restrict__ til
         base += total;
     }
 }
+__global__ __launch_bounds__(VCO_SB) void k_fsk_scan1(unsigned* __restrict__ tilecnt, long ntiles) { fsk_scan1_body(tilecnt, ntiles); }
 
 // Stage 1, and in AFSK mode the audio-rate half of stage 2.  Per audio sample m of the push: its phase from the count of
 // one-samples up to it (fsk_phase1), then
@@ -309,7 +323,7 @@ __global__ __launch_bounds__(VCO_SB) void k_fsk_scan1(unsigned* __restrict__ til
 //           (SINGLE: on top of the carried phase 2), and the tile's sum to tiles2[tile] (SINGLE: phase 2 carried out)
 // The thread that owns the push's last sample writes phase 1 carried out.
 template <bool AFSK, bool SINGLE>
-__global__ __launch_bounds__(FSK_B) void k_fsk_audio(FskTxArgs a) {
+__device__ __forceinline__ void fsk_audio_body(const FskTxArgs& a) {
     __shared__ unsigned s_c[FSK_B / 64];
     __shared__ double s_w[FSK_B / 64];
     const long ntiles = (a.na + FSK_T - 1) / FSK_T;
@@ -360,6 +374,8 @@ __global__ __launch_bounds__(FSK_B) void k_fsk_audio(FskTxArgs a) {
         }
     }
 }
+template <bool AFSK, bool SINGLE>
+__global__ __launch_bounds__(FSK_B) void k_fsk_audio(FskTxArgs a) { fsk_audio_body<AFSK, SINGLE>(a); }
 
 // The output-rate kernel: a map.  Output o of the push belongs to audio sample m = src2(o) and is the j-th of its run, j - 1 =
 // floor(rem / D2) with rem what the division left; thread t takes o = tile * FSK_OT + t + 256 i, so a wave's stores are one run
@@ -367,7 +383,7 @@ __global__ __launch_bounds__(FSK_B) void k_fsk_audio(FskTxArgs a) {
 //   DIRECT  out[o] = val[m]
 //   AFSK    out[o] = (sin, cos)(base + pre2[m] + j * (k2 * audio[m])), base = tiles2[m's tile] (SINGLE: pre2 holds it already)
 template <bool AFSK, bool SINGLE>
-__global__ __launch_bounds__(FSK_B) void k_fsk_map(FskTxArgs a) {
+__device__ __forceinline__ void fsk_map_body(const FskTxArgs& a) {
     const long ntiles = (a.no + FSK_OT - 1) / FSK_OT;
     for (long tile = blockIdx.x; tile < ntiles; tile += (long)gridDim.x) {
         const long o0 = tile * FSK_OT + threadIdx.x;
@@ -394,6 +410,8 @@ __global__ __launch_bounds__(FSK_B) void k_fsk_map(FskTxArgs a) {
         }
     }
 }
+template <bool AFSK, bool SINGLE>
+__global__ __launch_bounds__(FSK_B) void k_fsk_map(FskTxArgs a) { fsk_map_body<AFSK, SINGLE>(a); }
 
 template <bool AFSK> static void fsk_launch(const FskTxArgs& a, hipStream_t s) {
     const long ntiles = (a.na + FSK_T - 1) / FSK_T;
@@ -416,6 +434,82 @@ void launch_fsk_tx(const FskTxArgs& a, bool afsk, hipStream_t s) {
     if (a.na <= 0) return;
     if (afsk) fsk_launch<true>(a, s);
     else fsk_launch<false>(a, s);
+}
+
+// ---- rr_fsk_tx_multi: the general path above for nstreams streams, the stream from blockIdx.y -------------------
+// One thread per stream plans its push from the FskPos it carries and its clamped count, and writes what no later kernel of the
+// push writes: the plan, the next FskPos, the public counts and the phases that stay as they are (both where the push makes no
+// audio sample; phase 2 always in DIRECT mode).  Phase 1 of a stream with audio is k_fskm_audio's, its phase 2 k_fskm_scan2's.
+__global__ __launch_bounds__(FSK_B) void k_fskm_plan(FskTxMultiArgs m, int afsk) {
+    const long c = (long)blockIdx.x * FSK_B + threadIdx.x;
+    if (c >= m.nstreams) return;
+    unsigned long long k = m.counts ? m.counts[c] : (unsigned long long)m.n_cap;
+    if (k > (unsigned long long)m.n_cap) k = (unsigned long long)m.n_cap;
+    const FskStream st = m.st_in[c];
+    FskPush u = fsk_plan(st.pos, m.r1, m.r2, (long)k);
+    // (residues in [0, D) keep a push inside the bound; a state that is not such a one takes nothing rather than write beyond it)
+    if (u.no < 0 || u.na > m.audio_cap || u.no > m.out_cap) u = fsk_plan(st.pos, m.r1, m.r2, 0);
+    m.plan[c] = u;
+    m.st_out[c].pos = u.next;
+    if (u.na == 0) m.st_out[c].ph[0] = st.ph[0];
+    if (u.na == 0 || !afsk) m.st_out[c].ph[1] = st.ph[1];
+    m.made[c] = (unsigned long long)u.na;
+    m.made[m.nstreams + c] = (unsigned long long)u.no;
+}
+// stream c of the push as rr_fsk_tx's kernels see one push: indices relative to the stream's own push start, so nothing below
+// depends on n_cap, the strides, nstreams or another stream
+__device__ __forceinline__ FskTxArgs fskm_view(const FskTxMultiArgs& m, long c) {
+    const FskPush* u = m.plan + c;
+    FskTxArgs a;
+    a.bits = m.bits + c * m.bits_stride;
+    a.n = u->n; a.na = u->na; a.no = u->no;
+    a.r1 = m.r1; a.r2 = m.r2;
+    a.e1 = u->e1; a.e2 = u->e2;
+    a.map_dq = m.map_dq; a.map_dr = m.map_dr;
+    a.dhi = m.dhi; a.dlo = m.dlo; a.k2 = m.k2;
+    a.gain = m.gain;
+    a.carry_in = m.st_in[c].ph;
+    a.carry_out = m.st_out[c].ph;
+    a.tilecnt = m.tilecnt + c * m.tpitch;
+    a.tiles2 = m.tiles2 + c * m.tpitch;
+    a.audio = m.audio + c * m.audio_stride;
+    a.pre2 = m.pre2 + c * m.audio_cap;
+    a.val = m.val + c * m.audio_cap;
+    a.out = m.out + c * m.out_stride;
+    return a;
+}
+__global__ __launch_bounds__(FSK_B) void k_fskm_count(FskTxMultiArgs m) { fsk_count_body(fskm_view(m, blockIdx.y)); }
+__global__ __launch_bounds__(VCO_SB) void k_fskm_scan1(FskTxMultiArgs m) {
+    const FskTxArgs a = fskm_view(m, blockIdx.y);
+    fsk_scan1_body(a.tilecnt, (a.na + FSK_T - 1) / FSK_T);
+}
+template <bool AFSK> __global__ __launch_bounds__(FSK_B) void k_fskm_audio(FskTxMultiArgs m) {
+    fsk_audio_body<AFSK, false>(fskm_view(m, blockIdx.y));
+}
+__global__ __launch_bounds__(VCO_SB) void k_fskm_scan2(FskTxMultiArgs m) {
+    const FskTxArgs a = fskm_view(m, blockIdx.y);
+    if (a.na <= 0) return;                    // (the plan kernel carried this stream's phase 2 over)
+    vco_scan_body(a.tiles2, (a.na + FSK_T - 1) / FSK_T, a.carry_in + 1, a.carry_out + 1);
+}
+template <bool AFSK> __global__ __launch_bounds__(FSK_B) void k_fskm_map(FskTxMultiArgs m) {
+    fsk_map_body<AFSK, false>(fskm_view(m, blockIdx.y));
+}
+
+template <bool AFSK> static void fskm_launch(const FskTxMultiArgs& m, hipStream_t s) {
+    const unsigned ns = (unsigned)m.nstreams;
+    const dim3 ga(tiles_grid(m.tpitch), ns), go(tiles_grid((m.out_cap + FSK_OT - 1) / FSK_OT), ns), one(1, ns);
+    hipLaunchKernelGGL(k_fskm_plan, dim3((ns + FSK_B - 1) / FSK_B), dim3(FSK_B), 0, s, m, AFSK ? 1 : 0);
+    hipLaunchKernelGGL(k_fskm_count, ga, dim3(FSK_B), 0, s, m);
+    hipLaunchKernelGGL(k_fskm_scan1, one, dim3(VCO_SB), 0, s, m);
+    hipLaunchKernelGGL((k_fskm_audio<AFSK>), ga, dim3(FSK_B), 0, s, m);
+    if (AFSK) hipLaunchKernelGGL(k_fskm_scan2, one, dim3(VCO_SB), 0, s, m);
+    hipLaunchKernelGGL((k_fskm_map<AFSK>), go, dim3(FSK_B), 0, s, m);
+    RR_HIP(hipGetLastError());
+}
+void launch_fsk_tx_multi(const FskTxMultiArgs& m, bool afsk, hipStream_t s) {
+    if (m.n_cap <= 0 || m.nstreams <= 0) return;
+    if (afsk) fskm_launch<true>(m, s);
+    else fskm_launch<false>(m, s);
 }
 
 }  // namespace rr

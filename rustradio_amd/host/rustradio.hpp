@@ -1305,6 +1305,87 @@ public:
     size_t scan_chunk_tiles() const { size_t a = 0, o = 0, c = 0; if (rr_fsk_tx_dims(h_.h, &a, &o, &c) != 0) throw Error(rr_last_error()); return c; }
 };
 
+// ---- FskTxMulti: FskTx x nstreams of one parameter set behind one handle, the counts of a push read on the device ------------------
+// (rr_fsk_tx_multi_create / _bound / _push / _push_dev / _counts / _counts_dev / _positions / _dims).  push() takes one row of
+// line bits per stream, of which stream c holds counts[c], and returns what each stream made.
+class FskTxMulti {
+    detail::Handle h_;
+    size_t nstreams_;
+public:
+    struct Pushed {
+        std::vector<std::vector<Complex>> out;    // per stream
+        std::vector<std::vector<float>> audio;    // AFSK mode with audio asked for
+    };
+    FskTxMulti(size_t nstreams, int mode, size_t interp1, size_t deci1, float lo, float hi, double k1, float gain, size_t interp2 = 1,
+               size_t deci2 = 1, double k2 = 0.0)
+        : h_(rr_fsk_tx_multi_create(nstreams, mode, interp1, deci1, lo, hi, detail::f64_bits(k1), gain, interp2, deci2,
+                                    detail::f64_bits(k2))),
+          nstreams_(nstreams) {}
+    rr_block* handle() const { return h_.h; }
+    size_t nstreams() const { return nstreams_; }
+    // (audio_cap, out_cap): the most one stream makes from n_cap bits
+    std::pair<size_t, size_t> bound(size_t n_cap) const {
+        size_t a = 0, o = 0;
+        if (rr_fsk_tx_multi_bound(h_.h, n_cap, &a, &o) != 0) throw Error(rr_last_error());
+        return {a, o};
+    }
+    // rows: nstreams rows of one length n_cap; counts: empty (n_cap each) or one per stream
+    Pushed push(const std::vector<std::vector<unsigned char>>& rows, const std::vector<size_t>& counts = {}, bool want_audio = false) {
+        if (rows.size() != nstreams_) throw Error("FskTxMulti: one row per stream");
+        if (!counts.empty() && counts.size() != nstreams_) throw Error("FskTxMulti: one count per stream");
+        const size_t n = rows[0].size();
+        std::vector<unsigned char> bits(nstreams_ * n + 1);
+        for (size_t c = 0; c < nstreams_; c++) {
+            if (rows[c].size() != n) throw Error("FskTxMulti: rows of one length");
+            std::copy(rows[c].begin(), rows[c].end(), bits.begin() + (long)(c * n));
+        }
+        const auto [ac, oc] = bound(n);
+        std::vector<Complex> out(nstreams_ * oc + 1);
+        std::vector<float> audio(want_audio ? nstreams_ * ac + 1 : 0);
+        std::vector<size_t> no(nstreams_), na(nstreams_);
+        if (rr_fsk_tx_multi_push(h_.h, bits.data(), n, n, counts.empty() ? nullptr : counts.data(), reinterpret_cast<rr_c32*>(out.data()),
+                                 oc, want_audio ? audio.data() : nullptr, want_audio ? ac : 0, no.data(), na.data()) != 0)
+            throw Error(rr_last_error());
+        Pushed p;
+        p.out.resize(nstreams_);
+        if (want_audio) p.audio.resize(nstreams_);
+        for (size_t c = 0; c < nstreams_; c++) {
+            p.out[c].assign(out.begin() + (long)(c * oc), out.begin() + (long)(c * oc + std::min(no[c], oc)));
+            if (want_audio) p.audio[c].assign(audio.begin() + (long)(c * ac), audio.begin() + (long)(c * ac + std::min(na[c], ac)));
+        }
+        return p;
+    }
+    // device pointers; d_counts: unsigned long long[nstreams] on the device or nullptr; asynchronous on hip_stream
+    void push_dev(const void* d_bits, size_t bits_stride, size_t n_cap, const void* d_counts, void* d_out, size_t out_stride,
+                  void* d_audio = nullptr, size_t audio_stride = 0, void* hip_stream = nullptr) {
+        if (rr_fsk_tx_multi_push_dev(h_.h, d_bits, bits_stride, n_cap, d_counts, d_out, out_stride, d_audio, audio_stride, hip_stream) != 0)
+            throw Error(rr_last_error());
+    }
+    // (n_audio, n_out) of each stream in the most recent push; waits for it
+    std::vector<std::pair<size_t, size_t>> counts() {
+        std::vector<size_t> a(nstreams_), o(nstreams_);
+        size_t total = 0;
+        if (rr_fsk_tx_multi_counts(h_.h, a.data(), o.data(), nstreams_, &total) != 0) throw Error(rr_last_error());
+        std::vector<std::pair<size_t, size_t>> k(std::min(total, nstreams_));
+        for (size_t c = 0; c < k.size(); c++) k[c] = {a[c], o[c]};
+        return k;
+    }
+    const void* counts_dev() { return rr_fsk_tx_multi_counts_dev(h_.h); }
+    // bits taken, audio samples and outputs made by stream c so far; waits
+    struct Position { unsigned long long bits, audio, out; };
+    std::vector<Position> positions() {
+        std::vector<unsigned long long> b(nstreams_), a(nstreams_), o(nstreams_);
+        size_t total = 0;
+        if (rr_fsk_tx_multi_positions(h_.h, b.data(), a.data(), o.data(), nstreams_, &total) != 0) throw Error(rr_last_error());
+        std::vector<Position> p(std::min(total, nstreams_));
+        for (size_t c = 0; c < p.size(); c++) p[c] = {b[c], a[c], o[c]};
+        return p;
+    }
+    size_t audio_tile() const { size_t a = 0, o = 0, c = 0; if (rr_fsk_tx_multi_dims(h_.h, &a, &o, &c) != 0) throw Error(rr_last_error()); return a; }
+    size_t out_tile() const { size_t a = 0, o = 0, c = 0; if (rr_fsk_tx_multi_dims(h_.h, &a, &o, &c) != 0) throw Error(rr_last_error()); return o; }
+    size_t scan_chunk_tiles() const { size_t a = 0, o = 0, c = 0; if (rr_fsk_tx_multi_dims(h_.h, &a, &o, &c) != 0) throw Error(rr_last_error()); return c; }
+};
+
 class Vco : public SyncBlock<Float, Complex> {
 public:
     using SyncBlock<Float, Complex>::SyncBlock;
