@@ -3,7 +3,9 @@
 //   the composition table of the four maps (associativity, identity, agreement with applying one map after the other);
 //   EVERY string of the four sample classes up to EXH_LEN samples, whole and cut in two at every point, under tiny settings
 //   (short 1, long 2 or 3, tolerance 0 and 1, frame gap 2, reset gap 2 and 3, both gap modes);
-//   drawn pulse trains over several tiles in random pushes, pushes of one sample included, with a flush at the end.
+//   drawn pulse trains over several tiles in random pushes, pushes of one sample included, with a flush at the end;
+//   drawn transmissions of hundreds of frames of up to 70 bits against a table of 100 rows, cut at random and on every tile seam,
+//   so pwm_step's order of find, append and turn away holds where the table is larger than one wave of the walk.
 // Frames are compared exactly (bits, repeats, first_sample, order, and the push they are delivered in); so is the carried state.
 #include <cmath>
 #include <cstdio>
@@ -17,6 +19,7 @@ using namespace rr;
 
 static int fails = 0;
 static long delivered = 0, repeated = 0;     // frames the reference delivered in all comparisons; those with repeats > 1
+static size_t max_carried = 0, max_open = 0; // the most candidates, and the longest open frame, that a push left to the next
 #define CHECK(c, ...) do { if (!(c)) { if (fails++ < 20) { std::printf("FAIL %s:%d: %s — ", __FILE__, __LINE__, #c); std::printf(__VA_ARGS__); std::printf("\n"); } } } while (0)
 
 // the device side of a handle: what it carries, and the kernels' work of one push
@@ -135,6 +138,8 @@ static void compare(const PwmCfg& c, const std::vector<float>& x, const std::vec
             CHECK(emu.st.fcount == ref.bits.size() && !emu.st.finvalid && emu.st.has_start && emu.st.fstart == ref.frame_start,
                   "%s: carried frame behind %zu", what, end);
         CHECK(emu.meta.size() == ref.candidates.size(), "%s: carried candidates behind %zu", what, end);
+        max_carried = std::max(max_carried, ref.candidates.size());
+        max_open = std::max(max_open, ref.bits.size());
         at = end;
     }
     std::vector<PwmHostFrame> a, b;
@@ -199,6 +204,41 @@ int main(int argc, char** argv) {
         for (size_t seam : {(size_t)PWM_T - 1, (size_t)PWM_T, (size_t)PWM_T + 1}) compare(c, x, {seam}, "drawn, cut at a tile seam");
         runs += 5;
     }
+    // ---- drawn transmissions against a table of 100 rows: a pool of 140 words, most of 1 .. 12 bits, a quarter of 1 .. 71 (one more
+    // than max_frame_bits), 260 frames a transmission, so the table fills and turns words away; some 7,000 pulses a round
+    for (int round = 0; round < 4; round++) {
+        const bool delim = round & 1;
+        const PwmCfg c = pwm_cfg(0.5f, 0.25f, 1, 3, (round >> 1) & 1, 5, 12, 0, 70, 100, 1 + round % 2,
+                                 (delim ? RR_PWM_GAP_DELIMITER : 0) | (round & 2 ? RR_PWM_SHORT_IS_ZERO : 0));
+        std::vector<std::vector<unsigned char>> pool(140);
+        for (auto& wd : pool) {
+            wd.resize(rng() % 4 == 0 ? 1 + (size_t)(rng() % 71) : 1 + (size_t)(rng() % 12));
+            for (auto& b : wd) b = (unsigned char)(rng() % 2);
+        }
+        std::vector<float> x;
+        auto run = [&](bool high, size_t count) {          // (inside the band behind the run's first sample only: the widths stand)
+            for (size_t i = 0; i < count; i++) x.push_back(high ? (i && rng() % 9 == 0 ? 0.3f : 1.0f) : (i && rng() % 9 == 0 ? 0.4f : 0.0f));
+        };
+        for (int tx = 0; tx < 2; tx++) {
+            for (int f = 0; f < 260; f++) {
+                for (unsigned char b : pool[rng() % pool.size()]) {
+                    run(true, rng() % 50 == 0 ? 2 : b ? 1 : 3);      // a width of 2: the tie under tolerance 1, invalid under 0
+                    run(false, 1 + (size_t)(rng() % 4));
+                }
+                if (delim) run(true, 1);
+                run(false, f == 259 ? 12 + (size_t)(rng() % 3) : 5 + (size_t)(rng() % 7));
+            }
+        }
+        compare(c, x, {}, "table of 100, whole");
+        std::vector<size_t> cuts, seams, beside;
+        for (size_t at = 0; at < x.size();) { at += 1 + (size_t)(rng() % (round % 2 ? 40 : 3000)); if (at < x.size()) cuts.push_back(at); }
+        compare(c, x, cuts, "table of 100, cut");
+        for (size_t at = PWM_T; at + 1 < x.size(); at += PWM_T) { seams.push_back(at); beside.push_back(at - 1); beside.push_back(at + 1); }
+        compare(c, x, seams, "table of 100, cut on every tile seam");
+        compare(c, x, beside, "table of 100, cut beside every tile seam");
+        runs += 4;
+    }
+    CHECK(max_carried == 100 && max_open > 64, "a full table of 100 and an open frame past 64 bits are carried: %zu, %zu", max_carried, max_open);
     CHECK(delivered > 10000 && repeated > 100, "the comparisons deliver frames: %ld, %ld repeated", delivered, repeated);
     if (fails) { std::printf("%d failures\n", fails); return 1; }
     std::printf("%ld comparisons, %ld frames delivered, %ld of them repeated\npwm core ok\n", runs, delivered, repeated);

@@ -1,7 +1,7 @@
 """GPU: rr_pwm_decoder (kernels_pwm.hip) against the sequential model of tests/pwm_model.py.  Every comparison is exact: the bits,
 `repeats`, `first_sample` and the order of the frames, and the push that delivers them; there is no tolerance anywhere in this file.
 
-A Pair is a handle and a PwmModel fed the same samples, so the expectation follows the handle whatever came before: a stream that
+A Pair (tests/pwm_streams.py) is a handle and a PwmModel fed the same samples, so the expectation follows the handle whatever came before: a stream that
 ends in reset_gap of silence leaves both with no pulse, no frame and no candidate, and the next stream starts clean."""
 import numpy as np
 import pytest
@@ -9,6 +9,7 @@ import torch
 
 import pwm_model as pm
 import rustradio_amd as rr
+from pwm_streams import BASE, FGAP, LONG, RGAP, SHORT, Pair, frames_of, runs, word
 
 pytestmark = pytest.mark.gpu
 DOC = pm.load_known_answers()
@@ -16,62 +17,6 @@ DOC = pm.load_known_answers()
 
 def launches():
     return rr.lib().rr_debug_kernel_launches()
-
-
-def frames_of(result):
-    return [(tuple(int(b) for b in bits), repeats, first) for bits, repeats, first in result]
-
-
-class Pair:
-    def __init__(self, pos, kw, dtype=np.float32):
-        self.dev = rr.PwmDecoder(*pos, **kw, dtype=dtype)
-        self.model = pm.PwmModel(*pos, **kw)
-        self.pos, self.kw = pos, kw
-
-    def feed(self, x, via="push"):
-        """the next samples through both -> the frames delivered, asserted equal"""
-        x = np.ascontiguousarray(x, np.float32)
-        want = self.model.push(x)
-        if via == "push":
-            got = frames_of(self.dev.push(x))
-        else:
-            t = torch.from_numpy(x).cuda()
-            self.dev.push_dev(t.data_ptr() if len(x) else 0, len(x))
-            got = frames_of(self.dev.result())
-        assert got == want, (len(x), got[:3], want[:3])
-        return got
-
-    def feed_cut(self, x, cuts):
-        out, at = [], 0
-        for c in list(cuts) + [len(x)]:
-            out.append(self.feed(x[at:c]))
-            at = c
-        return out
-
-    def flush(self):
-        got, want = frames_of(self.dev.flush()), self.model.flush()
-        assert got == want
-        return got
-
-
-def runs(*pairs):
-    """(high, count) runs -> f32 samples, 1.0 and 0.0"""
-    return np.concatenate([np.full(c, 1.0 if h else 0.0, np.float32) for h, c in pairs] or [np.zeros(0, np.float32)])
-
-
-SHORT, LONG, FGAP, RGAP = 2, 5, 9, 20
-BASE = ([0.5, SHORT, LONG, FGAP, RGAP], dict(low_threshold=0.25, pulse_tolerance=1, max_frame_bits=16, max_distinct_frames=4))
-
-
-def word(bits, gap=FGAP, delimiter=False):
-    """add_frame (src/pwm_decoder.rs:702-712) with the gap behind it"""
-    r = []
-    for b in bits:
-        r += [(True, SHORT if b else LONG), (False, LONG if b else SHORT)]
-    if delimiter:
-        r.append((True, SHORT))
-    r.append((False, gap))
-    return r
 
 
 @pytest.fixture(scope="module")
