@@ -1290,6 +1290,24 @@ static bool chain_nf_wanted(bool u8, int64_t, int64_t, size_t) {
 static void reversed_taps(const rr_c32* t, size_t L, cf* dst) {
     for (size_t j = 0; j < L; j++) dst[j] = mkcf(t[L - 1 - j].re, t[L - 1 - j].im);
 }
+static std::vector<float> reversed_taps(const float* t, size_t L) {
+    return std::vector<float>(std::make_reverse_iterator(t + L), std::make_reverse_iterator(t));
+}
+// real taps as the Complex filter takes them (fft_filter.rs:398)
+static std::vector<rr_c32> widened_taps(const float* t, size_t L) {
+    std::vector<rr_c32> ct(L);
+    for (size_t i = 0; i < L; i++) ct[i] = rr_c32{t[i], 0.0f};
+    return ct;
+}
+// exp(-2 pi i k / FH), k < FH: the twiddles of the half-size inverse transforms
+static void upload_half_twiddles(DevBuf<cf>& d, size_t FH, hipStream_t s) {
+    std::vector<cf> th(FH);
+    for (size_t k = 0; k < FH; k++) {
+        const double a = -2.0 * 3.14159265358979323846 * (double)k / (double)FH;
+        th[k] = mkcf((float)std::cos(a), (float)std::sin(a));
+    }
+    d.upload(th.data(), th.size(), s);
+}
 // outputs (r positions) of the smallest tile a chain kernel of this call may have run on: P_y filtered samples hold at least
 // floor(P_y I / D) of them
 // (the chain kernels advance by fm_advance((F - L + 1) - ceil(D / I)), which rounds down to whole epilogue rounds but never
@@ -1318,12 +1336,13 @@ FmChain::FmChain(const rr_c32* taps, size_t ntaps, size_t interp, size_t deci, f
         const size_t Lc = fir_taps ? fir_ntaps + ntaps - 1 : ntaps, lim = ((size_t)1 << std::min(max_log2f, 14)) - 1;
         if (ntaps && Lc > lim) throw NotFusedShape("FmChain: more taps than the largest tile of the fused kernels holds");
     }
+    std::vector<rr_c32> gt;
     if (fir_taps) {                      // front FirFilter fused in: composite taps, head fix at stream start
         if (u8) throw Error("FmChain: the front FirFilter takes Complex input");
-        const std::vector<rr_c32> gt = FftFilter::composite(fir_taps, fir_ntaps, taps, ntaps);
+        gt = FftFilter::composite(fir_taps, fir_ntaps, taps, ntaps);
         f.reset(new FftFilter(gt.data(), gt.size(), true, max_log2f, false, fir_ntaps - 1));
         f->set_stage_taps(fir_taps, fir_ntaps, taps, ntaps);
-        ntaps = gt.size();
+        taps = gt.data(); ntaps = gt.size();         // every table below is built from the f->L composite taps
     } else {
         f.reset(new FftFilter(taps, ntaps, true, max_log2f));
     }
@@ -1331,15 +1350,7 @@ FmChain::FmChain(const rr_c32* taps, size_t ntaps, size_t interp, size_t deci, f
     const int64_t G = (D + I - 1) / I;
     if (G >= (int64_t)(((size_t)1 << f->log2f) - f->L + 1)) throw NotFusedShape("FmChain: decimation too large for the FFT tile");
     half_ok = !f->nsub && fm_multi_half_supported(f->log2f, I, D, (int)ntaps) && !build_opts().fm_full;
-    if (half_ok) {
-        const size_t FH = ((size_t)1 << f->log2f) / 2;
-        std::vector<cf> th(FH);
-        for (size_t k = 0; k < FH; k++) {
-            const double a = -2.0 * 3.14159265358979323846 * (double)k / (double)FH;
-            th[k] = mkcf((float)std::cos(a), (float)std::sin(a));
-        }
-        d_tw_half.upload(th.data(), th.size(), stream);
-    }
+    if (half_ok) upload_half_twiddles(d_tw_half, ((size_t)1 << f->log2f) / 2, stream);
     // decimate-first tiles: D phase transforms + one inverse per 1024 OUTPUT-rate positions (kernels_poly.hip).  Where they
     // win (tools/poly_probe.py on MI355X, ms per 2.4e7 samples, poly / best other kernel): 463 taps 1:2 0.084 / 0.102, 1:4
     // 0.065 / 0.087, 1:6 0.067 / 0.085, 1:7 0.083 / 0.095, 1:8 0.096 / 0.083; 2467 taps 1:6 0.086 / 0.157, 1:10 0.113 / 0.152,
@@ -1360,19 +1371,13 @@ FmChain::FmChain(const rr_c32* taps, size_t ntaps, size_t interp, size_t deci, f
     // (1:2 wins up to 500 taps per phase — 1000 taps 0.122 / 0.126, 1300 taps 0.159 / 0.141 — and 1:3 up to 600)
     const bool poly_wins = d_wins && Lsp <= (D == 2 ? 500u : D == 3 ? 600u : 768u);
     if ((build_opts().fm_poly > 0 || (build_opts().fm_poly == 0 && poly_wins)) && !build_opts().fm_full && I == 1 && D >= 2) {
-        std::vector<rr_c32> ct(f->L);
-        if (fir_taps) ct = FftFilter::composite(fir_taps, fir_ntaps, taps, f->L - (fir_ntaps - 1));
-        else std::copy(taps, taps + f->L, ct.begin());
         poly.reset(new PolyTables());
-        if (!poly->build(ct.data(), 1, f->L, (size_t)D, false, stream)) poly.reset();
+        if (!poly->build(taps, 1, f->L, (size_t)D, false, stream)) poly.reset();
     }
     for (auto& b : last_r) { b.reserve(1); RR_HIP(hipMemsetAsync(b.p, 0, sizeof(cf), stream)); }
     if (chain_nf_wanted(u8, I, D, f->nsamples)) {
-        std::vector<rr_c32> ct(f->L);
-        if (fir_taps) ct = FftFilter::composite(fir_taps, fir_ntaps, taps, f->L - (fir_ntaps - 1));
-        else std::copy(taps, taps + f->L, ct.begin());
         std::vector<cf> r(f->L);
-        reversed_taps(ct.data(), f->L, r.data());
+        reversed_taps(taps, f->L, r.data());
         nf.rev_c.upload(r.data(), r.size(), stream);
         nf.init(stream);
     }
@@ -1388,56 +1393,48 @@ size_t OutTail::drain(float* out, size_t out_stride, size_t out_cap, size_t C, h
     return m;
 }
 
-size_t FmChain::next_block_outputs() const {
-    auto N3 = [&](uint64_t y) { const uint64_t r = (uint64_t)(((__int128)y * I + D - 1) / D); return r ? r - 1 : 0; };
-    return (size_t)(N3(n1 + f->nsamples) - N3(n1));
-}
+static_assert(CHAIN_WAIT_SRC == RR_WAIT_SRC && CHAIN_WAIT_DST == RR_WAIT_DST, "chain_core.hpp restates the ABI's two waits");
 
-int FmChain::work_blocks(const void* in, size_t in_len, float* out, size_t, size_t out_cap, size_t* consumed,
-                         size_t* produced, size_t* need, hipStream_t s, uint64_t max_blocks) {
-    *consumed = *produced = *need = 0;
-    if (iq8) in_len /= 2;                          // whole I/Q pairs; an odd trailing byte is never consumed (:23)
-    bool packed = iq8;
-    if (iq8 && ((uintptr_t)in & 1)) {              // odd-addressed byte window: decode out of line
+// RTL-SDR byte windows of FmChain and FmMulti: whole I/Q pairs (an odd trailing byte is never consumed, rtlsdr_decode.rs:23), an
+// odd-addressed window decoded out of line into `decoded`; on the way out `consumed` and a WAIT_SRC `need` count bytes again.
+struct ByteSrc {
+    bool iq8, packed;
+    ByteSrc(bool u8, const void*& in, size_t& in_len, DevBuf<cf>& decoded, hipStream_t s) : iq8(u8), packed(u8) {
+        if (iq8) in_len /= 2;
+        if (!iq8 || !((uintptr_t)in & 1)) return;
         decoded.reserve(std::max<size_t>(in_len, 1));
         launch_rtlsdr_decode(static_cast<const unsigned char*>(in), decoded.p, (long)in_len, s);
         in = decoded.p;
         packed = false;
     }
-    const uint64_t S = f->nsamples;
-    auto N2 = [&](uint64_t y) { return (uint64_t)(((__int128)y * I + D - 1) / D); };
-    auto N3 = [&](uint64_t y) { const uint64_t r = N2(y); return r ? r - 1 : 0; };
-    const uint64_t o_old = N3(n1);
-    // like FftFilter::work (fft_filter.rs:294-303): room for one block's worth of output first
-    const uint64_t need_next = N3(n1 + S) - o_old;
-    if (need_next > out_cap) { *need = need_next; return RR_WAIT_DST; }
-    if (f->front && in_len < f->front + 1) { *need = f->front + 1; return RR_WAIT_SRC; }   // front FirFilter: fir.rs:498-501
-    const uint64_t av = f->avail(in_len);
-    const uint64_t total = f->pend_len + av;
-    const uint64_t k_in = total / S;
-    // largest k with N3(n1 + k S) - o_old <= out_cap  <=>  ceil((n1+kS) I / D) <= o_old + out_cap + 1
-    const __int128 X = (__int128)(o_old + out_cap + 1) * D / I;        // (n1 + k S) <= X
-    uint64_t k_out = X >= (__int128)n1 ? (uint64_t)((X - n1) / S) : 0;
-    while (k_out > 0 && N3(n1 + k_out * S) - o_old > out_cap) k_out--;
-    k_out = std::min(k_out, max_blocks);
-    uint64_t k, new_pend;
-    int st;
-    if (k_in > k_out) {
-        k = k_out; *consumed = k * S - f->pend_len; new_pend = 0;
-        st = RR_WAIT_DST; *need = N3(n1 + (k + 1) * S) - N3(n1 + k * S);
-    } else {
-        k = k_in; *consumed = av; new_pend = total - k * S;
-        st = RR_WAIT_SRC; *need = S - new_pend + f->front;
+    int done(int st, size_t* consumed, size_t* need) const {
+        if (iq8) { *consumed *= 2; if (st == RR_WAIT_SRC) *need *= 2; }
+        return st;
     }
-    const uint64_t n_y = k * S;
+};
+// the kernel arguments of a planned call that runs blocks (p.k > 0)
+static FmChainArgs fm_args(const ChainShape& c, const ChainPlan& p, const FmChain& ch) {
+    FmChainArgs a;
+    a.A = (long)ch.n1; a.n_y = (long)p.n_y; a.r_lo = (long)p.r_lo; a.r_hi = (long)p.r_hi; a.o_base = (long)p.o_old;
+    a.I = c.I; a.D = c.D; a.gain = ch.gain; a.mode = ch.mode; a.carry = ch.f->carry_out(p);
+    return a;
+}
+
+int FmChain::work_blocks(const void* in, size_t in_len, float* out, size_t, size_t out_cap, size_t* consumed,
+                         size_t* produced, size_t* need, hipStream_t s, uint64_t max_blocks) {
+    *consumed = *produced = *need = 0;
+    const ByteSrc bytes(iq8, in, in_len, decoded, s);
+    const bool packed = bytes.packed;
+    const ChainShape c = shape();
+    const ChainPlan p = chain_plan(c, n1, f->pend_len, in_len, out_cap, max_blocks);
+    *need = p.need;
+    if (p.early) return p.status;
+    const uint64_t S = c.S, n_y = p.n_y;
     const long plen = (long)(f->hist + f->pend_len);
     VSrc<cf> src{f->prefix[f->cur].p, plen, static_cast<const cf*>(in), (long)in_len};
     VSrcIQ8 src8{f->prefix[f->cur].p, plen, static_cast<const rr::iq8*>(in), (long)in_len};
-    if (k) {
-        FmChainArgs a;
-        a.A = (long)n1; a.n_y = (long)n_y; a.r_lo = (long)N2(n1); a.r_hi = (long)N2(n1 + n_y);
-        a.o_base = (long)o_old; a.I = I; a.D = D; a.gain = gain; a.mode = mode;
-        if (*consumed) a.carry = CarryOut{f->prefix[f->cur ^ 1].p, (long)n_y, (long)(f->hist + new_pend)};   // (see FftFilter::work_dev)
+    if (p.k) {
+        const FmChainArgs a = fm_args(c, p, *this);
         // decimate-first tiles cover D x 946 inputs each: below one tile per resident workgroup slot (~6 M samples at 1:6)
         // the 2048-point tiles keep more of the chip busy (tools/call_overhead.py, 463 taps 1:6, 512 k samples: 21.7 us
         // decimate-first, 15.4-18.8 us on the 2048-point tiles; 8 M samples: 32.9 against 35.1).  All kernels share the
@@ -1513,21 +1510,14 @@ int FmChain::work_blocks(const void* in, size_t in_len, float* out, size_t, size
             nf.seq++;
         }
         if (a.r_hi > a.r_lo) cur_lr ^= 1;
-    } else if (*consumed) {                        // nothing to filter yet: the window only joins the pending samples
-        if (packed) launch_vcopy_iq8(src8, (long)n_y, f->prefix[f->cur ^ 1].p, (long)(f->hist + new_pend), s);
-        else launch_vcopy_c32(src, (long)n_y, f->prefix[f->cur ^ 1].p, (long)(f->hist + new_pend), s);
+    } else if (p.consumed) {                       // nothing to filter yet: the window only joins the pending samples
+        if (packed) launch_vcopy_iq8(src8, (long)n_y, f->prefix[f->cur ^ 1].p, (long)(f->hist + p.new_pend), s);
+        else launch_vcopy_c32(src, (long)n_y, f->prefix[f->cur ^ 1].p, (long)(f->hist + p.new_pend), s);
     }
-    if (*consumed) {
-        f->cur ^= 1;
-        f->pend_len = new_pend;
-    }
-    *produced = N3(n1 + n_y) - o_old;
+    f->commit(p);
+    *consumed = p.consumed; *produced = p.produced;
     n1 += n_y;
-    if (iq8) {                                     // the input stream counts bytes
-        *consumed *= 2;
-        if (st == RR_WAIT_SRC) *need *= 2;
-    }
-    return st;
+    return bytes.done(p.status, consumed, need);
 }
 
 // ---- fused audio stage: FftFilterFloat -> RationalResampler -> MultiplyConst --------------------------------------------
@@ -1540,12 +1530,9 @@ AudioChain::AudioChain(const float* taps, size_t ntaps, size_t interp, size_t de
     if (ntaps > 3584) throw NotFusedShape("AudioChain: at most 3584 taps (real-stream tiles of up to 4096 points); use the three blocks");
     const int64_t gg = gcd64((int64_t)deci, (int64_t)interp);
     D = (int64_t)deci / gg; I = (int64_t)interp / gg;
-    std::vector<rr_c32> ct(ntaps);
-    for (size_t i = 0; i < ntaps; i++) ct[i] = rr_c32{taps[i], 0.0f};  // fft_filter.rs:398
-    f.reset(new FftFilter(ct.data(), ntaps, false, 12, true));
+    f.reset(new FftFilter(widened_taps(taps, ntaps).data(), ntaps, false, 12, true));
     if (chain_nf_wanted(false, I, D, f->nsamples)) {
-        std::vector<float> r(ntaps);
-        for (size_t j = 0; j < ntaps; j++) r[j] = taps[ntaps - 1 - j];
+        const std::vector<float> r = reversed_taps(taps, ntaps);
         nf.rev_f.upload(r.data(), r.size(), stream);
         nf.init(stream);
     }
@@ -1553,39 +1540,18 @@ AudioChain::AudioChain(const float* taps, size_t ntaps, size_t interp, size_t de
 
 // Bookkeeping as FmChain's without the demodulator's one-sample lag: a call emits whole filter blocks and every resampled
 // sample whose source lies in them.
-size_t AudioChain::next_block_outputs() const {
-    auto N2 = [&](uint64_t y) { return (uint64_t)(((__int128)y * I + D - 1) / D); };
-    return (size_t)(N2(n1 + f->nsamples) - N2(n1));
-}
-
 int AudioChain::work_blocks(const void* in, size_t in_len, float* out, size_t, size_t out_cap, size_t* consumed, size_t* produced,
                             size_t* need, hipStream_t s, uint64_t max_blocks) {
     *consumed = *produced = *need = 0;
-    const uint64_t S = f->nsamples;
-    auto N2 = [&](uint64_t y) { return (uint64_t)(((__int128)y * I + D - 1) / D); };
-    const uint64_t o_old = N2(n1);
-    const uint64_t need_next = N2(n1 + S) - o_old;                     // room for one filter block's outputs first
-    if (need_next > out_cap) { *need = need_next; return RR_WAIT_DST; }
-    const uint64_t total = f->pend_len + in_len, k_in = total / S;
-    const __int128 X = (__int128)(o_old + out_cap) * D / I;            // N2(n1 + k S) <= o_old + out_cap
-    uint64_t k_out = X >= (__int128)n1 ? (uint64_t)((X - n1) / S) : 0;
-    while (k_out > 0 && N2(n1 + k_out * S) - o_old > out_cap) k_out--;
-    k_out = std::min(k_out, max_blocks);
-    uint64_t k, new_pend;
-    int st;
-    if (k_in > k_out) {
-        k = k_out; *consumed = k * S - f->pend_len; new_pend = 0;
-        st = RR_WAIT_DST; *need = N2(n1 + (k + 1) * S) - N2(n1 + k * S);
-    } else {
-        k = k_in; *consumed = in_len; new_pend = total - k * S;
-        st = RR_WAIT_SRC; *need = S - new_pend;
-    }
-    const uint64_t n_y = k * S;
+    const ChainShape c = shape();
+    const ChainPlan p = chain_plan(c, n1, f->pend_len, in_len, out_cap, max_blocks);
+    *need = p.need;
+    if (p.early) return p.status;
+    const uint64_t S = c.S, n_y = p.n_y;
     VSrc<float> src{reinterpret_cast<const float*>(f->prefix[f->cur].p), (long)(f->hist + f->pend_len),
                     static_cast<const float*>(in), (long)in_len};
-    if (k) {
-        AudioChainArgs a{(long)n1, (long)n_y, (long)o_old, (long)N2(n1 + n_y), I, D, scale, {}};
-        if (*consumed) a.carry = CarryOut{f->prefix[f->cur ^ 1].p, (long)n_y, (long)(f->hist + new_pend)};
+    if (p.k) {
+        const AudioChainArgs a{(long)n1, (long)n_y, (long)p.r_lo, (long)p.r_hi, I, D, scale, f->carry_out(p)};
         prof_begin(s);
         launch_audio_chain(f->log2f, src, out, (int)f->L, f->d_tw.p, f->d_hpos.p, a, s);
         prof_end(s);
@@ -1595,16 +1561,13 @@ int AudioChain::work_blocks(const void* in, size_t in_len, float* out, size_t, s
                                           nf.slots.p, nf.seq, s);
             nf.seq++;
         }
-    } else if (*consumed) {
-        launch_vcopy_f32(src, (long)n_y, reinterpret_cast<float*>(f->prefix[f->cur ^ 1].p), (long)(f->hist + new_pend), s);
+    } else if (p.consumed) {
+        launch_vcopy_f32(src, (long)n_y, reinterpret_cast<float*>(f->prefix[f->cur ^ 1].p), (long)(f->hist + p.new_pend), s);
     }
-    if (*consumed) {
-        f->cur ^= 1;
-        f->pend_len = new_pend;
-    }
-    *produced = N2(n1 + n_y) - o_old;
+    f->commit(p);
+    *consumed = p.consumed; *produced = p.produced;
     n1 += n_y;
-    return st;
+    return p.status;
 }
 
 // ---- N FM chains on one shared source ---------------------------------------------------------------------
@@ -1650,14 +1613,7 @@ FmMulti::FmMulti(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, 
         }
         d_hpos_all.upload(all.data(), all.size(), stream);
         half_ok = fm_multi_half_supported(lg, chain->I, chain->D, (int)ntaps) && !build_opts().fm_full;
-        if (half_ok) {
-            std::vector<cf> th(F / 2);
-            for (size_t k = 0; k < F / 2; k++) {
-                const double a = -2.0 * 3.14159265358979323846 * (double)k / (double)(F / 2);
-                th[k] = mkcf((float)std::cos(a), (float)std::sin(a));
-            }
-            d_tw_half.upload(th.data(), th.size(), stream);
-        }
+        if (half_ok) upload_half_twiddles(d_tw_half, F / 2, stream);
     }
     for (auto& b : last_r) { b.reserve(C); RR_HIP(hipMemsetAsync(b.p, 0, C * sizeof(cf), stream)); }
     chain->nf.on = false;
@@ -1677,44 +1633,18 @@ int FmMulti::work_blocks(const void* in, size_t in_len, float* out, size_t out_s
     FmChain& ch = *chain;
     FftFilter* f = ch.f.get();
     *consumed = *produced = *need = 0;
-    if (iq8) in_len /= 2;                          // whole I/Q pairs; an odd trailing byte is never consumed
-    bool packed = iq8;
-    if (iq8 && ((uintptr_t)in & 1)) {              // odd-addressed byte window: decode out of line
-        decoded.reserve(std::max<size_t>(in_len, 1));
-        launch_rtlsdr_decode(static_cast<const unsigned char*>(in), decoded.p, (long)in_len, s);
-        in = decoded.p;
-        packed = false;
-    }
-    const uint64_t S = f->nsamples;
-    const int64_t I = ch.I, D = ch.D;
-    auto N2 = [&](uint64_t y) { return (uint64_t)(((__int128)y * I + D - 1) / D); };
-    const uint64_t lag = cplx ? 0 : 1;             // the demodulator's one-sample lag (none for the channelizer's Complex outputs)
-    auto N3 = [&](uint64_t y) { const uint64_t r = N2(y); return r > lag ? r - lag : 0; };
-    const uint64_t n1 = ch.n1, o_old = N3(n1);
-    const uint64_t need_next = N3(n1 + S) - o_old;
-    if (need_next > out_cap) { *need = need_next; return RR_WAIT_DST; }
-    const uint64_t total = f->pend_len + in_len, k_in = total / S;
-    const __int128 X = (__int128)(o_old + out_cap + lag) * D / I;
-    uint64_t k_out = X >= (__int128)n1 ? (uint64_t)((X - n1) / S) : 0;
-    while (k_out > 0 && N3(n1 + k_out * S) - o_old > out_cap) k_out--;
-    k_out = std::min(k_out, max_blocks);
-    uint64_t k, new_pend;
-    int st;
-    if (k_in > k_out) {
-        k = k_out; *consumed = k * S - f->pend_len; new_pend = 0;
-        st = RR_WAIT_DST; *need = N3(n1 + (k + 1) * S) - N3(n1 + k * S);
-    } else {
-        k = k_in; *consumed = in_len; new_pend = total - k * S;
-        st = RR_WAIT_SRC; *need = S - new_pend;
-    }
-    const uint64_t n_y = k * S;
+    const ByteSrc bytes(iq8, in, in_len, decoded, s);
+    const bool packed = bytes.packed;
+    const ChainShape c = shape();
+    const ChainPlan p = chain_plan(c, ch.n1, f->pend_len, in_len, out_cap, max_blocks);
+    *need = p.need;
+    if (p.early) return p.status;
+    const uint64_t S = c.S, n_y = p.n_y;
+    const int64_t I = c.I, D = c.D;
     VSrc<cf> src{f->prefix[f->cur].p, (long)(f->hist + f->pend_len), static_cast<const cf*>(in), (long)in_len};
     VSrcIQ8 src8{f->prefix[f->cur].p, (long)(f->hist + f->pend_len), static_cast<const rr::iq8*>(in), (long)in_len};
-    if (k) {
-        FmChainArgs a;
-        a.A = (long)n1; a.n_y = (long)n_y; a.r_lo = (long)N2(n1); a.r_hi = (long)N2(n1 + n_y);
-        a.o_base = (long)o_old; a.I = I; a.D = D; a.gain = ch.gain; a.mode = ch.mode;
-        if (*consumed) a.carry = CarryOut{f->prefix[f->cur ^ 1].p, (long)n_y, (long)(f->hist + new_pend)};
+    if (p.k) {
+        FmChainArgs a = fm_args(c, p, ch);
         a.multi_waves = poly_waves;
         prof_begin(s);
         cf* oc = reinterpret_cast<cf*>(out);
@@ -1759,21 +1689,14 @@ int FmMulti::work_blocks(const void* in, size_t in_len, float* out, size_t out_s
             nf.seq++;
         }
         if (a.r_hi > a.r_lo) cur_lr ^= 1;
-    } else if (*consumed) {
-        if (packed) launch_vcopy_iq8(src8, (long)n_y, f->prefix[f->cur ^ 1].p, (long)(f->hist + new_pend), s);
-        else launch_vcopy_c32(src, (long)n_y, f->prefix[f->cur ^ 1].p, (long)(f->hist + new_pend), s);
+    } else if (p.consumed) {
+        if (packed) launch_vcopy_iq8(src8, (long)n_y, f->prefix[f->cur ^ 1].p, (long)(f->hist + p.new_pend), s);
+        else launch_vcopy_c32(src, (long)n_y, f->prefix[f->cur ^ 1].p, (long)(f->hist + p.new_pend), s);
     }
-    if (*consumed) {
-        f->cur ^= 1;
-        f->pend_len = new_pend;
-    }
-    *produced = N3(n1 + n_y) - o_old;
+    f->commit(p);
+    *consumed = p.consumed; *produced = p.produced;
     ch.n1 += n_y;
-    if (iq8) {                                     // the input stream counts bytes
-        *consumed *= 2;
-        if (st == RR_WAIT_SRC) *need *= 2;
-    }
-    return st;
+    return bytes.done(p.status, consumed, need);
 }
 
 // ---- N-station FM receiver: FmMulti -> C audio chains in one kernel (examples/rtl_fm.rs:381-419 behind a Tee) ------------
@@ -1791,8 +1714,7 @@ FmReceiver::FmReceiver(const rr_c32* rf_taps, size_t nchan, size_t rf_ntaps, siz
     rf.reset(new FmMulti(rf_taps, nchan, rf_ntaps, rf_interp, rf_deci, gain, mode, u8));      // (may throw NotFusedShape)
     const int64_t gg = gcd64((int64_t)audio_deci, (int64_t)audio_interp);
     D2 = (int64_t)audio_deci / gg; I2 = (int64_t)audio_interp / gg;
-    std::vector<rr_c32> ct(audio_ntaps);
-    for (size_t i = 0; i < audio_ntaps; i++) ct[i] = rr_c32{audio_taps[i], 0.0f};              // fft_filter.rs:398
+    const std::vector<rr_c32> ct = widened_taps(audio_taps, audio_ntaps);
     af.reset(new FftFilter(ct.data(), audio_ntaps, false, 12, true));
     if (!audio_multi_supported(af->log2f)) throw NotFusedShape("FmReceiver: audio tile beyond the fused kernel");
     // The tile above minimises the cost per sample of a full chip.  A call whose work items — tiles x channels, all channels
@@ -1816,22 +1738,13 @@ FmReceiver::FmReceiver(const rr_c32* rf_taps, size_t nchan, size_t rf_ntaps, siz
         RR_HIP(hipMemsetAsync(p.p, 0, C * pstride * sizeof(float), stream));
     }
     if (chain_nf_wanted(u8, I2, D2, af->nsamples)) {
-        std::vector<float> r(audio_ntaps);
-        for (size_t j = 0; j < audio_ntaps; j++) r[j] = audio_taps[audio_ntaps - 1 - j];
+        const std::vector<float> r = reversed_taps(audio_taps, audio_ntaps);
         rev_f.upload(r.data(), r.size(), stream);
         std::vector<int> none(6 * C, -1);
         slots.upload(none.data(), none.size(), stream);
         nf_on = true;
     }
     RR_HIP(hipStreamSynchronize(stream));
-}
-
-// A(k) = ceil(floor(d(k S1) / S2) S2 I2 / D2), d(y) = max(ceil(y I1 / D1) - 1, 0): the demodulator lags the resampler by one sample
-uint64_t FmReceiver::audio_after(uint64_t k) const {
-    const FmChain& ch = *rf->chain;
-    const uint64_t r = (uint64_t)(((__int128)(k * ch.f->nsamples) * ch.I + ch.D - 1) / ch.D);
-    const uint64_t d = r ? r - 1 : 0, S2 = af->nsamples;
-    return (uint64_t)(((__int128)(d / S2 * S2) * I2 + D2 - 1) / D2);
 }
 
 // AudioChain::work_blocks' protocol with N2 replaced by A: WAIT_DST(A(K + 1) - A(K)) when the audio the next RF block completes
@@ -1841,8 +1754,8 @@ int FmReceiver::work_dev(const void* in, size_t in_len, void* out, size_t out_ca
                          hipStream_t s) {
     *consumed = *produced = *need = 0;
     FmChain& ch = *rf->chain;
-    const uint64_t S1 = ch.f->nsamples, S2 = af->nsamples;
-    const uint64_t K = ch.n1 / S1, a0 = audio_after(K);
+    const ChainShape rfs = rf->shape(), aus = audio_shape();
+    const uint64_t S1 = rfs.S, S2 = aus.S, K = ch.n1 / S1, a0 = audio_after(K);
     if (audio_after(K + 1) - a0 > out_cap) { *need = audio_after(K + 1) - a0; return RR_WAIT_DST; }
     const uint64_t k_in = (ch.f->pend_len + (iq8 ? in_len / 2 : in_len)) / S1;
     uint64_t lo = 1, hi = std::max<uint64_t>(k_in, 1);             // largest k in [1, max(k_in, 1)] whose audio fits (A is monotone)
@@ -1851,10 +1764,7 @@ int FmReceiver::work_dev(const void* in, size_t in_len, void* out, size_t out_ca
         if (audio_after(K + m) - a0 <= out_cap) lo = m; else hi = m - 1;
     }
     const uint64_t k_fit = lo, kk = std::min(k_in, k_fit);
-    auto demod_after = [&](uint64_t k) {
-        const uint64_t r = (uint64_t)(((__int128)(k * S1) * ch.I + ch.D - 1) / ch.D);
-        return r ? r - 1 : 0;
-    };
+    auto demod_after = [&](uint64_t k) { return chain_emitted(rfs, k * S1); };
     // stage 1 into the internal buffer: room for the blocks it will run (at least one: FmMulti asks for that before it looks)
     const size_t m_need = (size_t)(demod_after(K + std::max<uint64_t>(kk, 1)) - demod_after(K)) + 1;
     if (mid_cap < m_need) {
@@ -1867,30 +1777,29 @@ int FmReceiver::work_dev(const void* in, size_t in_len, void* out, size_t out_ca
     *consumed = c1;
     // stage 2: the p1 new demodulated samples of every channel behind its carried ones
     if (p1) {
-        const uint64_t total = pend_len + p1, k2 = total / S2, n_y = k2 * S2, new_pend = total - n_y;
-        auto N2 = [&](uint64_t y) { return (uint64_t)(((__int128)y * I2 + D2 - 1) / D2); };
+        const ReceiverSplit sp = receiver_split(aus, n1, pend_len, p1);
         const AudioMultiSrc src{pre[cur].p, (long)(af->hist + pend_len), (long)pstride, mid.p, (long)p1, (long)mid_cap};
-        AudioChainArgs a{(long)n1, (long)n_y, (long)N2(n1), (long)N2(n1 + n_y), I2, D2, scale, {}};
-        a.carry = CarryOut{pre[cur ^ 1].p, (long)n_y, (long)(af->hist + new_pend)};
+        const AudioChainArgs a{(long)n1, (long)sp.n_y, (long)sp.r_lo, (long)sp.r_hi, I2, D2, scale,
+                               CarryOut{pre[cur ^ 1].p, (long)sp.n_y, (long)(af->hist + sp.new_pend)}};
         const FftFilter* f = af.get();
-        if (af_small && k2) {
+        if (af_small && sp.k2) {
             const uint64_t per = 2 * (((uint64_t)1 << af->log2f) - af->L + 1);
-            if (C * ((n_y + per - 1) / per) < (uint64_t)std::max(1, device_cu_count())) f = af_small.get();
+            if (C * ((sp.n_y + per - 1) / per) < (uint64_t)std::max(1, device_cu_count())) f = af_small.get();
         }
         if ((size_t)(a.r_hi - a.r_lo) > out_cap) throw Error("FmReceiver: bookkeeping out of step");
         prof_begin(s);
         launch_audio_multi(f->log2f, src, (int)C, static_cast<float*>(out), (long)out_cap, (int)f->L, f->d_tw.p, f->d_hpos.p, a, s);
         prof_end(s);
-        if (nf_on && k2) {
+        if (nf_on && sp.k2) {
             const long P_y = (long)((size_t)1 << f->log2f) - (long)f->L + 1;       // one real segment of a tile
             launch_audio_multi_blocks_nonfinite(src, (int)C, static_cast<float*>(out), (long)out_cap, a, (long)S2, (long)af->hist,
                                                 chain_probe_stride(P_y, I2, D2), (int)af->L, rev_f.p, slots.p, nf_seq, s);
             nf_seq++;
         }
         cur ^= 1;
-        pend_len = new_pend;
+        pend_len = sp.new_pend;
         *produced = a.r_hi - a.r_lo;
-        n1 += n_y;
+        n1 += sp.n_y;
     }
     if (st1 == RR_WAIT_DST) {
         const uint64_t Kn = ch.n1 / S1;
@@ -1904,8 +1813,7 @@ int FmReceiver::work_dev(const void* in, size_t in_len, void* out, size_t out_ca
 // ---- FftFilterFloat (fft_filter.rs:365-491) ---------------------------------------------------------
 FftFilterFloat::FftFilterFloat(const float* taps, size_t ntaps) : Block("FftFilterFloat", 4, 4) {
     if (ntaps == 0) throw Error("FftFilterFloat: empty taps");
-    std::vector<rr_c32> ct(ntaps);
-    for (size_t i = 0; i < ntaps; i++) ct[i] = rr_c32{taps[i], 0.0f};  // fft_filter.rs:398
+    const std::vector<rr_c32> ct = widened_taps(taps, ntaps);
     real_inner = ntaps <= 3584 && !build_opts().fftfloat_complex;       // (the option keeps the three-kernel path testable)
     inner.reset(real_inner ? new FftFilter(ct.data(), ntaps, false, 12, true) : new FftFilter(ct.data(), ntaps));
     inner->ref_blocks_on(ct.data());

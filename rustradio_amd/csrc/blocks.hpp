@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/rustradio_amd.h"
+#include "chain_core.hpp"
 #include "kernels.hpp"
 #include "stage.hpp"
 
@@ -282,6 +283,9 @@ struct FftFilter : Block {
     void set_stage_taps(const rr_c32* t1, size_t n1, const rr_c32* t2, size_t n2);
     // samples of the window that can be filtered now (all of them without a front FIR)
     size_t avail(size_t in_len) const { return front ? (in_len > front ? in_len - front : 0) : in_len; }
+    // a fused chain's planned call (chain_core.hpp): the new carry prefix its kernel writes, and the state behind the call
+    CarryOut carry_out(const ChainPlan& p) const { return p.consumed ? CarryOut{prefix[cur ^ 1].p, (long)p.n_y, (long)(hist + p.new_pend)} : CarryOut{}; }
+    void commit(const ChainPlan& p) { if (p.consumed) { cur ^= 1; pend_len = p.new_pend; } }
     int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
     // out[n] = sum_k t[k] src[n + L - 1 - k], n < n_out (the tile kernel of the chosen size)
     // (carry: the caller's carry-state update, written by the same launch — common.hpp CarryOut)
@@ -372,7 +376,8 @@ struct FmChain : Block {
     ChainNf nf;                       // non-finite samples on the reference's blocks (round 6)
     FmChain(const rr_c32* taps, size_t ntaps, size_t interp, size_t deci, float gain, int mode, bool iq8 = false,
             int max_log2f = 14, const rr_c32* fir_taps = nullptr, size_t fir_ntaps = 0);
-    size_t next_block_outputs() const;
+    ChainShape shape() const { return ChainShape{f->nsamples, I, D, 1, f->front}; }     // lag 1: the demodulator's
+    size_t next_block_outputs() const { return (size_t)chain_next_block_outputs(shape(), n1); }
     int work_blocks(const void*, size_t, float*, size_t, size_t, size_t*, size_t*, size_t*, hipStream_t, uint64_t max_blocks);
     int work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* c, size_t* p, size_t* need, hipStream_t s) override {
         return trickle_work(*this, tail, 1, in, in_len, out, out_cap, c, p, need, s);
@@ -392,7 +397,8 @@ struct AudioChain : Block {
     OutTail tail;
     ChainNf nf;
     AudioChain(const float* taps, size_t ntaps, size_t interp, size_t deci, float scale);
-    size_t next_block_outputs() const;
+    ChainShape shape() const { return ChainShape{f->nsamples, I, D, 0, 0}; }
+    size_t next_block_outputs() const { return (size_t)chain_next_block_outputs(shape(), n1); }
     int work_blocks(const void*, size_t, float*, size_t, size_t, size_t*, size_t*, size_t*, hipStream_t, uint64_t max_blocks);
     int work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* c, size_t* p, size_t* need, hipStream_t s) override {
         return trickle_work(*this, tail, 1, in, in_len, out, out_cap, c, p, need, s);
@@ -424,7 +430,9 @@ struct FmMulti : Block {
     FmMulti(const rr_c32* taps, size_t nchan, size_t ntaps, size_t interp, size_t deci, float gain, int mode, bool iq8 = false,
             bool cplx = false);
     size_t out_windows() const override { return C; }
-    size_t next_block_outputs() const { return chain->next_block_outputs(); }
+    // the demodulator's one-sample lag; none for the channelizer's Complex outputs
+    ChainShape shape() const { return ChainShape{chain->f->nsamples, chain->I, chain->D, cplx ? 0u : 1u, 0}; }
+    size_t next_block_outputs() const { return chain->next_block_outputs(); }     // (lag 1: the channelizer never asks)
     int work_blocks(const void*, size_t, float*, size_t, size_t, size_t*, size_t*, size_t*, hipStream_t, uint64_t max_blocks);
     int work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* c, size_t* p, size_t* need, hipStream_t s) override {
         if (cplx) return work_blocks(in, in_len, static_cast<float*>(out), out_cap, out_cap, c, p, need, s, ~(uint64_t)0);
@@ -460,7 +468,9 @@ struct FmReceiver : Block {
     FmReceiver(const rr_c32* rf_taps, size_t nchan, size_t rf_ntaps, size_t rf_interp, size_t rf_deci, float gain, int mode,
                const float* audio_taps, size_t audio_ntaps, size_t audio_interp, size_t audio_deci, float scale, bool iq8);
     size_t out_windows() const override { return C; }
-    uint64_t audio_after(uint64_t rf_blocks) const;     // A(k): audio samples per channel after k RF filter blocks
+    ChainShape audio_shape() const { return ChainShape{af->nsamples, I2, D2, 0, 0}; }
+    // A(k), audio samples per channel after k RF filter blocks: ceil(floor(d(k S1) / S2) S2 I2 / D2), d(y) = max(ceil(y I1 / D1) - 1, 0)
+    uint64_t audio_after(uint64_t k) const { return receiver_audio_after(rf->shape(), audio_shape(), k); }
     int work_dev(const void*, size_t, void*, size_t, size_t*, size_t*, size_t*, hipStream_t) override;
 };
 // ... and what the fused kernels do not cover (FastFM, more than 3584 audio taps, RF shapes beyond FmMulti): make_fm_multi(...)

@@ -1163,6 +1163,49 @@ def test_fir_fm_chain_fused_block(rr, L1, L2, I, D, stream_bytes):
     _demod_close(yg / gain, yo / gain, ro)
 
 
+def test_fir_fm_chain_streams_through_short_windows_and_tight_rooms(rr):
+    """rr.FirFmChain, the one chain with a front FIR (5 taps: 4 samples stay in the window), 33 filter taps, 2:3, over a stream of
+    four filter blocks: windows of 1, front, front + 1 and S + front samples, output rooms of the next block's outputs and one
+    less.  Every call's (status, consumed, produced, need) against tests/chain_model.py and its samples against the oracle's
+    four blocks at the place in their stream the counts so far put them."""
+    from chain_model import ChainModel
+    L1, L2, I, D, gain = 5, 33, 2, 3, 0.7
+    t1 = (rnd_c(L1, L1) / 2).astype(np.complex64)
+    t2 = (rnd_c(L2, L2 + 1) / 8).astype(np.complex64)
+    front, S = L1 - 1, orc.fftfilter_dims(orc.FftFilter(t2))[1]
+    x = fm_signal(4 * S + front, 10e6, 0.0, 77)
+    yo = run_chain([orc.FirFilter(t1), orc.FftFilter(t2), orc.RationalResampler(I, D), orc.QuadratureDemod(gain)], x)
+    ro = run_chain([orc.FirFilter(t1), orc.FftFilter(t2), orc.RationalResampler(I, D)], x)
+    mag = np.abs(ro.astype(np.complex128))
+    eps = TOL * float(mag.max())
+    bound = TOL * np.pi + eps / np.maximum(mag[:-1], 1e-30) + eps / np.maximum(mag[1:], 1e-30)      # (_demod_close's, per sample)
+    m = ChainModel(S, I, D, 1, front)
+    assert len(yo) == -(-4 * S * I // D) - 1
+    blk = rr.FirFmChain(t1, t2, I, D, gain)
+    assert "unfused" not in blk.name
+    windows = [1, front, front + 1, S + front]
+    ring, pos, at, seen = np.zeros(0, np.complex64), 0, 0, set()
+    for i in range(400):
+        cin = windows[i % 4]
+        cout = max(m.next_block_outputs() - (i // 4) % 2, 1)
+        take = max(0, min(cin - len(ring), len(x) - pos))
+        ring = np.concatenate([ring, x[pos:pos + take]]); pos += take
+        want = m.work(len(ring[:cin]), cout)
+        st, c, p, need, out = blk.work(ring[:cin], cout)
+        assert (st, c, p, need) == want, (i, cin, cout, (st, c, p, need), want)
+        d = np.abs(out.astype(np.float64) - yo[at:at + p]) / gain
+        assert np.all(np.minimum(d, 2 * np.pi - d) <= bound[at:at + p]), (i, at, p)
+        ring = ring[c:]; at += p
+        seen.add((st, cin, c > 0, p > 0))
+        if at == len(yo) and pos == len(x):
+            break
+    assert at == len(yo) and len(ring) == front
+    # windows below the front FIR's minimum, one that only joins the pending samples, whole blocks into exactly their room (the
+    # tie: WAIT_SRC), a block through the tail (WAIT_DST) and its rest handed out ahead of a window too short to look at
+    assert (WAIT_SRC, 1, False, False) in seen and (WAIT_SRC, front, False, False) in seen and (WAIT_SRC, front + 1, True, False) in seen
+    assert (WAIT_SRC, S + front, True, True) in seen and (WAIT_DST, S + front, True, True) in seen and (WAIT_SRC, 1, False, True) in seen
+
+
 # ---- fused audio stage (SURVEY §8 f3): FftFilterFloat -> RationalResampler -> MultiplyConst as one kernel --------------
 @pytest.mark.parametrize("L,I,D", [(963, 48000, 200000), (963, 44100, 200000), (65, 1, 1), (127, 1, 4), (401, 3, 2), (1, 5, 7), (3584, 1, 5),
                                    (500, 7, 3)])

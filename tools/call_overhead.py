@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """GPU box: fixed cost of one work_dev() call per block type — 20 back-to-back calls on windows of 64k / 512k samples, events
-around the batch (GPU time per call) and host time per call."""
+around the batch (GPU time per call) and host time per call.
+Arguments, all optional: window sizes in samples (default 512000 2000000 8000000) and parts of block names to keep
+(`call_overhead.py 512000 FmChain463 FmMulti`)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -12,6 +14,7 @@ blocks = [("FftFilter401", lambda: rr.FftFilter(lp(10e6, 1e6, 60e3)), 8, 8, 1),
           ("Fir255/8", lambda: rr.FirFilter(lp(100e6, 5e6, 943e3), deci=8), 8, 8, 8),
           ("Fir401/6 poly", lambda: rr.FirFilter(lp(10e6, 1e6, 60e3), deci=6), 8, 8, 6),
           ("FmChain463 1:6", lambda: rr.FmChain(lp(2.4e6, 100e3, 12.5e3), 1, 6, 1.0), 8, 4, 6),
+          ("FmMulti463 x8 1:6", lambda: rr.FmMulti(np.stack([lp(2.4e6, 100e3, 12.5e3)] * 8), 1, 6, 1.0), 8, 4, 6),
           ("HilbertFir65*255/8", lambda: rr.HilbertFir(65, lp(100e6, 5e6, 943e3), 8), 4, 8, 8),
           ("Fir255/8 no-prune", lambda: _opt(dict(fir_prune=-1), lambda: rr.FirFilter(lp(100e6, 5e6, 943e3), deci=8)), 8, 8, 8),
           ("Fir255/8 direct", lambda: _opt(dict(fir_path="direct"), lambda: rr.FirFilter(lp(100e6, 5e6, 943e3), deci=8)), 8, 8, 8),
@@ -46,11 +49,15 @@ def _opt(o, f):
         return f()
 
 
-for n in (512_000, 2_000_000, 8_000_000):
+sizes = [int(a) for a in sys.argv[1:] if a.isdigit()] or [512_000, 2_000_000, 8_000_000]
+only = [a for a in sys.argv[1:] if not a.isdigit()]
+for n in sizes:
     x = torch.rand(2 * n, device="cuda") * 2 - 1
     y = torch.empty(2 * n + 4096, device="cuda")
     print()
     for name, mk, ies, oes, d in blocks:
+        if only and not any(o in name for o in only):
+            continue
         b = mk(); cap = n // d + 16
         for _ in range(5): b.work_dev(x.data_ptr(), n, y.data_ptr(), cap, s)
         torch.cuda.synchronize()
