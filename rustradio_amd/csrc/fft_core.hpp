@@ -13,6 +13,7 @@
 // Everything here is __host__ __device__ so tests/cpu_emulate_fft.cpp can run the
 // same pass functions thread-by-thread on the CPU.
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -26,6 +27,18 @@ namespace rr {
 
 struct alignas(8) cf { float x, y; };   // Complex<f32>, interleaved (src/lib.rs:268-271)
 RR_HD cf mkcf(float x, float y) { cf r; r.x = x; r.y = y; return r; }
+
+// evaluated in double, rounded once
+constexpr float kSqrtHalf = (float)0.70710678118654752440;
+constexpr float kCos8 = (float)0.92387953251128675613;   // cos(pi/8)
+constexpr float kSin8 = (float)0.38268343236508977173;   // sin(pi/8)
+constexpr float kTan8 = (float)0.41421356237309504880;   // tan(pi/8)  = sin(pi/8) / cos(pi/8)
+constexpr float kCot8 = (float)2.41421356237309504880;   // tan(3pi/8) = cos(pi/8) / sin(pi/8)
+
+// The butterflies' real constants, named by their slot: two share one SGPR pair on the device (op_sel picks the half), so
+// that the five take three pairs.  The persistent-register kernels have no SGPR to spare.
+enum { K_TAN8, K_COT8, K_COS8, K_SIN8, K_SQRT_HALF };
+template <int K> constexpr float kval() { return K == K_TAN8 ? kTan8 : K == K_COT8 ? kCot8 : K == K_COS8 ? kCos8 : K == K_SIN8 ? kSin8 : kSqrtHalf; }
 
 // Register type of the transform.  On the device a complex value lives in an aligned VGPR
 // pair (ext_vector float2) so that complex add/sub are single v_pk_add_f32 and a complex
@@ -84,23 +97,27 @@ RR_HD void cmulc2(creg& a0, creg w0, creg& a1, creg w1) {
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]" : "=v"(r1) : "v"(a1), "v"(w1), "v"(t1));
     a0 = r0; a1 = r1;
 }
-// the same with a compile-time constant w: the pair rides in SGPRs (one constant-bus operand) instead of two VGPRs that
-// the compiler would hoist out of the tile loop and keep for the whole kernel
-RR_HD creg cmul_k(creg a, creg w) {
-    creg t = a * __builtin_shufflevector(w, w, 0, 0), r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]"
-        : "=v"(r) : "v"(a), "s"(w), "v"(t));
+// Constant K's SGPR pair, (kval<K & ~1>, kval<K | 1>): an "s" operand is one constant-bus read, where VGPRs would be hoisted
+// out of the tile loop and kept for the whole kernel
+template <int K> RR_HD creg kpair() { return mk(kval<(K & ~1)>(), kval<(K | 1) <= K_SQRT_HALF ? (K | 1) : K>()); }
+// a + k u and a - k u, k = kval<K>: ONE packed FMA (hipcc emits the splat of an SGPR by itself), the minus on u's neg
+// modifier so that -k takes no SGPR of its own.  Written as asm these two cost 9 more s_nop per 2048-point tile.
+template <int K> RR_HD creg fma_k(creg u, creg a) { return __builtin_elementwise_fma(u, mk(kval<K>(), kval<K>()), a); }
+template <int K> RR_HD creg fms_k(creg u, creg a) { return __builtin_elementwise_fma(-u, mk(kval<K>(), kval<K>()), a); }
+// a + k (-j u) = (a.x + k u.y, a.y - k u.x) and a + k (+j u) = (a.x - k u.y, a.y + k u.x): the rotation rides on the
+// modifiers as in add_mj / add_pj
+template <int K> RR_HD creg fma_mj_k(creg u, creg a) {
+    creg r;
+    if constexpr (K & 1) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]" : "=v"(r) : "v"(u), "s"(kpair<K>()), "v"(a));
+    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_hi:[1,0,0]" : "=v"(r) : "v"(u), "s"(kpair<K>()), "v"(a));
     return r;
 }
-RR_HD creg cmulc_k(creg a, creg w) {
-    creg t = a * __builtin_shufflevector(w, w, 0, 0), r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]"
-        : "=v"(r) : "v"(a), "s"(w), "v"(t));
+template <int K> RR_HD creg fma_pj_k(creg u, creg a) {
+    creg r;
+    if constexpr (K & 1) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]" : "=v"(r) : "v"(u), "s"(kpair<K>()), "v"(a));
+    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_lo:[1,0,0]" : "=v"(r) : "v"(u), "s"(kpair<K>()), "v"(a));
     return r;
 }
-// a * k (real constant): ONE packed multiply (this file is compiled without SLP vectorisation, which would otherwise
-// be the only thing fusing the two scalar products)
-RR_HD creg cscale(creg a, float k) { return a * k; }
 RR_HD creg to_reg(cf a) { return mk(a.x, a.y); }
 RR_HD cf from_reg(creg a) { cf r; r.x = a.x; r.y = a.y; return r; }
 #else
@@ -112,11 +129,12 @@ RR_HD creg add_mj(creg a, creg b) { return mk(a.x + b.y, a.y - b.x); }
 RR_HD creg add_pj(creg a, creg b) { return mk(a.x - b.y, a.y + b.x); }
 RR_HD creg cmul(creg a, creg b) { return mk(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 RR_HD creg cmulc(creg a, creg b) { return mk(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }
-RR_HD creg cscale(creg a, float k) { return mk(a.x * k, a.y * k); }
+template <int K> RR_HD creg fma_k(creg u, creg a) { return mk(fmaf(kval<K>(), u.x, a.x), fmaf(kval<K>(), u.y, a.y)); }
+template <int K> RR_HD creg fms_k(creg u, creg a) { return mk(fmaf(-kval<K>(), u.x, a.x), fmaf(-kval<K>(), u.y, a.y)); }
+template <int K> RR_HD creg fma_mj_k(creg u, creg a) { return mk(fmaf(kval<K>(), u.y, a.x), fmaf(-kval<K>(), u.x, a.y)); }
+template <int K> RR_HD creg fma_pj_k(creg u, creg a) { return mk(fmaf(-kval<K>(), u.y, a.x), fmaf(kval<K>(), u.x, a.y)); }
 RR_HD void cmul2(creg& a0, creg w0, creg& a1, creg w1) { a0 = cmul(a0, w0); a1 = cmul(a1, w1); }
 RR_HD void cmulc2(creg& a0, creg w0, creg& a1, creg w1) { a0 = cmulc(a0, w0); a1 = cmulc(a1, w1); }
-RR_HD creg cmul_k(creg a, creg b) { return cmul(a, b); }
-RR_HD creg cmulc_k(creg a, creg b) { return cmulc(a, b); }
 RR_HD creg to_reg(cf a) { return a; }
 RR_HD cf from_reg(creg a) { return a; }
 #endif
@@ -127,44 +145,18 @@ RR_HD cf from_reg(creg a) { return a; }
 #define RR_LDS_Q
 #endif
 
-constexpr float kSqrtHalf = 0.70710678118654752440f;
-constexpr float kCos8 = 0.92387953251128675613f;   // cos(pi/8)
-constexpr float kSin8 = 0.38268343236508977173f;   // sin(pi/8)
-
 // a + w4 b and a - w4 b, w4 = -j (forward) or +j (inverse): the rotation is free
 template <bool INV> RR_HD creg add_w4(creg a, creg b) { return INV ? add_pj(a, b) : add_mj(a, b); }
 template <bool INV> RR_HD creg sub_w4(creg a, creg b) { return INV ? add_mj(a, b) : add_pj(a, b); }
+// a + k (w4 u) and a - k (w4 u), k = kval<K>: -w4 is the w4 of the other direction
+template <bool INV, int K> RR_HD creg fma_w4_k(creg u, creg a) { return INV ? fma_pj_k<K>(u, a) : fma_mj_k<K>(u, a); }
+template <bool INV, int K> RR_HD creg fms_w4_k(creg u, creg a) { return INV ? fma_mj_k<K>(u, a) : fma_pj_k<K>(u, a); }
+// x + t (w4 x), t = kval<T>: the product w x without its real factor c, for w = c (1 -+ j t) = exp(-+ j atan t)
+template <bool INV, int T> RR_HD creg rot_tan(creg x) { return fma_w4_k<INV, T>(x, x); }
 
-// multiply by w16^M = exp(-2 pi i M / 16) (forward) or its conjugate (INV)
-template <int M, bool INV> RR_HD creg mul_w16(creg a) {
-    constexpr int m = ((M % 16) + 16) % 16;
-    const creg zero = mk(0.0f, 0.0f);
-    if constexpr (m == 0) return a;
-    else if constexpr (m == 4) return add_w4<INV>(zero, a);
-    else if constexpr (m == 8) return csub(zero, a);
-    else if constexpr (m == 12) return sub_w4<INV>(zero, a);
-    else if constexpr (m == 2) {   // (1 -+ j)/sqrt2 : (a + w4 a) / sqrt2
-        creg t = add_w4<INV>(a, a);
-        return cscale(t, kSqrtHalf);
-    } else if constexpr (m == 6) { // (-1 -+ j)/sqrt2 : (w4 a - a) / sqrt2 = -(a - w4 a)/sqrt2
-        creg t = sub_w4<INV>(a, a);
-        return cscale(t, -kSqrtHalf);
-    } else if constexpr (m == 10) {
-        creg t = add_w4<INV>(a, a);
-        return cscale(t, -kSqrtHalf);
-    } else if constexpr (m == 14) {
-        creg t = sub_w4<INV>(a, a);
-        return cscale(t, kSqrtHalf);
-    } else {
-        // generic: forward w = (c, -s), s = sin(pi m / 8), c = cos(pi m / 8)
-        constexpr float c = (m == 1 || m == 15) ? kCos8 : (m == 3 || m == 13) ? kSin8
-                          : (m == 5 || m == 11) ? -kSin8 : -kCos8;            // m == 7, 9
-        constexpr float s = (m == 1 || m == 7) ? kSin8 : (m == 3 || m == 5) ? kCos8
-                          : (m == 9 || m == 15) ? -kSin8 : -kCos8;            // m == 11, 13
-        const creg w = mk(c, -s);
-        return INV ? cmulc_k(a, w) : cmul_k(a, w);
-    }
-}
+// The constant rotations w16^m between the two layers of Dft<8> / Dft<16> cost no multiply of their own: each is
+// written c (1 + t w4) (m = 1, 3, 9: t = tan, one rot_tan), (+-1 + w4) sqrt(1/2) (m = 2, 6: one add_w4 / sub_w4) or w4
+// itself (m = 4: nothing), and the real factor c that is left rides on the FMAs of the butterfly that consumes the value.
 
 template <bool INV> RR_HD void bfly2(creg& a, creg& b) {
     creg t = csub(a, b);
@@ -190,15 +182,35 @@ template <bool INV> struct Dft<2, INV> {
 template <bool INV> struct Dft<4, INV> {
     static RR_HD void run(creg* v) { bfly4<INV>(v[0], v[1], v[2], v[3]); }
 };
+// the second half of a 4-point DFT whose odd sums carry an outstanding real factor k = kval<K>:
+// (a0, a2) = t0 +- k t2, (a1, a3) = t1 +- k (w4 t3)
+template <bool INV, int K> RR_HD void bfly4_out_k(creg& a0, creg& a1, creg& a2, creg& a3, creg t0, creg t1, creg t2, creg t3) {
+    a0 = fma_k<K>(t2, t0);
+    a2 = fms_k<K>(t2, t0);
+    a1 = fma_w4_k<INV, K>(t3, t1);
+    a3 = fms_w4_k<INV, K>(t3, t1);
+}
+// natural-order 4-point DFT in place of (a0, k1 a1, +-k2 a2, +-kr k1 a3), minus with NEG: the real factors kval<K1>,
+// kval<K2>, kval<KR> ride on the FMAs
+template <bool INV, bool NEG, int K1, int K2, int KR> RR_HD void bfly4_k(creg& a0, creg& a1, creg& a2, creg& a3) {
+    creg p0 = fma_k<K2>(a2, a0), m0 = fms_k<K2>(a2, a0), p1 = fma_k<KR>(a3, a1), m1 = fms_k<KR>(a3, a1);
+    if constexpr (NEG) bfly4_out_k<INV, K1>(a0, a1, a2, a3, m0, p0, m1, p1);
+    else bfly4_out_k<INV, K1>(a0, a1, a2, a3, p0, m0, p1, m1);
+}
+
 template <bool INV> struct Dft<8, INV> {
     // n = 2 n1 + n2 (N1 = 4, N2 = 2), k = k1 + 4 k2
     static RR_HD void run(creg* v) {
         bfly4<INV>(v[0], v[2], v[4], v[6]);
         bfly4<INV>(v[1], v[3], v[5], v[7]);
-        v[3] = mul_w16<2, INV>(v[3]);   // w8^1
-        v[5] = mul_w16<4, INV>(v[5]);   // w8^2
-        v[7] = mul_w16<6, INV>(v[7]);   // w8^3
-        bfly2<INV>(v[0], v[1]); bfly2<INV>(v[2], v[3]); bfly2<INV>(v[4], v[5]); bfly2<INV>(v[6], v[7]);
+        // v[2 k1 + 1] *= w8^k1, folded into the 2-point butterflies
+        creg u3 = add_w4<INV>(v[3], v[3]);   // w8^1 v[3] = sqrt(1/2) u3
+        creg u7 = sub_w4<INV>(v[7], v[7]);   // w8^3 v[7] = -sqrt(1/2) u7
+        bfly2<INV>(v[0], v[1]);
+        v[3] = fms_k<K_SQRT_HALF>(u3, v[2]); v[2] = fma_k<K_SQRT_HALF>(u3, v[2]);
+        creg t = sub_w4<INV>(v[4], v[5]);    // w8^2 = w4
+        v[4] = add_w4<INV>(v[4], v[5]); v[5] = t;
+        v[7] = fma_k<K_SQRT_HALF>(u7, v[6]); v[6] = fms_k<K_SQRT_HALF>(u7, v[6]);
         // v[2 k1 + k2] = X[k1 + 4 k2]  ->  natural order
         creg t1 = v[1], t2 = v[2], t3 = v[3], t4 = v[4], t5 = v[5], t6 = v[6];
         v[1] = t2; v[2] = t4; v[3] = t6; v[4] = t1; v[5] = t3; v[6] = t5;
@@ -211,14 +223,23 @@ template <bool INV> struct Dft<16, INV> {
         bfly4<INV>(v[1], v[5], v[9], v[13]);
         bfly4<INV>(v[2], v[6], v[10], v[14]);
         bfly4<INV>(v[3], v[7], v[11], v[15]);
-        // v[4 k1 + n2] *= w16^(n2 k1)
-        v[5] = mul_w16<1, INV>(v[5]);   v[6] = mul_w16<2, INV>(v[6]);   v[7] = mul_w16<3, INV>(v[7]);
-        v[9] = mul_w16<2, INV>(v[9]);   v[10] = mul_w16<4, INV>(v[10]); v[11] = mul_w16<6, INV>(v[11]);
-        v[13] = mul_w16<3, INV>(v[13]); v[14] = mul_w16<6, INV>(v[14]); v[15] = mul_w16<9, INV>(v[15]);
+        // v[4 k1 + n2] *= w16^(n2 k1), each without its real factor (in brackets); the three rows side by side, so that no
+        // packed FMA reads the result of the one right before it (cmul2's wait state)
+        v[5] = rot_tan<INV, K_TAN8>(v[5]);    // w16^1  [cos(pi/8)]
+        v[13] = rot_tan<INV, K_COT8>(v[13]);  // w16^3  [sin(pi/8)]
+        v[7] = rot_tan<INV, K_COT8>(v[7]);    // w16^3  [sin(pi/8)]
+        v[15] = rot_tan<INV, K_TAN8>(v[15]);  // w16^9  [-cos(pi/8)]
+        v[6] = add_w4<INV>(v[6], v[6]);      // w16^2  [sqrt(1/2)]
+        v[14] = sub_w4<INV>(v[14], v[14]);   // w16^6  [-sqrt(1/2)]
+        v[9] = add_w4<INV>(v[9], v[9]);      // w16^2  [sqrt(1/2)]
+        v[11] = sub_w4<INV>(v[11], v[11]);   // w16^6  [-sqrt(1/2)]; w16^4 v[10] = w4 v[10] rides on row 2's first layer
         bfly4<INV>(v[0], v[1], v[2], v[3]);
-        bfly4<INV>(v[4], v[5], v[6], v[7]);
-        bfly4<INV>(v[8], v[9], v[10], v[11]);
-        bfly4<INV>(v[12], v[13], v[14], v[15]);
+        bfly4_k<INV, false, K_COS8, K_SQRT_HALF, K_TAN8>(v[4], v[5], v[6], v[7]);
+        {   // row 2: the odd pair's factors are +- sqrt(1/2), so its sums are plain
+            creg t0 = add_w4<INV>(v[8], v[10]), t1 = sub_w4<INV>(v[8], v[10]), t2 = csub(v[9], v[11]), t3 = cadd(v[9], v[11]);
+            bfly4_out_k<INV, K_SQRT_HALF>(v[8], v[9], v[10], v[11], t0, t1, t2, t3);
+        }
+        bfly4_k<INV, true, K_SIN8, K_SQRT_HALF, K_COT8>(v[12], v[13], v[14], v[15]);
         // v[4 k1 + k2] = X[k1 + 4 k2]  -> transpose 4x4 to natural order
         creg t;
         t = v[1]; v[1] = v[4]; v[4] = t;
