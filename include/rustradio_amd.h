@@ -1118,6 +1118,79 @@ int         rr_fanout_release(rr_fanout *f, unsigned long long t, void *compute_
 /* waits for the communication stream; summed duration and number of the broadcasts timed since the last call */
 int         rr_fanout_stats(rr_fanout *f, double *broadcast_ms, size_t *broadcasts);
 
+/* ---- KISS framing on the device (src/kiss.rs) -------------------------------------------------------------------
+ * The host side of examples/bell202.rs and examples/g3ruh.rs: ReaderSource -> KissFrame -> KissDecode -> FcsAdder -> … on the way
+ * out, … -> HdlcDeframer -> KissEncode -> PduToStream -> WriterSink on the way in.  FEND 0xC0, FESC 0xDB, TFEND 0xDC, TFESC 0xDD
+ * (:7-10).  Batch blocks: rr_block_work on either handle is an error.
+ *
+ * rr_kiss_decode: KissFrame (:165-228) -> KissDecode (:96-137) over pushes of one byte stream, in closed form.  With f_0 < f_1 < …
+ * the positions of the stream's FEND bytes: bytes in front of f_0 are dropped (Unsynced); every gap G = b[f_j + 1 .. f_j+1) with
+ * 1 <= |G| <= max_len is one KissFrame output (an empty gap is none, :204-206; a longer one is none and the machine resyncs at
+ * f_j+1, :211-217); G[0] & 0x0F != 0 drops it as non-data (:110-113), else port = G[0] >> 4 and x = G[1..] is un-escaped
+ * (:47-77): x is dropped when some FESC of it is its last byte or is followed by a byte other than TFEND / TFESC, else the packet
+ * is x without its FESC bytes, the byte behind each mapped TFEND -> FEND, TFESC -> FESC.  A packet of 0 bytes is delivered.  The
+ * three tags (:122-134) are record fields.  A push delivers every packet whose closing FEND lies inside it, whatever the split of
+ * the stream into pushes; the dst.remaining() back-pressure (:99-101, :168-170) has no counterpart.  The state between pushes —
+ * whether a FEND has been seen, the bytes of the gap still open (at most max_len = carry_bytes; a longer open gap carries
+ * nothing) and the five counters — stays on the device.  max_len 10000 is the reference's MAX_LEN (:6).
+ * NULL + rr_last_error, said before any device is touched: "kiss decode: max_len out of range (1 .. 2^20)". */
+typedef struct {
+    unsigned long long pos;    /* stream position of the closing FEND */
+    unsigned long long start;  /* first byte of the packet in the byte arena of this push; packets lie packed in stream order */
+    unsigned len;              /* "KissDecode:output-bytes" */
+    unsigned in_bytes;         /* "KissDecode:input-bytes": |x|, the escaped bytes behind the port byte */
+    unsigned port;             /* "KissDecode:port" */
+    unsigned reserved;         /* 0 */
+} rr_kiss_packet;              /* 32 bytes */
+rr_block *rr_kiss_decode_create(size_t max_len);
+/* The next n bytes of the stream, on the device (read on hip_stream) or on the host.  n == 0 launches nothing and leaves every
+ * state alone.  RR_ERR before any device is touched, nothing launched: "kiss decode: null input", "kiss decode: more than 2^30
+ * bytes in one push". */
+int rr_kiss_decode_push_dev(rr_block *b, const void *d_bytes, size_t n, void *hip_stream);
+int rr_kiss_decode_push(rr_block *b, const unsigned char *bytes, size_t n);
+/* The packets of the most recent push, ascending by pos (the contract of rr_wpcr_results), and their bytes.  Both wait for the
+ * push; every number the device wrote is checked against the push's length, the carry bound and max_len before it is used. */
+int rr_kiss_packets(rr_block *b, rr_kiss_packet *rec, size_t cap, size_t *total);
+int rr_kiss_packet_bytes(rr_block *b, unsigned char *out, size_t cap, size_t *total);
+/* The arena of the most recent push on the device (valid until the next push); *n_total: an upper bound of its bytes. */
+const void *rr_kiss_packet_bytes_dev(rr_block *b, size_t *n_total);
+/* So far: KissFrame outputs, packets delivered, non-data frames, bad escapes, gaps of more than max_len bytes (counted at the FEND
+ * that closes them).  frames = delivered + nondata + bad_escape. */
+int rr_kiss_decode_stats(rr_block *b, unsigned long long *five);
+/* The tile in bytes, the most bytes a push carries over, and the kernel launches of every push of n > 0 bytes. */
+int rr_kiss_decode_dims(const rr_block *b, size_t *tile_bytes, size_t *carry_bytes, size_t *launches);
+
+/* rr_kiss_encode: KissEncode (:247-286) -> PduToStream over a batch of packets of one byte buffer: per packet FEND, port << 4, the
+ * bytes with FEND -> FESC TFEND and FESC -> FESC TFESC (escape, :30-44), FEND; the frames lie back to back in d_out.  A port of
+ * 16 or more is 0 (:261-265).  The port byte is NOT escaped, as in the reference: port 12 writes a raw 0xC0. */
+typedef struct {
+    size_t start, len;         /* the frame is d_out[start .. start + len): "KissEncode:output-bytes" */
+    unsigned escaped;          /* len = 3 + L + escaped, L = the packet's bytes ("KissEncode:input-bytes") */
+    unsigned port;
+} rr_kiss_frame_record;
+rr_block *rr_kiss_encode_create(void);
+/* sum of 3 + 2 L: what out_cap must hold.  Saturates at SIZE_MAX. */
+size_t rr_kiss_encode_bound(const size_t *lens, size_t npackets);
+/* Packet p is bytes[starts[p] .. starts[p] + lens[p]) (ranges may overlap or repeat), its port ports[p] (NULL: 0).  npackets == 0
+ * launches nothing.  RR_ERR before any device is touched, nothing launched: "kiss encode: null packet descriptors", "… more than
+ * 2^30 bytes in one push", "… packet outside the buffer", "… more than 2^30 encoded bytes in one push", "… output shorter than the
+ * encoded bytes can be", "… null argument".  Bytes of d_out beyond *produced are not written. */
+int rr_kiss_encode_push_dev(rr_block *b, const void *d_bytes, size_t n_bytes, size_t *starts, size_t *lens, const unsigned *ports,
+                            size_t npackets, void *d_out, size_t out_cap, void *hip_stream);
+int rr_kiss_encode_push(rr_block *b, const unsigned char *bytes, size_t n_bytes, size_t *starts, size_t *lens, const unsigned *ports,
+                        size_t npackets, unsigned char *out, size_t out_cap, size_t *produced);
+/* The frames of the most recent push (the contract of rr_wpcr_results) and their sum; waits for the push. */
+int rr_kiss_encode_records(rr_block *b, rr_kiss_frame_record *rec, size_t cap, size_t *total, size_t *produced);
+int rr_kiss_encode_dims(const rr_block *b, size_t *tile_bytes, size_t *launches);
+/* The two joins, in the manner of rr_wpcr_process_pdus: wait for the producer's most recent push, take its checked records on the
+ * host, run the consumer on the producer's device arena — the payload bytes never leave the device.
+ * rr_kiss_encode_frames: the frames of an rr_hdlc_deframer (port 0; port_of_stream may be NULL) or an rr_hdlc_receiver (port
+ * port_of_stream[rec.stream], nports >= its streams) -> KISS bytes in d_out; any other handle is RR_ERR.
+ * rr_hdlc_framer_push_kiss: the packets of an rr_kiss_decode -> rr_hdlc_framer_push_dev. */
+int rr_kiss_encode_frames(rr_block *kiss, rr_block *deframer_or_receiver, const unsigned *port_of_stream, size_t nports, void *d_out,
+                          size_t out_cap, void *hip_stream);
+int rr_hdlc_framer_push_kiss(rr_block *framer, rr_block *kiss_decode, void *d_out, size_t out_cap, void *hip_stream);
+
 /* Measurement aid: when enabled, every work call brackets the block's dominant kernel
  * with HIP events on the stream it is launched on; rr_block_profile waits for them and
  * returns the summed kernel time and the number of launches (reset != 0 clears them). */

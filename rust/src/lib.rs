@@ -105,6 +105,26 @@ unsafe extern "C" {
     fn rr_hdlc_stats(b: *mut RrBlock, decoded: *mut u64, crc_error: *mut u64, bitfixed: *mut u64) -> c_int;
     #[allow(dead_code)]
     fn rr_hdlc_deframer_dims(b: *const RrBlock, tile_bits: *mut usize, carry_bits: *mut usize) -> c_int;
+    // (declared for completeness: KissDecode and KissEncode are NCReadStream<Vec<u8>> / NCWriteStream<Vec<u8>> blocks in the
+    //  reference (src/kiss.rs); their typed blocks need rr_kiss_packets / rr_kiss_encode_records (structs) and the descriptor
+    //  arrays, types outside this file's FFI map; the device-pointer side only; not written yet)
+    #[allow(dead_code)]
+    fn rr_kiss_decode_create(max_len: usize) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_kiss_decode_push_dev(b: *mut RrBlock, d_bytes: *const c_void, n: usize, hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_kiss_packet_bytes_dev(b: *mut RrBlock, n_total: *mut usize) -> *const c_void;
+    #[allow(dead_code)]
+    fn rr_kiss_decode_stats(b: *mut RrBlock, five: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn rr_kiss_decode_dims(b: *const RrBlock, tile_bytes: *mut usize, carry_bytes: *mut usize, launches: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_kiss_encode_create() -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_kiss_encode_dims(b: *const RrBlock, tile_bytes: *mut usize, launches: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_hdlc_framer_push_kiss(framer: *mut RrBlock, kiss_decode: *mut RrBlock, d_out: *mut c_void, out_cap: usize,
+                                hip_stream: *mut c_void) -> c_int;
     // (declared for completeness: SymbolSync takes a ReadStream<Float> and feeds a WriteStream<Float> plus the optional out_clock()
     //  stream; one handle runs N of them, so its typed block belongs with the N-channel blocks; not written yet)
     #[allow(dead_code)]

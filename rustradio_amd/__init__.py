@@ -761,6 +761,12 @@ class HdlcFramer(Block):
         rec, = _fetch(lib().rr_hdlc_framer_records, self._h, FRAME_RECORD, tail=(C.byref(produced),))
         return rec, produced.value
 
+    def push_kiss(self, kiss_decode: "KissDecode", d_out: int, out_cap: int, stream: int = 0) -> None:
+        """rr_hdlc_framer_push_kiss: the packets of the most recent push of a KissDecode, read from its device arena;
+        asynchronous on `stream`; records() waits"""
+        if lib().rr_hdlc_framer_push_kiss(self._h, kiss_decode._h, C.c_void_p(d_out), out_cap, C.c_void_p(stream)) != 0:
+            raise RuntimeError(last_error())
+
     def produced_dev(self) -> int:
         """-> raw device pointer to the elements the most recent push produced, one unsigned long long
         (rr_hdlc_framer_produced_dev): the d_counts of FskTxMulti.push_dev; valid until the next push"""
@@ -827,6 +833,146 @@ class HdlcDeframer(Block):
         if lib().rr_hdlc_stats(self._h, C.byref(d), C.byref(e), C.byref(f)) != 0:
             raise RuntimeError(last_error())
         return d.value, e.value, f.value
+
+
+KISS_MAX_LEN = 10000                             # MAX_LEN of src/kiss.rs:6
+# rr_kiss_packet
+KISS_PACKET = np.dtype([("pos", np.uint64), ("start", np.uint64), ("len", np.uint32), ("in_bytes", np.uint32), ("port", np.uint32),
+                        ("reserved", np.uint32)], align=True)
+# rr_kiss_frame_record
+KISS_FRAME_RECORD = np.dtype([("start", np.uintp), ("len", np.uintp), ("escaped", np.uint32), ("port", np.uint32)], align=True)
+
+
+class KissDecode(Block):
+    """KissFrame -> KissDecode behind one handle (rr_kiss_decode_create; src/kiss.rs:96-228; not a stream block: work() raises):
+    the next bytes of a KISS stream in, the packets whose closing FEND lies inside them out.  Whether a FEND has been seen, the
+    open gap's bytes and the counters stay on the device between pushes.  See include/rustradio_amd.h."""
+
+    def __init__(self, max_len: int = KISS_MAX_LEN):
+        super().__init__(lib().rr_kiss_decode_create(int(max_len)), np.uint8, np.uint8)
+        self.max_len = int(max_len)
+
+    def dims(self):
+        """-> (tile_bytes, carry_bytes, launches of a push) (rr_kiss_decode_dims)"""
+        t, c, k = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_kiss_decode_dims(self._h, C.byref(t), C.byref(c), C.byref(k)) != 0:
+            raise RuntimeError(last_error())
+        return t.value, c.value, k.value
+
+    def push_dev(self, d_bytes: int, n: int, stream: int = 0) -> None:
+        """rr_kiss_decode_push_dev: the next n bytes from a raw device pointer; asynchronous on `stream`; packets() waits"""
+        if lib().rr_kiss_decode_push_dev(self._h, C.c_void_p(d_bytes), int(n), C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+
+    def push(self, data):
+        """rr_kiss_decode_push on host bytes -> [(pos, port, in_bytes, bytes)] of the packets that ended inside them"""
+        x = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else data, np.uint8).ravel()
+        if lib().rr_kiss_decode_push(self._h, _ptr(x) if len(x) else None, len(x)) != 0:
+            raise ValueError(last_error())
+        return self.result()
+
+    def packets(self) -> np.ndarray:
+        """-> KISS_PACKET per packet of the most recent push, ascending by pos (rr_kiss_packets; waits)"""
+        return _fetch(lib().rr_kiss_packets, self._h, KISS_PACKET)[0]
+
+    def packet_bytes(self) -> np.ndarray:
+        """-> the byte arena of the most recent push, packed in stream order (rr_kiss_packet_bytes; waits)"""
+        return _fetch(lib().rr_kiss_packet_bytes, self._h, np.uint8)[0]
+
+    def bytes_dev(self):
+        """-> (raw device pointer or None, an upper bound of its bytes) of the same arena (rr_kiss_packet_bytes_dev)"""
+        n = C.c_size_t(0)
+        p = lib().rr_kiss_packet_bytes_dev(self._h, C.byref(n))
+        return p, n.value
+
+    def result(self):
+        """packets() and packet_bytes() of the most recent push as [(pos, port, in_bytes, bytes)]"""
+        rec = self.packets()
+        arena = self.packet_bytes() if len(rec) else np.zeros(0, np.uint8)
+        return [(int(r["pos"]), int(r["port"]), int(r["in_bytes"]), arena[int(r["start"]):int(r["start"]) + int(r["len"])].tobytes())
+                for r in rec]
+
+    def stats(self):
+        """-> (frames, delivered, nondata, bad_escape, overlong) of the handle so far (rr_kiss_decode_stats; waits)"""
+        five = (C.c_ulonglong * 5)()
+        if lib().rr_kiss_decode_stats(self._h, five) != 0:
+            raise RuntimeError(last_error())
+        return tuple(int(v) for v in five)
+
+
+class KissEncode(Block):
+    """KissEncode -> PduToStream<u8> behind one handle (rr_kiss_encode_create; src/kiss.rs:247-286; not a stream block: work()
+    raises): a batch of packets in, their KISS frames out, back to back.  See include/rustradio_amd.h."""
+
+    def __init__(self):
+        super().__init__(lib().rr_kiss_encode_create(), np.uint8, np.uint8)
+
+    def dims(self):
+        """-> (tile_bytes, launches of a push) (rr_kiss_encode_dims)"""
+        t, k = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_kiss_encode_dims(self._h, C.byref(t), C.byref(k)) != 0:
+            raise RuntimeError(last_error())
+        return t.value, k.value
+
+    @staticmethod
+    def bound(lens) -> int:
+        """rr_kiss_encode_bound: the bytes a push of packets of these lengths produces at most"""
+        ln = np.ascontiguousarray(lens, np.uintp)
+        return lib().rr_kiss_encode_bound(_ptr(ln) if len(ln) else None, len(ln))
+
+    @staticmethod
+    def _ports(ports, n):
+        if ports is None:
+            return None
+        po = np.ascontiguousarray(ports, np.uint32)
+        if po.shape != (n,):
+            raise ValueError("ports must be one per packet")
+        return po
+
+    def push_dev(self, d_bytes: int, n_bytes: int, starts, lens, ports, d_out: int, out_cap: int, stream: int = 0) -> None:
+        """rr_kiss_encode_push_dev: packet p is d_bytes[starts[p] : starts[p] + lens[p]] (raw device pointers); asynchronous on
+        `stream`; records() waits"""
+        st, ln = HdlcFramer._desc(starts, lens)
+        po = self._ports(ports, len(st))
+        if lib().rr_kiss_encode_push_dev(self._h, C.c_void_p(d_bytes), n_bytes, _ptr(st) if len(st) else None,
+                                         _ptr(ln) if len(ln) else None, _ptr(po) if po is not None and len(po) else None, len(st),
+                                         C.c_void_p(d_out), out_cap, C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+
+    def push_buffer(self, data, starts, lens, ports=None) -> np.ndarray:
+        """rr_kiss_encode_push on a host byte buffer -> the bytes the push produced"""
+        x = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else data, np.uint8).ravel()
+        st, ln = HdlcFramer._desc(starts, lens)
+        po = self._ports(ports, len(st))
+        cap = self.bound(ln)
+        out = np.zeros(max(cap, 1), np.uint8)
+        produced = C.c_size_t(0)
+        if lib().rr_kiss_encode_push(self._h, _ptr(x) if len(x) else None, len(x), _ptr(st) if len(st) else None,
+                                     _ptr(ln) if len(ln) else None, _ptr(po) if po is not None and len(po) else None, len(st),
+                                     _ptr(out), cap, C.byref(produced)) != 0:
+            raise ValueError(last_error())
+        return out[:produced.value]
+
+    def push(self, packets, ports=None) -> bytes:
+        """what the block does to each popped Vec<u8>, for a list of packets in one call -> their frames back to back"""
+        pk = [bytes(p) for p in packets]
+        lens = np.array([len(p) for p in pk], np.uintp)
+        starts = (np.cumsum(lens) - lens).astype(np.uintp)
+        return self.push_buffer(b"".join(pk), starts, lens, ports).tobytes()
+
+    def records(self):
+        """-> (KISS_FRAME_RECORD per packet of the most recent push, the bytes it produced) (rr_kiss_encode_records; waits)"""
+        produced = C.c_size_t(0)
+        rec, = _fetch(lib().rr_kiss_encode_records, self._h, KISS_FRAME_RECORD, tail=(C.byref(produced),))
+        return rec, produced.value
+
+    def encode_frames(self, source, d_out: int, out_cap: int, port_of_stream=None, stream: int = 0) -> None:
+        """rr_kiss_encode_frames: the frames of the most recent push of an HdlcDeframer or an HdlcReceiver, read from its device
+        arena; asynchronous on `stream`; records() waits"""
+        po = None if port_of_stream is None else np.ascontiguousarray(port_of_stream, np.uint32)
+        if lib().rr_kiss_encode_frames(self._h, source._h, _ptr(po) if po is not None and len(po) else None,
+                                       0 if po is None else len(po), C.c_void_p(d_out), out_cap, C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
 
 
 PWM_SHORT_IS_ZERO, PWM_GAP_DELIMITER = 1, 2      # RR_PWM_*

@@ -14,6 +14,8 @@
 #include "frame_host.hpp"
 #include "hdlc_host.hpp"
 #include "hdlcrx_host.hpp"
+#include "kiss_core.hpp"
+#include "kiss_host.hpp"
 #include "pdu_host.hpp"
 #include "symsync_host.hpp"
 #include "taps.hpp"
@@ -85,6 +87,7 @@ static const char NOT_WPCR[] = "not a wpcr handle", NOT_PDU[] = "not a stream_to
 static const char NOT_DEFRAMER[] = "not an hdlc deframer handle", NOT_SYNC[] = "not a symbol sync handle", NOT_AFSK[] = "not an afsk demod handle";
 static const char NOT_RECEIVER[] = "not an hdlc receiver handle", NOT_PWM[] = "not a pwm decoder handle";
 static const char NOT_FSK[] = "not an fsk tx handle", NOT_FSKM[] = "not an fsk tx multi handle";
+static const char NOT_KISSDEC[] = "not a kiss decode handle", NOT_KISSENC[] = "not a kiss encode handle";
 // a fetched list of (pos << shift) | val entries into the caller's two arrays
 template <class E> static void unpack(const std::vector<E>& e, unsigned shift, size_t* pos, unsigned char* val, size_t cap, size_t* total) {
     *total = e.size();
@@ -502,6 +505,137 @@ int rr_hdlc_deframer_dims(const rr_block* b, size_t* tile_bits, size_t* carry_bi
     *tile_bits = rr::HDLC_T;
     *carry_bits = rr::hdlc_carry_bits(d->core.max_size);
     return 0;
+}
+rr_block* rr_kiss_decode_create(size_t max_len) {
+    if (const char* e = rr::kiss_check_create(max_len)) return refuse_create(e);
+    return make_block([&] { return new rr::KissDecode(max_len); });
+}
+int rr_kiss_decode_push_dev(rr_block* b, const void* d_bytes, size_t n, void* hip_stream) {
+    auto* d = as<rr::KissDecode>(b, "rr_kiss_decode_push_dev", NOT_KISSDEC);
+    if (!d) return RR_ERR;
+    if (const char* e = rr::kiss_check_push(d_bytes, n)) { rr::set_last_error(e); return RR_ERR; }     // before any device is touched
+    return on_device(d, hip_stream, [&](hipStream_t s) { d->push_dev(static_cast<const unsigned char*>(d_bytes), n, s); });
+}
+int rr_kiss_decode_push(rr_block* b, const unsigned char* bytes, size_t n) {
+    auto* d = as<rr::KissDecode>(b, "rr_kiss_decode_push", NOT_KISSDEC);
+    if (!d) return RR_ERR;
+    if (const char* e = rr::kiss_check_push(bytes, n)) { rr::set_last_error(e); return RR_ERR; }
+    return guarded([&] { d->push_host(bytes, n); });
+}
+int rr_kiss_packets(rr_block* b, rr_kiss_packet* rec, size_t cap, size_t* total) {
+    auto* d = as<rr::KissDecode>(b, "rr_kiss_packets", NOT_KISSDEC);
+    if (!d) return RR_ERR;
+    if (!total || (cap && !rec)) { rr::set_last_error("rr_kiss_packets: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] { rr::kiss_copy_out(d->fetch_packets(), rec, cap, total); });
+}
+int rr_kiss_packet_bytes(rr_block* b, unsigned char* out, size_t cap, size_t* total) {
+    auto* d = as<rr::KissDecode>(b, "rr_kiss_packet_bytes", NOT_KISSDEC);
+    if (!d) return RR_ERR;
+    if (!total || (cap && !out)) { rr::set_last_error("rr_kiss_packet_bytes: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] { rr::kiss_copy_out(d->fetch_bytes(), out, cap, total); });
+}
+const void* rr_kiss_packet_bytes_dev(rr_block* b, size_t* n_total) {
+    auto* d = as<rr::KissDecode>(b, "rr_kiss_packet_bytes_dev", NOT_KISSDEC);
+    if (n_total) *n_total = d ? d->arena_len() : 0;
+    return d ? d->arena_dev() : nullptr;
+}
+int rr_kiss_decode_stats(rr_block* b, unsigned long long* five) {
+    auto* d = as<rr::KissDecode>(b, "rr_kiss_decode_stats", NOT_KISSDEC);
+    if (!d) return RR_ERR;
+    if (!five) { rr::set_last_error("rr_kiss_decode_stats: null argument"); return RR_ERR; }
+    return on_device(d, [&] { d->fetch_stats(five); });
+}
+int rr_kiss_decode_dims(const rr_block* b, size_t* tile_bytes, size_t* carry_bytes, size_t* launches) {
+    auto* d = as<rr::KissDecode>(b, "rr_kiss_decode_dims", NOT_KISSDEC);
+    if (!d || !tile_bytes || !carry_bytes || !launches) { if (d) rr::set_last_error("rr_kiss_decode_dims: null argument"); return RR_ERR; }
+    *tile_bytes = rr::KISS_T;
+    *carry_bytes = d->max_len;
+    *launches = rr::KISS_DECODE_LAUNCHES;
+    return 0;
+}
+rr_block* rr_kiss_encode_create(void) {
+    return make_block([&] { return new rr::KissEncode(); });
+}
+size_t rr_kiss_encode_bound(const size_t* lens, size_t npackets) {
+    if (npackets && !lens) return 0;
+    return rr::kiss_encode_bound(lens, npackets);
+}
+int rr_kiss_encode_push_dev(rr_block* b, const void* d_bytes, size_t n_bytes, size_t* starts, size_t* lens, const unsigned* ports,
+                            size_t npackets, void* d_out, size_t out_cap, void* hip_stream) {
+    auto* k = as<rr::KissEncode>(b, "rr_kiss_encode_push_dev", NOT_KISSENC);
+    if (!k) return RR_ERR;
+    size_t bound = 0;                                  // every refusal before any device is touched
+    if (const char* e = rr::kiss_encode_check_push(n_bytes, starts, lens, npackets, out_cap, &bound)) { rr::set_last_error(e); return RR_ERR; }
+    if (npackets && (!d_out || (n_bytes && !d_bytes))) { rr::set_last_error("kiss encode: null argument"); return RR_ERR; }
+    return on_device(k, hip_stream, [&](hipStream_t s) {
+        k->push_dev(static_cast<const unsigned char*>(d_bytes), n_bytes, starts, lens, ports, npackets, d_out, out_cap, s);
+    });
+}
+int rr_kiss_encode_push(rr_block* b, const unsigned char* bytes, size_t n_bytes, size_t* starts, size_t* lens, const unsigned* ports,
+                        size_t npackets, unsigned char* out, size_t out_cap, size_t* produced) {
+    auto* k = as<rr::KissEncode>(b, "rr_kiss_encode_push", NOT_KISSENC);
+    if (!k) return RR_ERR;
+    if (!produced) { rr::set_last_error("kiss encode: null argument"); return RR_ERR; }
+    size_t bound = 0;
+    if (const char* e = rr::kiss_encode_check_push(n_bytes, starts, lens, npackets, out_cap, &bound)) { rr::set_last_error(e); return RR_ERR; }
+    if (npackets && (!out || (n_bytes && !bytes))) { rr::set_last_error("kiss encode: null argument"); return RR_ERR; }
+    return guarded([&] { k->push_host(bytes, n_bytes, starts, lens, ports, npackets, out, out_cap, produced); });
+}
+int rr_kiss_encode_records(rr_block* b, rr_kiss_frame_record* rec, size_t cap, size_t* total, size_t* produced) {
+    auto* k = as<rr::KissEncode>(b, "rr_kiss_encode_records", NOT_KISSENC);
+    if (!k) return RR_ERR;
+    if (!total || !produced || (cap && !rec)) { rr::set_last_error("rr_kiss_encode_records: null argument"); return RR_ERR; }
+    return on_device(k, [&] {
+        rr::kiss_copy_out(k->fetch_records(), rec, cap, total);
+        *produced = k->produced;
+    });
+}
+int rr_kiss_encode_dims(const rr_block* b, size_t* tile_bytes, size_t* launches) {
+    auto* k = as<rr::KissEncode>(b, "rr_kiss_encode_dims", NOT_KISSENC);
+    if (!k || !tile_bytes || !launches) { if (k) rr::set_last_error("rr_kiss_encode_dims: null argument"); return RR_ERR; }
+    *tile_bytes = rr::KISS_T;
+    *launches = rr::KISS_ENCODE_LAUNCHES;
+    return 0;
+}
+int rr_kiss_encode_frames(rr_block* kiss, rr_block* src, const unsigned* port_of_stream, size_t nports, void* d_out, size_t out_cap,
+                          void* hip_stream) {
+    auto* k = as<rr::KissEncode>(kiss, "rr_kiss_encode_frames", NOT_KISSENC);
+    if (!k) return RR_ERR;
+    auto* d = src ? dynamic_cast<rr::HdlcDeframer*>(src->b.get()) : nullptr;
+    auto* r = src ? dynamic_cast<rr::HdlcReceiver*>(src->b.get()) : nullptr;
+    if (!d && !r) { rr::set_last_error("rr_kiss_encode_frames: not an hdlc deframer or receiver handle"); return RR_ERR; }
+    return on_device(k, [&] {
+        if (k->device != (d ? d->device : r->device)) throw rr::Error("rr_kiss_encode_frames: the two handles live on different devices");
+        std::vector<size_t> starts, lens;
+        std::vector<unsigned> ports;
+        if (d) {
+            for (const rr_hdlc_frame& f : d->fetch_frames()) { starts.push_back((size_t)f.start); lens.push_back(f.len); }
+        } else {
+            if (r->core.nstreams > nports || !port_of_stream) throw rr::Error("kiss encode: port_of_stream shorter than the receiver's streams");
+            for (const rr_hdlc_stream_frame& f : r->fetch_frames()) {
+                starts.push_back((size_t)f.start); lens.push_back(f.len); ports.push_back(port_of_stream[f.stream]);
+            }
+        }
+        rr::HdlcCore& core = d ? d->core : r->core;
+        hipStream_t s = static_cast<hipStream_t>(hip_stream);
+        k->last_stream = s;
+        k->push_dev(core.arena_dev(), core.arena_len(), starts.data(), lens.data(), d ? nullptr : ports.data(), starts.size(), d_out, out_cap, s);
+    });
+}
+int rr_hdlc_framer_push_kiss(rr_block* framer, rr_block* kiss_decode, void* d_out, size_t out_cap, void* hip_stream) {
+    auto* f = as<rr::HdlcFramer>(framer, "rr_hdlc_framer_push_kiss", NOT_FRAMER);
+    auto* k = as<rr::KissDecode>(kiss_decode, "rr_hdlc_framer_push_kiss", NOT_KISSDEC);
+    if (!f || !k) return RR_ERR;
+    return on_device(f, [&] {
+        if (f->device != k->device) throw rr::Error("rr_hdlc_framer_push_kiss: the two handles live on different devices");
+        std::vector<size_t> starts, lens;
+        for (const rr_kiss_packet& p : k->fetch_packets()) { starts.push_back((size_t)p.start); lens.push_back(p.len); }
+        hipStream_t s = static_cast<hipStream_t>(hip_stream);
+        f->last_stream = s;
+        f->push_dev(k->arena_dev(), k->arena_len(), starts.data(), lens.data(), starts.size(), d_out, out_cap, s);
+    });
 }
 rr_block* rr_pwm_decoder_create(float high_threshold, float low_threshold, size_t short_width, size_t long_width, size_t pulse_tolerance,
                                 size_t frame_gap, size_t reset_gap, size_t frame_bits, size_t max_frame_bits, size_t max_distinct_frames,

@@ -1,5 +1,5 @@
 // blocks_packet.cpp — host side of the packet-side blocks (blocks_packet.hpp): the sync blocks, the burst and bit blocks, and the
-// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver, AfskDemod, FskTx, FskTxMulti).  Citations are to the reference's src, as in blocks.cpp.
+// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver, AfskDemod, FskTx, FskTxMulti, KissDecode, KissEncode).  Citations are to the reference's src, as in blocks.cpp.
 #include "blocks_packet.hpp"
 
 #include <algorithm>
@@ -10,6 +10,7 @@
 #include "frame_core.hpp"
 #include "frame_host.hpp"
 #include "hdlcrx_core.hpp"
+#include "kiss_core.hpp"
 #include "pdu_host.hpp"
 #include "symsync_host.hpp"
 #include "taps.hpp"
@@ -664,6 +665,161 @@ void HdlcDeframer::fetch_stats(unsigned long long out[3]) {
     settle();
     const std::vector<unsigned long long> now = core.fetch_stats(false, stream);
     std::copy(now.begin(), now.end(), out);
+}
+
+// ---- KissDecode (kiss.rs:96-228; kernels_kiss.hip) --------------------------------------------------------------------------------------
+static_assert(sizeof(KissRec) == sizeof(rr_kiss_packet) && offsetof(KissRec, pos) == offsetof(rr_kiss_packet, pos) &&
+              offsetof(KissRec, start) == offsetof(rr_kiss_packet, start) && offsetof(KissRec, len) == offsetof(rr_kiss_packet, len) &&
+              offsetof(KissRec, in_bytes) == offsetof(rr_kiss_packet, in_bytes) && offsetof(KissRec, port) == offsetof(rr_kiss_packet, port),
+              "KissRec is rr_kiss_packet");
+static_assert(KISS_TILE == (size_t)KISS_T, "kiss_host.hpp plans in the kernels' tiles");
+KissDecode::KissDecode(size_t mx)
+    : BatchBlock("KissFrame>KissDecode", 1, 1, "KissDecode delivers packets: rr_kiss_decode_push / rr_kiss_decode_push_dev"), max_len(mx) {
+    if (const char* e = kiss_check_create(mx)) throw Error(e);
+    KissState init{};
+    init.code = KISS_UNSYNC;                   // FrameState::default() (kiss.rs:140-145)
+    st.upload(&init, 1, stream);
+    for (auto& b : cbytes.buf) b.reserve(mx);
+    count.reserve(2);
+    root.reserve(6);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void KissDecode::push_dev(const unsigned char* d_bytes, size_t n, hipStream_t s) {
+    if (const char* e = kiss_check_push(d_bytes, n)) throw Error(e);
+    packets.clear();
+    bytes.clear();
+    fetched = bfetched = true;                 // a push of no bytes has no packets and leaves every state alone
+    last_n = n;
+    if (!n) return;
+    last_carry = carry;
+    const KissPlan p = kiss_plan(carry, n);
+    sums.reserve(6 * p.ntiles); tin.reserve(6 * p.ntiles); tsum.reserve(5 * p.ntiles); toff.reserve(2 * p.ntiles); obase.reserve(p.ntiles + 1);
+    arena.reserve(p.arena_cap);
+    recs.reserve(std::max<size_t>(p.rec_cap, 1));
+    KissArgs a{};
+    a.bytes = d_bytes; a.n = (long)n; a.cin = cbytes.in(); a.cout = cbytes.out(); a.st_in = st.in(); a.st_out = st.out();
+    a.max_len = (unsigned)max_len; a.nv_max = (long)p.nv_max; a.ntiles = (long)p.ntiles; a.w0 = w0;
+    a.sums = sums.p; a.tin = tin.p; a.root = root.p; a.tsum = tsum.p; a.toff = toff.p; a.obase = obase.p;
+    a.arena = arena.p; a.arena_cap = (long)p.arena_cap; a.recs = recs.p; a.rec_cap = (long)p.rec_cap; a.count = count.p;
+    prof_begin(s);
+    RR_HIP(hipMemsetAsync(obase.p, 0xff, (p.ntiles + 1) * sizeof(unsigned), s));
+    launch_kiss_decode(a, s);
+    prof_end(s);
+    st.flip();
+    cbytes.flip();
+    carry = kiss_next_carry(carry, n, max_len);
+    w0 += n;
+    fetched = bfetched = false;
+}
+void KissDecode::push_host(const unsigned char* hb, size_t n) {
+    host_call([&] {
+        if (const char* e = kiss_check_push(hb, n)) throw Error(e);
+        if (n) {
+            h_bytes.reserve(n);
+            hstage().h2d(h_bytes.p, hb, n, stream);
+        }
+        push_dev(h_bytes.p, n, stream);
+    });
+}
+const std::vector<rr_kiss_packet>& KissDecode::fetch_packets() {
+    settle();
+    if (!fetched) {
+        fetched = true;                        // (a refused push has no packets: the refusal is not repeated)
+        bfetched = true;
+        const KissPlan p = kiss_plan(last_carry, last_n);
+        unsigned long long k[2] = {0, 0};
+        stage_download_sync(k, count.p, sizeof k, stream);
+        if (const char* e = kiss_check_count(k, p)) throw Error(e);
+        std::vector<rr_kiss_packet> r((size_t)k[0]);
+        if (k[0]) stage_download_sync(r.data(), recs.p, (size_t)k[0] * sizeof(rr_kiss_packet), stream);
+        KissState now{}, before{};
+        stage_download_sync(&now, st.in(), sizeof now, stream);
+        stage_download_sync(&before, st.out(), sizeof before, stream);
+        if (const char* e = kiss_validate(r, p, max_len, w0 - last_n, last_n, last_carry, k[1], before.stats, now.stats)) throw Error(e);
+        packets.swap(r);
+        bytes.assign((size_t)k[1], 0);         // the arena is read only behind a push whose records stood the checks
+        bfetched = k[1] == 0;
+    }
+    return packets;
+}
+const std::vector<unsigned char>& KissDecode::fetch_bytes() {
+    fetch_packets();
+    if (!bfetched) {
+        stage_download_sync(bytes.data(), arena.p, bytes.size(), stream);
+        bfetched = true;
+    }
+    return bytes;
+}
+void KissDecode::fetch_stats(unsigned long long out[5]) {
+    settle();
+    KissState now{};
+    stage_download_sync(&now, st.in(), sizeof now, stream);
+    std::copy(now.stats, now.stats + 5, out);
+}
+
+// ---- KissEncode (kiss.rs:247-286; kernels_kiss.hip) -------------------------------------------------------------------------------------
+KissEncode::KissEncode()
+    : BatchBlock("KissEncode>PduToStream", 1, 1, "KissEncode takes whole packets: rr_kiss_encode_push / rr_kiss_encode_push_dev") {
+    total.reserve(1);
+}
+void KissEncode::push_dev(const unsigned char* d_bytes, size_t n_bytes, const size_t* st, const size_t* ln, const unsigned* po,
+                          size_t npackets, void* d_out, size_t out_cap, hipStream_t s) {
+    size_t bnd = 0;
+    if (const char* e = kiss_encode_check_push(n_bytes, st, ln, npackets, out_cap, &bnd)) throw Error(e);
+    if (npackets && (!d_out || (n_bytes && !d_bytes))) throw Error("kiss encode: null argument");
+    lens.assign(ln, ln + npackets);
+    if (po) ports.assign(po, po + npackets); else ports.assign(npackets, 0u);
+    bound = bnd;
+    records.clear();
+    produced = 0;
+    fetched = true;                            // a push of no packets has no records
+    if (!npackets) return;
+    KissEncPlan pl;
+    kiss_encode_plan(st, ln, po, npackets, pl);
+    KissEncArgs a{};
+    a.P = (long)npackets;
+    a.nbytes = (long)pl.nbytes;
+    a.ntiles = (long)std::max<size_t>(1, (pl.nbytes + KISS_T - 1) / KISS_T);
+    desc.reserve(pl.words.size());
+    tcnt.reserve((size_t)a.ntiles); tin.reserve((size_t)a.ntiles); cb.reserve(npackets + 1);
+    hstage().h2d(desc.p, pl.words.data(), pl.words.size() * sizeof(unsigned long long), s);      // (pl is free on return)
+    a.bytes = d_bytes;
+    a.starts = desc.p; a.pb = desc.p + npackets; a.ports = desc.p + 2 * npackets + 1;
+    a.tcnt = tcnt.p; a.tin = tin.p; a.cb = cb.p; a.total = total.p;
+    a.out = static_cast<unsigned char*>(d_out);
+    a.cap = (long)bnd;
+    prof_begin(s);
+    launch_kiss_encode(a, s);
+    prof_end(s);
+    fetched = false;
+}
+void KissEncode::push_host(const unsigned char* hb, size_t n_bytes, const size_t* st, const size_t* ln, const unsigned* po, size_t npackets,
+                           unsigned char* out, size_t out_cap, size_t* prod) {
+    host_call([&] {
+        size_t bnd = 0;
+        if (const char* e = kiss_encode_check_push(n_bytes, st, ln, npackets, out_cap, &bnd)) throw Error(e);
+        *prod = 0;
+        if (!npackets) { push_dev(nullptr, n_bytes, st, ln, po, 0, nullptr, out_cap, stream); return; }
+        h_in.reserve(std::max<size_t>(n_bytes, 1));
+        h_out.reserve(std::max<size_t>(bnd, 1));
+        if (n_bytes) hstage().h2d(h_in.p, hb, n_bytes, stream);
+        push_dev(h_in.p, n_bytes, st, ln, po, npackets, h_out.p, bnd, stream);
+        fetch_records();                       // waits; `produced` is checked against the bound in there
+        if (produced) hstage().d2h(out, h_out.p, produced, stream);
+        *prod = produced;
+    });
+}
+const std::vector<rr_kiss_frame_record>& KissEncode::fetch_records() {
+    settle();
+    if (!fetched) {
+        fetched = true;
+        std::vector<unsigned> hcb(lens.size() + 1);
+        unsigned long long tot = 0;
+        stage_download_sync(hcb.data(), cb.p, hcb.size() * sizeof(unsigned), stream);
+        stage_download_sync(&tot, total.p, sizeof tot, stream);
+        if (const char* e = kiss_encode_records(lens, ports, hcb, tot, bound, records, &produced)) throw Error(e);
+    }
+    return records;
 }
 
 // ---- PwmDecoder (pwm_decoder.rs:385-513; kernels_pwm.hip) -------------------------------------------------------------------------------

@@ -5,6 +5,7 @@
 #include "pwm_host.hpp"
 #include "afsk_host.hpp"
 #include "fsk_host.hpp"
+#include "kiss_host.hpp"
 
 namespace rr {
 
@@ -319,6 +320,55 @@ struct HdlcDeframer : BatchBlock {
     const std::vector<rr_hdlc_frame>& fetch_frames();         // waits for the most recent push
     const std::vector<unsigned char>& fetch_bytes();
     void fetch_stats(unsigned long long out[3]);
+};
+
+// KissFrame -> KissDecode (kiss.rs:96-228) over windows of a byte stream (kernels_kiss.hip): no stream protocol (work_dev is an
+// error).  Everything between pushes (KissState: synced or not, the counters; the open gap's bytes) stays on the device in pairs;
+// the host keeps the stream position and ONE upper bound of the carried bytes, which with a push's length gives every size here.
+struct KissDecode : BatchBlock {
+    size_t max_len;
+    Carried<KissState> st;                        // in(): what the stream so far left behind
+    Carried<unsigned char> cbytes;                // ... and the bytes of its open gap: max_len each
+    size_t carry = 0;                             // the carried bytes, at most
+    unsigned long long w0 = 0;                    // bytes of the stream so far
+    DevBuf<unsigned> sums, tin, root, tsum, toff, obase;
+    DevBuf<unsigned long long> count;
+    DevBuf<unsigned char> arena;
+    DevBuf<KissRec> recs;
+    DevBuf<unsigned char> h_bytes;                // push_host(): the host window's device copy
+    size_t last_n = 0, last_carry = 0;            // the most recent push: its bytes; the carry bound it began with
+    bool fetched = true, bfetched = true;         // `packets` / `bytes` hold the most recent push's
+    std::vector<rr_kiss_packet> packets;          // ... ascending by pos
+    std::vector<unsigned char> bytes;
+    explicit KissDecode(size_t max_len);
+    void push_dev(const unsigned char* d_bytes, size_t n, hipStream_t s);
+    void push_host(const unsigned char* bytes, size_t n);
+    const std::vector<rr_kiss_packet>& fetch_packets();       // waits for the most recent push
+    const std::vector<unsigned char>& fetch_bytes();
+    void fetch_stats(unsigned long long out[5]);
+    size_t arena_len() const { return last_n ? kiss_plan(last_carry, last_n).arena_cap : 0; }
+    const unsigned char* arena_dev() const { return arena_len() ? arena.p : nullptr; }
+};
+
+// KissEncode -> PduToStream<u8> (kiss.rs:247-286) in PDU form over a batch of packets of one byte buffer (kernels_kiss.hip): no
+// stream protocol (work_dev is an error), no state between pushes.  The host keeps the geometry of the latest push; what it
+// reads back (kiss_host.hpp) is sized from that geometry.
+struct KissEncode : BatchBlock {
+    DevBuf<unsigned long long> desc, total;       // this push's starts / pb / ports; the bytes it made
+    DevBuf<unsigned> tcnt, tin, cb;
+    DevBuf<unsigned char> h_in, h_out;            // push_host(): the host buffers' device copies
+    std::vector<size_t> lens;                     // the latest push's geometry
+    std::vector<unsigned> ports;
+    size_t bound = 0;
+    bool fetched = true;                          // `records` / `produced` hold the latest push's
+    std::vector<rr_kiss_frame_record> records;
+    size_t produced = 0;
+    KissEncode();
+    void push_dev(const unsigned char* d_bytes, size_t n_bytes, const size_t* starts, const size_t* lens, const unsigned* ports,
+                  size_t npackets, void* d_out, size_t out_cap, hipStream_t s);
+    void push_host(const unsigned char* bytes, size_t n_bytes, const size_t* starts, const size_t* lens, const unsigned* ports,
+                   size_t npackets, unsigned char* out, size_t out_cap, size_t* produced);
+    const std::vector<rr_kiss_frame_record>& fetch_records();     // waits for the latest push
 };
 
 // [ComplexToMag2 ->] PwmDecoder (pwm_decoder.rs:385-513) over windows of a power or Complex stream (kernels_pwm.hip): no stream

@@ -508,6 +508,64 @@ struct LineArgs {
 };
 void launch_line(const LineArgs& a, hipStream_t s);
 
+// ---- kernels_kiss.hip: KissFrame -> KissDecode (kiss.rs:96-228) over the next n bytes of a stream, and KissEncode -> PduToStream
+//      (kiss.rs:247-286) over a batch of packets (kiss_core.hpp holds the arithmetic) ----------------------------------------------------
+// The VIRTUAL stream of a decode push: the st_in->carry bytes of the gap still open (cin), then bytes[0 .. n).  nv_max >= carry + n
+// is the host's own bound; it alone sizes the grids and the scratch: ntiles = ceil(nv_max / KISS_T) entries of sums / tin / tsum /
+// toff (tsum: 5 words a tile), ntiles + 1 of obase (all ones on entry).  Packets go to arena packed in stream order, their records
+// to recs in the same order, *count of them and *total bytes.  st_out / cout: what the next push starts from (distinct from st_in /
+// cin).  KISS_DECODE_LAUNCHES launches whatever the bytes hold; n == 0 launches nothing.
+constexpr int KISS_DECODE_LAUNCHES = 6, KISS_ENCODE_LAUNCHES = 3;
+struct KissState {
+    unsigned long long stats[5];              // frames, delivered, nondata, bad_escape, overlong so far
+    int code;                                 // KISS_VIRT / KISS_UNSYNC / KISS_OVER
+    unsigned carry;                           // carried bytes (KISS_VIRT only)
+};
+struct KissRec {                              // rr_kiss_packet
+    unsigned long long pos, start;
+    unsigned len, in_bytes, port, reserved;
+};
+struct KissArgs {
+    const unsigned char* bytes;
+    long n;
+    const unsigned char* cin;
+    unsigned char* cout;
+    const KissState* st_in;
+    KissState* st_out;
+    unsigned max_len;                         // bytes of cin / cout
+    long nv_max, ntiles;
+    unsigned long long w0;                    // stream position of bytes[0]
+    unsigned* sums;                           // 6 words a tile: its KissSum
+    unsigned* tin;                            // ... and the summary of everything in front of it
+    unsigned* root;                           // the summary of the whole virtual stream
+    unsigned* tsum;                           // packets, bytes, nondata, bad escapes, over-long gaps closed in the tile
+    unsigned* toff;                           // 2 words a tile: the packets and bytes in front of it
+    unsigned* obase;                          // where the gap opened by a tile's last FEND (slot tile + 1; 0: the carried one) goes
+    unsigned char* arena;
+    long arena_cap;
+    KissRec* recs;
+    long rec_cap;
+    unsigned long long* count;                // [0] packets, [1] arena bytes
+};
+void launch_kiss_decode(const KissArgs& a, hipStream_t s);
+// Packet p is bytes[starts[p] ..), pb[p] the bytes of the packets before it (pb[P] = nbytes), ports[p] its port.  The packets' bytes,
+// back to back, are cut into tiles of KISS_T: ntiles = max(1, ceil(nbytes / KISS_T)) entries of tcnt / tin.  cb[b], b <= P: the escaped
+// bytes in front of packet b; *total: the bytes of the push.  KISS_ENCODE_LAUNCHES launches whatever the packets hold; P == 0 none.
+struct KissEncArgs {
+    const unsigned char* bytes;
+    const unsigned long long* starts;
+    const unsigned long long* pb;
+    const unsigned long long* ports;
+    long P, nbytes, ntiles;
+    unsigned* tcnt;
+    unsigned* tin;
+    unsigned* cb;
+    unsigned long long* total;
+    unsigned char* out;
+    long cap;                                 // bytes of out: the bound of the push
+};
+void launch_kiss_encode(const KissEncArgs& a, hipStream_t s);
+
 // ---- kernels_hdlc.hip: HdlcDeframer (hdlc_deframer.rs:123-232) over the next n bits of a stream (hdlc_core.hpp holds the
 //      arithmetic) -------------------------------------------------------------------------------------------------------------------------
 // The VIRTUAL stream of a push: the st_in->count bits the stream so far left in cin (HDLC_HALO bits, then the raw bits of the gap

@@ -936,6 +936,88 @@ public:
     }
 };
 
+// ---- KissFrame -> KissDecode (src/kiss.rs:96-228): the message (PDU) form of its output --------------------------------------------------
+// (rr_kiss_decode_create / rr_kiss_decode_push / rr_kiss_packets / rr_kiss_packet_bytes / rr_kiss_decode_stats).  push() takes the
+// next bytes of the KISS stream and returns what the NCWriteStream<Vec<u8>> behind KissDecode receives for them: one (bytes, tags)
+// per packet whose closing FEND lay inside them, each with the three tags of :122-134.  Whether a FEND has been seen, the open
+// gap's bytes and the counters stay in the block from push to push; dst.remaining() (:99-101) has no counterpart.
+class KissDecode {
+    detail::Handle h_;
+public:
+    using Packet = std::pair<std::vector<uint8_t>, std::vector<Tag>>;
+    struct Stats { unsigned long long frames, delivered, nondata, bad_escape, overlong; };
+    explicit KissDecode(size_t max_len = 10000) : h_(rr_kiss_decode_create(max_len)) {}
+    rr_block* handle() const { return h_.h; }
+    std::vector<Packet> push(const std::vector<uint8_t>& bytes, std::vector<uint64_t>* pos = nullptr) {
+        if (rr_kiss_decode_push(h_.h, bytes.data(), bytes.size()) != 0) throw Error(rr_last_error());
+        size_t n = 0, nb = 0;
+        if (rr_kiss_packets(h_.h, nullptr, 0, &n) != 0) throw Error(rr_last_error());
+        std::vector<rr_kiss_packet> rec(n + 1);
+        if (n && rr_kiss_packets(h_.h, rec.data(), n, &n) != 0) throw Error(rr_last_error());
+        if (rr_kiss_packet_bytes(h_.h, nullptr, 0, &nb) != 0) throw Error(rr_last_error());
+        std::vector<uint8_t> arena(nb + 1);
+        if (n && nb && rr_kiss_packet_bytes(h_.h, arena.data(), nb, &nb) != 0) throw Error(rr_last_error());
+        std::vector<Packet> out(n);
+        if (pos) pos->assign(n, 0);
+        for (size_t i = 0; i < n; i++) {
+            if (rec[i].start > nb || rec[i].len > nb - rec[i].start) throw Error("KissDecode: packet outside the arena");
+            out[i].first.assign(arena.begin() + (long)rec[i].start, arena.begin() + (long)(rec[i].start + rec[i].len));
+            out[i].second.emplace_back(0, "KissDecode:port", (uint64_t)rec[i].port);
+            out[i].second.emplace_back(0, "KissDecode:input-bytes", (uint64_t)rec[i].in_bytes);
+            out[i].second.emplace_back(0, "KissDecode:output-bytes", (uint64_t)rec[i].len);
+            if (pos) (*pos)[i] = rec[i].pos;
+        }
+        return out;
+    }
+    Stats stats() {
+        unsigned long long s[5] = {0, 0, 0, 0, 0};
+        if (rr_kiss_decode_stats(h_.h, s) != 0) throw Error(rr_last_error());
+        return Stats{s[0], s[1], s[2], s[3], s[4]};
+    }
+    size_t carry_bytes() const {
+        size_t t = 0, c = 0, k = 0;
+        if (rr_kiss_decode_dims(h_.h, &t, &c, &k) != 0) throw Error(rr_last_error());
+        return c;
+    }
+};
+
+// ---- KissEncode -> PduToStream<u8> (src/kiss.rs:247-286, src/pdu_to_stream.rs:57-101) ---------------------------------------------------
+// (rr_kiss_encode_create / rr_kiss_encode_bound / rr_kiss_encode_push / rr_kiss_encode_records).  push() takes what the chain pops
+// in one go, every packet with its "KissEncode:port" (none: 0; 16 or more: 0), and returns the frames back to back with their
+// records.  The port byte is not escaped, as in the reference.
+class KissEncode {
+    detail::Handle h_;
+public:
+    struct Frames {
+        std::vector<uint8_t> stream;
+        std::vector<rr_kiss_frame_record> records;
+    };
+    KissEncode() : h_(rr_kiss_encode_create()) {}
+    rr_block* handle() const { return h_.h; }
+    Frames push(const std::vector<std::vector<uint8_t>>& packets, const std::vector<unsigned>& ports = {}) {
+        if (!ports.empty() && ports.size() != packets.size()) throw Error("KissEncode: one port per packet");
+        std::vector<size_t> starts(packets.size() + 1), lens(packets.size() + 1);
+        size_t total = 0;
+        for (size_t p = 0; p < packets.size(); p++) { starts[p] = total; lens[p] = packets[p].size(); total += lens[p]; }
+        std::vector<uint8_t> x(total + 1);
+        for (size_t p = 0; p < packets.size(); p++) std::copy(packets[p].begin(), packets[p].end(), x.begin() + (long)starts[p]);
+        const size_t cap = rr_kiss_encode_bound(lens.data(), packets.size());
+        Frames f;
+        f.stream.resize(cap + 1);
+        size_t produced = 0;
+        if (rr_kiss_encode_push(h_.h, x.data(), total, starts.data(), lens.data(), ports.empty() ? nullptr : ports.data(), packets.size(),
+                                f.stream.data(), cap, &produced) != 0)
+            throw Error(rr_last_error());
+        f.stream.resize(produced);
+        f.records.resize(packets.size() + 1);
+        size_t n = 0, again = 0;
+        if (rr_kiss_encode_records(h_.h, f.records.data(), packets.size(), &n, &again) != 0) throw Error(rr_last_error());
+        if (n != packets.size() || again != produced) throw Error("KissEncode: record count");
+        f.records.resize(n);
+        return f;
+    }
+};
+
 // ---- PwmDecoder (src/pwm_decoder.rs:165-266, 385-513): the builder and the frames of its NCWriteStream<PwmFrame> ------------------------
 // (rr_pwm_decoder_create / rr_pwm_decoder_push / rr_pwm_decoder_flush / rr_pwm_frames / rr_pwm_frame_bits).  The builder holds the
 // reference's defaults (:76-98) and build<T>() refuses what validate() refuses, in its words.  push() takes the next samples of the
