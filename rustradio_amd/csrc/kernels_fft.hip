@@ -308,6 +308,14 @@ __device__ __forceinline__ creg opaque_copy(creg a) {
     return a;
 }
 
+// a per-lane index the optimiser cannot see through: what is computed from it is not loop-invariant
+__device__ __forceinline__ int opaque_index(int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(i));
+#endif
+    return i;
+}
+
 // v[r] for a workgroup-uniform r in [LO, HI]: nested two-way branches (a `switch` the compiler flattens into a cascade of flag
 // tests) down to opaque copies (a plain selection it turns into a run-time index into v[], through scratch memory)
 template <int LO, int HI> __device__ __forceinline__ creg pick_row(const creg* v, int r) {
@@ -356,6 +364,132 @@ template <int T> struct TileStore {
     }
 };
 
+// ---- interior tiles of k_fftfilt_os ------------------------------------------------------------------
+// A tile is INTERIOR when its whole window lies inside src.in and all of it inside n_out: load_tile16's test and the
+// whole-tile test of the store both hold.  With v0 = tile * S that is plen <= v0 <= min(in_len + plen, n_out + first) - F:
+// one contiguous run of each workgroup's tile sequence, found once (k_fftfilt_os) and walked by a loop of its own that asks
+// no tile anything.  The window and the output are addressed through two running byte pointers, advanced by step * S *
+// sizeof(creg) per tile; no tile * S is formed.
+//
+// Bases: the 13-bit signed immediate of global_* reaches [-4096, 4096) around a scalar base, so a base in the MIDDLE of
+// 8 KiB of rows serves all of them (load_tile16 / TileStore take a base per 4 KiB and count upwards only): one scalar add
+// pair per 8 KiB and direction, derived from the running pointer by a constant.
+//
+// Rows: which rows of a tile are stored depends on first / T alone (TileStore).  The loop is instantiated per class
+// [LO, HI] of row0: rows above HI are stored without a test, rows LO+1 .. HI keep TileStore's scalar compare-and-branch
+// chain, row row0 takes the keep0 mask (LO == HI: its register is known, no pick_row).  RR_FFT_ROW_CLASS is the width of a
+// class: 1 = a loop per row0 and no row decision left in it, 16 = one loop with TileStore's whole chain (measurement builds).
+//
+// Which row0 get a loop of their own: those above RR_FFT_ROW_CHAIN_MAX = 1.  With row0 = 0 or 1, fourteen or fifteen
+// unconditional stores, the per-row0 loop measured 0.7 % SLOWER than the parent on FirFilter's 127 taps (fir_1e8, six rounds,
+// and both runs of bench.py --full) while the loop with the chain measured the same as the parent there: row0 <= 1 runs
+// interior_run<0, 15>, TileStore's whole chain on the running pointers.  Both forms are product code, and the row tests of
+// tests/test_gpu_fftfilter_interior.py run both on every tile size.  RR_FFT_ROW_CLASS and RR_FFT_STORE_GAP are measurement
+// switches like RR_FFT_ABLATE_BITS (make EXTRA=-D...): the product is built with their defaults only.
+//
+// Pace: the unconditional stores of a tile are NOT issued back to back.  Thirteen streaming stores in consecutive issue
+// slots measured 3.5 % SLOWER than TileStore's chain (0.3303 against 0.3192 ms per 1e8-sample step, at the same power cap
+// and a HIGHER clock, 2052 against 1988 MHz: the waves wait, they do not work) — the compare, branch and v_mov the chain
+// put between two stores had been pacing them.  RR_FFT_STORE_GAP is the s_nop operand behind each such store (7 = eight
+// idle cycles of this wave, issue slots the CU's other waves use; -1 = none, measurement builds): 0.3153 ms with it
+// (profiles/TUNING_LOG.md section 4.1).  That the waves wait on the stores is inferred from clock and time, no counter
+// was read.  FRAGILE: nothing but the scheduler's habit of keeping a volatile asm where it stands between two stores
+// holds the order store / s_nop / store; a compiler that regroups them gives the slow form back without a word.  After a
+// compiler update count them: tools/kernel_resources.py --loop 'k_fftfilt_os<11, 0, 0>' --spans 13 must show s_nop=37.
+#ifndef RR_FFT_ROW_CLASS
+#define RR_FFT_ROW_CLASS 1
+#endif
+#ifndef RR_FFT_ROW_CHAIN_MAX
+#define RR_FFT_ROW_CHAIN_MAX 1
+#endif
+#ifndef RR_FFT_STORE_GAP
+#define RR_FFT_STORE_GAP 7
+#endif
+template <int LOG2F> struct InteriorIO {
+    static constexpr int T = 1 << (LOG2F - 4);
+    static constexpr int ROWB = T * (int)sizeof(creg);
+    static constexpr int RB = 8192 / ROWB < 16 ? 8192 / ROWB : 16;        // rows per base
+    static constexpr int MIDB = (RB / 2) * ROWB;                          // the base's place inside its rows
+    static_assert(T <= 256 && RB >= 2 && MIDB <= 4096 && (RB - 1 - RB / 2) * ROWB < 4096, "a base reaches its rows by immediates");
+
+    __device__ __forceinline__ static void load(creg* v, const char* pin, unsigned lane) {
+        const unsigned l = lane_in_block(lane);
+#pragma unroll
+        for (int g = 0; g < 16; g += RB) {
+            const char* b = scalar_base(pin + g * ROWB + MIDB);
+#pragma unroll
+            for (int n = g; n < g + RB; n++) v[n] = *lane_at<creg>(b, l, (n - g) * ROWB - MIDB);
+        }
+    }
+    template <int LO, int HI>
+    __device__ __forceinline__ static void store(const char* pout, const creg* v, int row0, bool keep0, unsigned lane) {
+        const char* b[16 / RB];
+#pragma unroll
+        for (int g = 0; g < 16 / RB; g++) b[g] = scalar_base(pout + g * RB * ROWB + MIDB);
+        if constexpr (HI < 15) {
+            const unsigned l = lane_in_block(lane);
+#pragma unroll
+            for (int n = HI + 1; n < 16; n++) {
+                store_stream(lane_at_w<creg>(b[n / RB], l, (n % RB) * ROWB - MIDB), v[n]);
+#if RR_FFT_STORE_GAP >= 0 && defined(__HIP_DEVICE_COMPILE__)
+                asm volatile("s_nop %0" :: "n"(RR_FFT_STORE_GAP));      // (paced: see above)
+#endif
+            }
+        }
+        if constexpr (LO == HI) {
+            if (keep0) store_stream(lane_at_w<creg>(b[LO / RB], lane_in_block(lane), (LO % RB) * ROWB - MIDB), v[LO]);
+        } else {
+            int r0 = row0;                 // (re-read per tile, and the chain uniform from end to end: see TileStore)
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+s"(r0));
+#endif
+#pragma unroll
+            for (int n = LO + 1; n <= HI; n++)
+                if (n > r0) store_stream(lane_at_w<creg>(b[n / RB], lane_in_block(lane), (n % RB) * ROWB - MIDB), v[n]);
+            const creg edge = pick_row<LO, HI>(v, r0);
+            const char* b0 = scalar_base(pout + r0 * ROWB);
+            if (keep0) store_stream(lane_at_w<creg>(b0, lane_in_block(lane), 0), edge);
+        }
+    }
+};
+
+// The run of interior tiles whose window starts at pin and ends with the tile at pin_last (pin <= pin_last: at least one
+// tile); -> the number of tiles done.
+template <int LOG2F, int VAR, int FIX, int LO, int HI>
+__device__ __forceinline__ int interior_run(const TileXform<LOG2F, VAR>& X, creg* lds, const char* pin, const char* pout,
+                                            const char* pin_last, long stepb, const TileStore<(1 << (LOG2F - 4))>& st) {
+    int n = 0;
+    long left = pin_last - pin;                      // bytes to the last window; the loop bound stays in scalar registers
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(left));
+#endif
+    do {
+        creg v[16];
+        InteriorIO<LOG2F>::load(v, pin, st.lane);
+        RR_PHASE();
+        X.run(v, lds, 0);
+        if constexpr (FIX) nf_mark(nf_bad(v[15]));   // (a non-finite input makes every output of the tile non-finite)
+        InteriorIO<LOG2F>::template store<LO, HI>(pout, v, st.row0, st.keep0, st.lane);
+        RR_PHASE();
+        pin += stepb; pout += stepb; left -= stepb; n++;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(pin), "+s"(pout), "+s"(left));    // running values: not rewritten as base + n * stepb
+#endif
+    } while (left >= 0);
+    return n;
+}
+// row0 -> its class, by uniform two-way branches, once per run
+template <int LOG2F, int VAR, int FIX, int LO, int HI, class... A>
+__device__ __forceinline__ int interior_rows(int row0, const A&... a) {
+    if constexpr (HI - LO + 1 <= RR_FFT_ROW_CLASS) {
+        return interior_run<LOG2F, VAR, FIX, LO, HI>(a...);
+    } else {
+        constexpr int MID = (LO + HI) / 2;
+        if (row0 <= MID) return interior_rows<LOG2F, VAR, FIX, LO, MID>(row0, a...);
+        return interior_rows<LOG2F, VAR, FIX, MID + 1, HI>(row0, a...);
+    }
+}
+
 // ---- FftFilter -----------------------------------------------------------------------------------
 // (FIX 1: FirFilter on these tiles — nan_fix.hpp nf_finish; FIX 2: the FftFilter BLOCK — the reference's blocks, rb_finish;
 //  FIX 0: the chains and measurement builds carry none of it)
@@ -379,9 +513,37 @@ void k_fftfilt_os(NanFixCtx nfx, VSrc<cf> src, cf* __restrict__ out, long n_out,
     creg* out_reg = reinterpret_cast<creg*>(out);
     const TileStore<T> store_tile(first, t);
 
+    // Interior tiles (see InteriorIO) leave this loop for one of their own; what is left here are the edge tiles: at most
+    // the first few of a call (carry prefix, start of the stream) and the last two.  Measurement builds keep every tile here.
+    constexpr bool SPLIT = T <= 256 && RR_FFT_ABLATE_BITS == 0
+#ifdef RR_FFT_TIMING_BUILD
+                           && false
+#endif
+        ;
+    const long v_hi = (src.in_len + src.plen < n_out + first ? src.in_len + src.plen : n_out + first) - F;   // last interior v0
+
     int iter = 0;
     for (TileIter it(ntiles); it.tile < it.end; it.tile += it.step, iter++) {
         const long tile = tile_base + it.tile;           // (tile_base: a sub-range of the tiles, see launch_fftfilt_t32)
+        if constexpr (SPLIT) {
+            const long v0 = tile * S;
+            if (v0 >= src.plen && v0 <= v_hi) {
+                // the run ends with the last tile of the sequence or with the last interior window, whichever comes first
+                const long v_end = (tile_base + it.end - 1) * S;
+                const creg* in_reg = reinterpret_cast<const creg*>(src.in);
+                const int n = store_tile.row0 <= RR_FFT_ROW_CHAIN_MAX
+                    ? interior_run<LOG2F, VAR, FIX, 0, 15>(X, lds, reinterpret_cast<const char*>(in_reg + (v0 - src.plen)),
+                    reinterpret_cast<const char*>(out_reg + (v0 - first)),
+                    reinterpret_cast<const char*>(in_reg + ((v_end < v_hi ? v_end : v_hi) - src.plen)),
+                    it.step * S * (long)sizeof(creg), store_tile)
+                    : interior_rows<LOG2F, VAR, FIX, 0, 15>(store_tile.row0, X, lds, reinterpret_cast<const char*>(in_reg + (v0 - src.plen)),
+                    reinterpret_cast<const char*>(out_reg + (v0 - first)),
+                    reinterpret_cast<const char*>(in_reg + ((v_end < v_hi ? v_end : v_hi) - src.plen)),
+                    it.step * S * (long)sizeof(creg), store_tile);
+                it.tile += (n - 1) * it.step;             // (the latch adds the last step)
+                continue;
+            }
+        }
 #ifdef RR_FFT_TIMING_BUILD
         unsigned long long* stamps = (dbg && blockIdx.x == 0 && t == 0 && iter == 2) ? dbg : nullptr;
 #else
@@ -423,10 +585,13 @@ void k_fftfilt_os(NanFixCtx nfx, VSrc<cf> src, cf* __restrict__ out, long n_out,
                 }
             }
         } else {
-            creg* po = out_reg + o0 + t;
+            // (the thread index re-read per edge tile: left loop-invariant, sixteen 64-bit positions and sixteen lane masks
+            //  of this store are hoisted out of the tile loop and live across the interior tiles' loop, which spilled them)
+            const int te = SPLIT ? opaque_index(t) : t;
+            creg* po = out_reg + o0 + te;
 #pragma unroll
             for (int n = 0; n < 16; n++) {
-                const int idx = n * T + t;
+                const int idx = n * T + te;
                 if (idx >= first && o0 + idx < n_out) po[n * T] = v[n];
             }
         }

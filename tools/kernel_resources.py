@@ -12,6 +12,8 @@
               branch and its target) that holds the most packed-f32 instructions, innermost on a tie.  One line per basic block
               of the loop and the sum; --blocks sums a chosen subset instead (block numbers as printed), which is how the
               steady-state path is counted apart from the boundary-tile blocks that sit in the same loop.
+--spans N   : with --loop: every backward-branch span of that kernel with exactly N global stores, one line each (-1: all
+              spans with packed math) — the per-row0 interior loops of k_fftfilt_os are nested in the loop --loop picks
 --no-build  : read DIR/<name>.s as it is
 
 A tile kernel that starts to spill is 1.5-2x slower (every scratch access waits on the whole in-order vmcnt queue,
@@ -128,7 +130,26 @@ def parse_blocks(sel):
     return out
 
 
-def loop_report(path, want, blocks):
+def span_report(lines, stores, title):
+    """every backward-branch span of the kernel that holds packed math and exactly `stores` global stores (all of them
+    when stores < 0), counted line by line: the per-row0 interior loops of k_fftfilt_os are such spans, nested in the
+    edge-tile loop that --loop alone reports"""
+    label_at = {m.group(1): i for i, ln in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", ln)] if m}
+    print(title, "- backward-branch spans" + (f" with {stores} global stores" if stores >= 0 else ""))
+    for i, ln in enumerate(lines):
+        m = re.match(r"^\s+s_c?branch\S*\s+(\.LBB\d+_\d+)", ln)
+        if not m or label_at.get(m.group(1), i + 1) > i:
+            continue
+        h = dict.fromkeys(CLASSES, 0)
+        for t in (x.split(";")[0].strip() for x in lines[label_at[m.group(1)]:i + 1]):
+            if t and not t.startswith(".") and not t.startswith(";"):
+                ins, _, ops = t.partition(" ")
+                h[classify(ins, ops)] += 1
+        if h["pk_f32"] and (stores < 0 or h["gstore"] == stores):
+            print(f"{m.group(1):12s} " + " ".join(f"{c}={v}" for c, v in h.items() if v) + f" total={sum(h.values())}")
+
+
+def loop_report(path, want, blocks, stores=None):
     txt = open(path, errors="replace").read()
     names = list(parse(path))
     dm = demangle(names)
@@ -136,6 +157,8 @@ def loop_report(path, want, blocks):
     if len(hits) != 1:
         sys.exit(f"{want!r} matches {len(hits)} kernels of {os.path.basename(path)}: " + ", ".join(re.sub(r"\(.*", "", dm[k]) for k in hits[:8]))
     lines = kernel_body(txt, hits[0])
+    if stores is not None:
+        return span_report(lines, stores, re.sub(r"\(.*", "", dm[hits[0]]).replace("void rr::", ""))
     lo, hi = tile_loop(lines)
     # the loop's blocks: the header and every block the compiler marks "in Loop: Header=<it>" (some are laid out behind the
     # backward branch), blocks of loops nested in it included
@@ -188,6 +211,9 @@ def main():
     ap.add_argument("--extra", default="", help="extra compiler flags, e.g. -DRR_POLY_NB=2")
     ap.add_argument("--loop", default=None, help="demangled kernel name (substring): histogram of its tile loop")
     ap.add_argument("--blocks", default=None, help="with --loop: sum only these basic blocks, e.g. 0-3,7")
+    ap.add_argument("--spans", type=int, default=None, metavar="N",
+                    help="with --loop: one line per backward-branch span of the kernel that holds exactly N global stores "
+                         "(-1: every span with packed math) instead of the one loop --loop picks")
     ap.add_argument("--no-build", action="store_true", help="use the assembly already in --build DIR")
     ap.add_argument("files", nargs="*")
     a = ap.parse_args()
@@ -198,7 +224,7 @@ def main():
         for f in files:
             sp = os.path.join(a.build, os.path.basename(f).replace(".hip", ".s"))
             if any(a.loop in v for v in demangle(list(parse(sp))).values()):
-                return loop_report(sp, a.loop, parse_blocks(a.blocks) if a.blocks else None)
+                return loop_report(sp, a.loop, parse_blocks(a.blocks) if a.blocks else None, a.spans)
         sys.exit(f"no kernel named like {a.loop!r}")
     bad = 0
     for f in files:
