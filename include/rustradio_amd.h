@@ -674,6 +674,70 @@ int rr_hdlc_receiver_consumed(rr_block *b, unsigned long long *symbols, size_t c
 /* *tile_bits, *carry_bits: as rr_hdlc_deframer_dims, for every stream. */
 int rr_hdlc_receiver_dims(const rr_block *b, size_t *tile_bits, size_t *carry_bits);
 
+/* BinarySlicer (src/binary_slicer.rs:17-19) -> [XorConst(1)] -> CorrelateAccessCodeTag::new(il2p_deframer::SYNC_WORD, "sync",
+ * allowed_diffs) (src/correlate_access_code.rs:93-118) -> Il2pDeframer (src/il2p_deframer.rs:172-237, 247-319) x nstreams, as
+ * wired in examples/il2p-1200-rx.rs:118-137: the consumer of rr_symbol_sync for IL2P.  One handle takes the ragged symbol windows
+ * of nstreams streams, with their counts read on the device, and delivers the parsed headers of all of them in three launches
+ * whatever nstreams and the symbols are; each stream's state (its position, the bits-seen count, how far the open header still
+ * blocks, its last 192 sliced bits as three words) stays on the device.  rr_fm_multi -> rr_afsk_demod -> rr_symbol_sync ->
+ * rr_il2p_receiver is the whole graph of il2p-1200-rx for N channels, with no host round trip before the headers.
+ * A batch block like rr_hdlc_receiver: rr_block_work on the handle is an error.
+ * EXACT, per stream and whatever the split into pushes and the other streams hold: b[i] = (x[i] > 0.0f) ^ invert (NaN, +-0.0 and
+ * -Inf slice to 0 before the inversion); position i carries a tag when 24 bits of the stream have been seen and b[i-23 ..= i]
+ * differs from SYNC_WORD (0xF15E48, oldest bit first) in at most allowed_diffs places; the first tag at p >= free_from (0 at the
+ * start) is accepted, its header is the 120 bits b[p+1 .. p+121), then free_from = p + 121; every other tag is dropped.  The
+ * header is descrambled (Lfsr::new(0x108, 0x1f0), :101-128, 257), packed MSB first into 15 bytes (:130-141) and its first 13 bytes
+ * parsed as Header::parse (:289-319) with decode_callsign (:265-274).  The reference strips the 2 parity bytes unchecked (TODO at
+ * :209) and delivers no payload (TODO at :186); so does this block, and it keeps the parity bytes in raw.
+ * NULL + rr_last_error, said before any device is touched: "nstreams out of range" (0 or above 4096), "il2p receiver: unknown bit
+ * flags" (anything other than 0 or RR_BITS_INVERT).  allowed_diffs takes any value; 24 and above: every position from 23 on matches.
+ * Device memory: 2 * 64 bytes of state per stream live as long as the handle (rr_il2p_receiver_dims: carry_bits = 192).
+ * NOT TESTED: a push of 2^30 symbols; more than 4096 tiles in one stream on the device. */
+typedef struct {
+    unsigned long long pos;      /* stream position (that stream's own symbols) of the sync tag: the sync word's last bit */
+    unsigned stream;
+    unsigned short payload_size; /* 10 bits */
+    unsigned char pid;           /* 4 bits */
+    unsigned char control;       /* 7 bits */
+    unsigned char flags;         /* bit 0 ui, bit 1 fec, bit 2 hdrtype1 */
+    unsigned char diffs;         /* the tag's value */
+    unsigned char dst_ssid, src_ssid;
+    unsigned char raw[15];       /* the descrambled header, its 2 parity bytes last (kept: a host may run the RS check) */
+    char dst[7], src[7];         /* decode_callsign, NUL padded */
+    unsigned char reserved[15];  /* 0 */
+} rr_il2p_header;                /* 64 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(rr_il2p_header) == 64, "rr_il2p_header is 64 bytes");
+#else
+_Static_assert(sizeof(rr_il2p_header) == 64, "rr_il2p_header is 64 bytes");
+#endif
+rr_block *rr_il2p_receiver_create(size_t nstreams, int bit_flags /* RR_BITS_INVERT or 0 */, size_t allowed_diffs);
+/* stream c: the next min(d_counts[c], n_cap) f32 symbols at d_syms + c*stride, the layout rr_symbol_sync_push_dev writes.
+ * d_counts: unsigned long long[nstreams] on the device, the pointer rr_symbol_sync_counts_dev returns, read there and clamped to
+ * n_cap before it is used; NULL: every stream has n_cap.  Elements at and beyond a stream's count are never read.  A stream whose
+ * count is 0 keeps every piece of its state.  RR_ERR before any device is touched: "il2p receiver: stride shorter than n_cap",
+ * "il2p receiver: more than 2^30 symbols in one push" (nstreams * n_cap), "il2p receiver: null symbols" (n_cap > 0 with a null
+ * buffer).  n_cap == 0 launches nothing, has no headers and leaves every state alone.  Asynchronous on hip_stream (used as given). */
+int rr_il2p_receiver_push_dev(rr_block *b, const void *d_syms, size_t stride, size_t n_cap, const void *d_counts, void *hip_stream);
+/* The same with host pointers (counts may be NULL): copies symbols and counts down, runs and waits. */
+int rr_il2p_receiver_push(rr_block *b, const float *syms, size_t stride, size_t n_cap, const size_t *counts /* [nstreams] or NULL */);
+/* The headers of all streams whose 120th bit lay inside the most recent push (il2p_deframer.rs:206-213), ascending by (stream,
+ * pos).  Waits for that push, writes the first min(*total, cap) records; rec == NULL with cap == 0 only counts (the contract of
+ * rr_wpcr_results).  The list holds floor((n_cap + 119) / 121) + 1 records per stream, more than a push can emit, so no record is
+ * ever dropped.  Everything the device wrote — the record count, every record's stream, its position inside that stream's range of
+ * the push, positions of one stream at least 121 apart, the fields' ranges — is checked against the host's own bounds before it is
+ * used ("il2p receiver: ..." and no headers otherwise). */
+int rr_il2p_receiver_headers(rr_block *b, rr_il2p_header *rec, size_t cap, size_t *total);
+/* headers delivered and sync tags seen (accepted or not, correlate_access_code.rs:110-116) of every stream since creation; waits
+ * for the most recent push.  *total = nstreams, the first min(*total, cap) of each array written (the contract of
+ * rr_symbol_sync_produced); an array may be NULL. */
+int rr_il2p_receiver_stats(rr_block *b, unsigned long long *headers, unsigned long long *syncs, size_t cap, size_t *total);
+/* symbols every stream has taken so far (its stream position); waits for the most recent push.  Same contract. */
+int rr_il2p_receiver_consumed(rr_block *b, unsigned long long *symbols, size_t cap, size_t *total);
+/* *tile_bits: symbols of one tile of the kernels; *carry_bits: sliced bits every stream keeps between pushes (23 for the
+ * correlator, 120 for an open header's tag and bits, rounded up to words) */
+int rr_il2p_receiver_dims(const rr_block *b, size_t *tile_bits, size_t *carry_bits);
+
 /* [ComplexToMag2 ->] PwmDecoder::builder(high_threshold, short_width, long_width, frame_gap, reset_gap) with every builder
  * setting (src/pwm_decoder.rs:165-266; process :385-513): OOK power samples in, PWM frames out, the whole graph of
  * examples/restaurant_pager.rs behind one handle.  A batch block like rr_hdlc_deframer: rr_block_work on the handle is an error.

@@ -162,6 +162,19 @@ unsafe extern "C" {
     fn rr_hdlc_receiver_consumed(b: *mut RrBlock, symbols: *mut u64, cap: usize, total: *mut usize) -> c_int;
     #[allow(dead_code)]
     fn rr_hdlc_receiver_dims(b: *const RrBlock, tile_bits: *mut usize, carry_bits: *mut usize) -> c_int;
+    // (declared for completeness: the same for N Il2pDeframers; rr_il2p_receiver_headers (a struct) and _push (a size_t array in)
+    //  have types outside this file's FFI map; not written yet)
+    #[allow(dead_code)]
+    fn rr_il2p_receiver_create(nstreams: usize, bit_flags: c_int, allowed_diffs: usize) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_il2p_receiver_push_dev(b: *mut RrBlock, d_syms: *const c_void, stride: usize, n_cap: usize, d_counts: *const c_void,
+                                 hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_il2p_receiver_stats(b: *mut RrBlock, headers: *mut u64, syncs: *mut u64, cap: usize, total: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_il2p_receiver_consumed(b: *mut RrBlock, symbols: *mut u64, cap: usize, total: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_il2p_receiver_dims(b: *const RrBlock, tile_bits: *mut usize, carry_bits: *mut usize) -> c_int;
     // (declared for completeness: PwmDecoder's dst is an NCWriteStream<PwmFrame>, a message stream, so its block is not one of the
     //  window blocks below; rr_pwm_frames (a struct) and rr_pwm_frame_bits (byte pointers) have types outside this file's FFI map;
     //  not written yet)

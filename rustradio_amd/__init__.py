@@ -1137,6 +1137,72 @@ class HdlcReceiver(Block):
         return _fetch(lib().rr_hdlc_receiver_consumed, self._h, np.uint64)[0]
 
 
+# rr_il2p_header
+IL2P_HEADER = np.dtype({"names": ["pos", "stream", "payload_size", "pid", "control", "flags", "diffs", "dst_ssid", "src_ssid", "raw",
+                                  "dst", "src", "reserved"],
+                        "formats": [np.uint64, np.uint32, np.uint16, np.uint8, np.uint8, np.uint8, np.uint8, np.uint8, np.uint8,
+                                    (np.uint8, 15), "S7", "S7", (np.uint8, 15)],
+                        "offsets": [0, 8, 12, 14, 15, 16, 17, 18, 19, 20, 35, 42, 49], "itemsize": 64})
+
+
+class Il2pReceiver(Block):
+    """BinarySlicer -> [XorConst(1)] -> CorrelateAccessCodeTag(il2p SYNC_WORD, "sync", allowed_diffs) -> Il2pDeframer x nstreams
+    behind one handle (rr_il2p_receiver_create; examples/il2p-1200-rx.rs:118-137; not a stream block: work() raises): the ragged
+    symbol windows SymbolSync leaves on the device in, with their counts read there, the parsed IL2P headers of all streams out.
+    Every stream's state stays on the device between pushes.  See include/rustradio_amd.h."""
+
+    def __init__(self, nstreams: int, invert: bool = False, allowed_diffs: int = 0, bit_flags=None):
+        bits = (BITS_INVERT if invert else 0) if bit_flags is None else int(bit_flags)
+        super().__init__(lib().rr_il2p_receiver_create(int(nstreams), bits, int(allowed_diffs)), np.float32, np.uint8)
+        self.nstreams, self.allowed_diffs = int(nstreams), int(allowed_diffs)
+
+    def dims(self):
+        """-> (tile_bits, carry_bits) (rr_il2p_receiver_dims)"""
+        t, c = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_il2p_receiver_dims(self._h, C.byref(t), C.byref(c)) != 0:
+            raise RuntimeError(last_error())
+        return t.value, c.value
+
+    def push_dev(self, d_syms: int, stride: int, n_cap: int, d_counts=None, stream: int = 0) -> None:
+        """rr_il2p_receiver_push_dev: stream c's next min(d_counts[c], n_cap) symbols at d_syms + c * stride (raw device pointers;
+        d_counts: unsigned long long[nstreams], SymbolSync.counts_dev(), or None: n_cap each); asynchronous on `stream`;
+        headers() waits"""
+        if lib().rr_il2p_receiver_push_dev(self._h, C.c_void_p(d_syms) if d_syms else None, int(stride), int(n_cap),
+                                           C.c_void_p(d_counts) if d_counts else None, C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+
+    def push(self, syms, counts=None):
+        """rr_il2p_receiver_push on a host array of shape (nstreams, n_cap) (or (n_cap,) for one stream), of which stream c
+        holds counts[c] symbols (None: n_cap) -> headers()"""
+        a = np.ascontiguousarray(syms, np.float32)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        if a.ndim != 2 or a.shape[0] != self.nstreams:
+            raise ValueError("Il2pReceiver.push: one row per stream")
+        n = a.shape[1]
+        k = None
+        if counts is not None:
+            if len(counts) != self.nstreams:
+                raise ValueError("Il2pReceiver.push: one count per stream")
+            k = (C.c_size_t * self.nstreams)(*[int(v) for v in counts])
+        if lib().rr_il2p_receiver_push(self._h, _ptr(a) if n else None, n, n, k) != 0:
+            raise ValueError(last_error())
+        return self.headers()
+
+    def headers(self) -> np.ndarray:
+        """-> IL2P_HEADER per header whose 120th bit lay in the most recent push, ascending by (stream, pos)
+        (rr_il2p_receiver_headers; waits)"""
+        return _fetch(lib().rr_il2p_receiver_headers, self._h, IL2P_HEADER)[0]
+
+    def stats(self) -> np.ndarray:
+        """-> uint64[nstreams, 2]: headers delivered, sync tags seen of every stream so far (rr_il2p_receiver_stats; waits)"""
+        h, s = _fetch(lib().rr_il2p_receiver_stats, self._h, np.uint64, np.uint64)
+        return np.stack([h, s], axis=1)
+
+    def consumed(self) -> np.ndarray:
+        """-> uint64[nstreams]: symbols every stream has taken so far (rr_il2p_receiver_consumed; waits)"""
+        return _fetch(lib().rr_il2p_receiver_consumed, self._h, np.uint64)[0]
+
+
 class SymbolSync(Block):
     """SymbolSync::new(src, sps, max_deviation, TedZeroCrossing, IirFilter::new(taps)) x nstreams behind one handle
     (rr_symbol_sync_create; src/symbol_sync.rs:46-217; not a stream block: work() raises): the next n samples of each stream in,

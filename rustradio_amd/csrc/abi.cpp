@@ -14,6 +14,7 @@
 #include "frame_host.hpp"
 #include "hdlc_host.hpp"
 #include "hdlcrx_host.hpp"
+#include "il2p_host.hpp"
 #include "kiss_core.hpp"
 #include "kiss_host.hpp"
 #include "pdu_host.hpp"
@@ -86,6 +87,7 @@ template <class T> static T* as(const rr_block* b, const char* what, const char*
 static const char NOT_WPCR[] = "not a wpcr handle", NOT_PDU[] = "not a stream_to_pdu handle", NOT_FRAMER[] = "not an hdlc framer handle";
 static const char NOT_DEFRAMER[] = "not an hdlc deframer handle", NOT_SYNC[] = "not a symbol sync handle", NOT_AFSK[] = "not an afsk demod handle";
 static const char NOT_RECEIVER[] = "not an hdlc receiver handle", NOT_PWM[] = "not a pwm decoder handle";
+static const char NOT_IL2P[] = "not an il2p receiver handle";
 static const char NOT_FSK[] = "not an fsk tx handle", NOT_FSKM[] = "not an fsk tx multi handle";
 static const char NOT_KISSDEC[] = "not a kiss decode handle", NOT_KISSENC[] = "not a kiss encode handle";
 // a fetched list of (pos << shift) | val entries into the caller's two arrays
@@ -757,6 +759,61 @@ int rr_hdlc_receiver_dims(const rr_block* b, size_t* tile_bits, size_t* carry_bi
     if (!d || !tile_bits || !carry_bits) { if (d) rr::set_last_error("rr_hdlc_receiver_dims: null argument"); return RR_ERR; }
     *tile_bits = rr::HDLC_T;
     *carry_bits = rr::hdlc_carry_bits(d->core.max_size);
+    return 0;
+}
+// Il2pReceiver: BinarySlicer -> [XorConst(1)] -> CorrelateAccessCodeTag(SYNC_WORD) -> Il2pDeframer x nstreams (binary_slicer.rs:17-19,
+// correlate_access_code.rs:93-118, il2p_deframer.rs:172-237, 247-319; examples/il2p-1200-rx.rs:118-137)
+rr_block* rr_il2p_receiver_create(size_t nstreams, int bit_flags, size_t allowed_diffs) {
+    if (const char* e = rr::il2p_check_create(nstreams, bit_flags)) return refuse_create(e);
+    return make_block([&] { return new rr::Il2pReceiver(nstreams, bit_flags, allowed_diffs); });
+}
+// one Il2pDeframer::work() sweep of every stream (il2p_deframer.rs:172-237) over symbols that are already on the device
+int rr_il2p_receiver_push_dev(rr_block* b, const void* d_syms, size_t stride, size_t n_cap, const void* d_counts, void* hip_stream) {
+    auto* d = as<rr::Il2pReceiver>(b, "rr_il2p_receiver_push_dev", NOT_IL2P);
+    if (!d) return RR_ERR;
+    if (const char* e = rr::il2p_check_push(d->nstreams, d_syms, stride, n_cap)) { rr::set_last_error(e); return RR_ERR; }   // before any device is touched
+    return on_device(d, hip_stream, [&](hipStream_t s) {
+        d->push_dev(static_cast<const float*>(d_syms), stride, n_cap, static_cast<const unsigned long long*>(d_counts), s);
+    });
+}
+int rr_il2p_receiver_push(rr_block* b, const float* syms, size_t stride, size_t n_cap, const size_t* counts) {
+    auto* d = as<rr::Il2pReceiver>(b, "rr_il2p_receiver_push", NOT_IL2P);
+    if (!d) return RR_ERR;
+    if (const char* e = rr::il2p_check_push(d->nstreams, syms, stride, n_cap)) { rr::set_last_error(e); return RR_ERR; }
+    return guarded([&] { d->push_host(syms, stride, n_cap, counts); });
+}
+// what il2p_deframer.rs:206-213 parses (and :221-231 only logs): the headers that completed inside the most recent push
+int rr_il2p_receiver_headers(rr_block* b, rr_il2p_header* rec, size_t cap, size_t* total) {
+    auto* d = as<rr::Il2pReceiver>(b, "rr_il2p_receiver_headers", NOT_IL2P);
+    if (!d) return RR_ERR;
+    if (!total || (cap && !rec)) { rr::set_last_error("rr_il2p_receiver_headers: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] { rr::il2p_copy_headers(d->fetch_headers(), rec, cap, total); });
+}
+// il2p_deframer.rs:160 (decoded) and the tags of correlate_access_code.rs:110-116, per stream
+int rr_il2p_receiver_stats(rr_block* b, unsigned long long* headers, unsigned long long* syncs, size_t cap, size_t* total) {
+    auto* d = as<rr::Il2pReceiver>(b, "rr_il2p_receiver_stats", NOT_IL2P);
+    if (!d) return RR_ERR;
+    if (!total) { rr::set_last_error("rr_il2p_receiver_stats: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] {
+        const std::vector<unsigned long long> s = d->fetch_stats();
+        rr::il2p_copy_u64(s, 0, 2, headers, cap, total);
+        rr::il2p_copy_u64(s, 1, 2, syncs, cap, total);
+    });
+}
+int rr_il2p_receiver_consumed(rr_block* b, unsigned long long* symbols, size_t cap, size_t* total) {
+    auto* d = as<rr::Il2pReceiver>(b, "rr_il2p_receiver_consumed", NOT_IL2P);
+    if (!d) return RR_ERR;
+    if (!total || (cap && !symbols)) { rr::set_last_error("rr_il2p_receiver_consumed: null argument"); return RR_ERR; }
+    *total = 0;
+    return on_device(d, [&] { rr::il2p_copy_u64(d->fetch_consumed(), 0, 1, symbols, cap, total); });
+}
+int rr_il2p_receiver_dims(const rr_block* b, size_t* tile_bits, size_t* carry_bits) {
+    auto* d = as<rr::Il2pReceiver>(b, "rr_il2p_receiver_dims", NOT_IL2P);
+    if (!d || !tile_bits || !carry_bits) { if (d) rr::set_last_error("rr_il2p_receiver_dims: null argument"); return RR_ERR; }
+    *tile_bits = rr::IL2P_T;
+    *carry_bits = rr::IL2P_CARRY;
     return 0;
 }
 rr_block* rr_symbol_sync_create(float sps, float max_deviation, const float* taps, size_t ntaps, size_t nstreams) {

@@ -1095,6 +1095,99 @@ std::vector<unsigned long long> HdlcReceiver::positions(const unsigned long long
     return out;
 }
 
+// ---- Il2pReceiver (binary_slicer.rs:17-19, correlate_access_code.rs:93-118, il2p_deframer.rs:172-237, 247-319; kernels_il2p.hip) ----------
+Il2pReceiver::Il2pReceiver(size_t ns, int bit_flags, size_t allowed_diffs)
+    : BatchBlock("Il2pReceiver", 4, 1, "Il2pReceiver delivers headers: rr_il2p_receiver_push / rr_il2p_receiver_push_dev"),
+      nstreams(ns), invert((bit_flags & RR_BITS_INVERT) != 0), allowed(il2p_clamp_allowed(allowed_diffs)) {
+    if (const char* e = il2p_check_create(ns, bit_flags)) throw Error(e);
+    st.zero(ns * IL2P_ST_N, stream);              // no symbol taken, no bit seen, nothing blocked, no history (il2p_deframer.rs:143-149)
+    stats.reserve(2 * ns);
+    RR_HIP(hipMemsetAsync(stats.p, 0, 2 * ns * sizeof(unsigned long long), stream));
+    count.reserve(1);
+    RR_HIP(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), stream));
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void Il2pReceiver::push_dev(const float* d_syms, size_t stride, size_t n_cap, const unsigned long long* d_counts, hipStream_t s) {
+    if (const char* e = il2p_check_push(nstreams, d_syms, stride, n_cap)) throw Error(e);
+    headers.clear();
+    fetched = true;                            // a push of no symbols has no headers and leaves every state alone
+    last_n = n_cap;
+    if (!n_cap) return;
+    const Il2pBounds bd = il2p_bounds(nstreams, n_cap);
+    bits.reserve(nstreams * bd.words);
+    mw.reserve(nstreams * bd.tiles * IL2P_TW);
+    maps.reserve(nstreams * bd.tiles * IL2P_MAP_PITCH);
+    entry.reserve(nstreams * bd.tiles);
+    recs.reserve(std::max<size_t>(bd.headers, 1));
+    Il2pArgs a{};
+    a.syms = d_syms; a.stride = (long)stride; a.n_cap = (long)n_cap; a.nstreams = (long)nstreams; a.counts = d_counts;
+    a.invert = invert; a.allowed = allowed;
+    a.st_in = st.in(); a.st_out = st.out();
+    a.bits = bits.p; a.mw = mw.p; a.p_words = (long)bd.words; a.ntiles = (long)bd.tiles;
+    a.maps = maps.p; a.entry = entry.p;
+    a.recs = recs.p; a.rec_cap = (long)bd.headers; a.count = count.p; a.stats = stats.p;
+    prof_begin(s);
+    RR_HIP(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), s));
+    launch_il2p(a, s);
+    prof_end(s);
+    st.flip();
+    fetched = false;
+}
+void Il2pReceiver::push_host(const float* syms, size_t stride, size_t n_cap, const size_t* counts) {
+    host_call([&] {
+        if (const char* e = il2p_check_push(nstreams, syms, stride, n_cap)) throw Error(e);
+        if (n_cap) {
+            // only what the counts cover is read from the caller's buffer, as on the device
+            h_syms.reserve(nstreams * n_cap);
+            std::vector<unsigned long long> k(nstreams, n_cap);
+            for (size_t c = 0; c < nstreams; c++) {
+                if (counts) k[c] = std::min<unsigned long long>(counts[c], n_cap);
+                if (k[c]) hstage().h2d(h_syms.p + c * n_cap, syms + c * stride, (size_t)k[c] * sizeof(float), stream);
+            }
+            if (counts) {
+                h_counts.reserve(nstreams);
+                hstage().h2d(h_counts.p, k.data(), nstreams * sizeof(unsigned long long), stream);
+            }
+        }
+        push_dev(h_syms.p, n_cap, n_cap, counts ? h_counts.p : nullptr, stream);
+    });
+}
+const std::vector<rr_il2p_header>& Il2pReceiver::fetch_headers() {
+    settle();
+    if (!fetched) {
+        fetched = true;                        // (a refused push has no headers: the refusal is not repeated)
+        const Il2pBounds bd = il2p_bounds(nstreams, last_n);
+        unsigned long long k = 0;
+        stage_download_sync(&k, count.p, sizeof k, stream);
+        if (const char* e = il2p_check_count(k, bd)) throw Error(e);
+        std::vector<rr_il2p_header> r((size_t)k);
+        if (k) stage_download_sync(r.data(), recs.p, (size_t)k * sizeof(rr_il2p_header), stream);
+        // the pair's other half holds what the push started from
+        const std::vector<unsigned long long> p1 = positions(st.in()), p0 = positions(st.out());
+        std::vector<size_t> moved;
+        if (const char* e = il2p_clamp_consumed(p0.data(), p1.data(), nstreams, last_n, moved)) throw Error(e);
+        if (const char* e = il2p_validate(r, bd, p0.data(), moved.data())) throw Error(e);
+        headers.swap(r);
+    }
+    return headers;
+}
+std::vector<unsigned long long> Il2pReceiver::fetch_stats() {
+    settle();
+    std::vector<unsigned long long> v(2 * nstreams);
+    stage_download_sync(v.data(), stats.p, v.size() * sizeof(unsigned long long), stream);
+    return v;
+}
+std::vector<unsigned long long> Il2pReceiver::fetch_consumed() {
+    settle();
+    return positions(st.in());
+}
+std::vector<unsigned long long> Il2pReceiver::positions(const unsigned long long* d_st) const {
+    std::vector<unsigned long long> b(nstreams * IL2P_ST_N), out(nstreams);
+    stage_download_sync(b.data(), d_st, b.size() * sizeof(unsigned long long), stream);
+    for (size_t c = 0; c < out.size(); c++) out[c] = b[c * IL2P_ST_N + IL2P_ST_POS];
+    return out;
+}
+
 // ---- AfskDemod (hilbert.rs:38-61, quadrature_demod.rs:65-109, fft_filter.rs:365-491, add_const.rs:51-68; kernels_afsk.hip) ---------------
 AfskDemod::AfskDemod(size_t ns, size_t hilbert_ntaps, int window, float window_parm, float gn, const float* taps, size_t ntaps, float off)
     : BatchBlock("Hilbert>QuadratureDemod>FftFilterFloat>AddConst", 4, 4,

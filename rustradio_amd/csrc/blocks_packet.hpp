@@ -2,6 +2,7 @@
 #pragma once
 #include "blocks.hpp"
 #include "hdlcrx_host.hpp"
+#include "il2p_host.hpp"
 #include "pwm_host.hpp"
 #include "afsk_host.hpp"
 #include "fsk_host.hpp"
@@ -445,6 +446,32 @@ struct HdlcReceiver : BatchBlock {
     std::vector<unsigned long long> fetch_stats();            // 3 per stream
     std::vector<unsigned long long> fetch_consumed();         // 1 per stream
     std::vector<unsigned long long> positions(const unsigned long long* d_bst) const;    // RX_ST_POS of every stream, one download
+};
+
+// BinarySlicer -> [XorConst(1)] -> CorrelateAccessCodeTag(il2p SYNC_WORD) -> Il2pDeframer x nstreams over ragged windows of nstreams
+// f32 symbol streams (kernels_il2p.hip, il2p_core.hpp): no stream protocol (work_dev is an error).  Each stream's state between
+// pushes (IL2P_ST_*: position, bits seen, how far the open header blocks, the last IL2P_CARRY bits) stays on the device as a pair;
+// the host keeps only the geometry of the most recent push.
+struct Il2pReceiver : BatchBlock {
+    size_t nstreams;
+    int invert;
+    unsigned allowed;                             // allowed_diffs, clamped to 24
+    Carried<unsigned long long> st;               // in(): IL2P_ST_N words per stream
+    DevBuf<unsigned long long> bits, mw, count, stats;   // stats: headers, syncs per stream since creation
+    DevBuf<unsigned char> maps, entry;
+    DevBuf<Il2pRec> recs;
+    DevBuf<float> h_syms;                         // push_host(): the host buffers' device copies
+    DevBuf<unsigned long long> h_counts;
+    size_t last_n = 0;                            // n_cap of the most recent push
+    bool fetched = true;                          // `headers` holds the most recent push's
+    std::vector<rr_il2p_header> headers;          // ... ascending by (stream, pos)
+    Il2pReceiver(size_t nstreams, int bit_flags, size_t allowed_diffs);
+    void push_dev(const float* d_syms, size_t stride, size_t n_cap, const unsigned long long* d_counts, hipStream_t s);
+    void push_host(const float* syms, size_t stride, size_t n_cap, const size_t* counts);
+    const std::vector<rr_il2p_header>& fetch_headers();       // waits for the most recent push
+    std::vector<unsigned long long> fetch_stats();            // 2 per stream
+    std::vector<unsigned long long> fetch_consumed();         // 1 per stream
+    std::vector<unsigned long long> positions(const unsigned long long* d_st) const;     // IL2P_ST_POS of every stream, one download
 };
 
 // Hilbert -> QuadratureDemod -> FftFilterFloat -> AddConst x nstreams over windows of nstreams f32 streams (kernels_afsk.hip,

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "hdlc_dims.hpp"
+#include "il2p_core.hpp"
 #include "nan_fix.hpp"
 #include "pwm_core.hpp"
 #include "symsync_core.hpp"
@@ -641,6 +642,32 @@ struct HdlcRxArgs {
     HdlcRxRec* recs;
 };
 void launch_hdlcrx(const HdlcRxArgs& a, hipStream_t s);
+
+// ---- kernels_il2p.hip: BinarySlicer -> [XorConst(1)] -> CorrelateAccessCodeTag(il2p SYNC_WORD) -> Il2pDeframer over the next
+//      symbols of nstreams independent streams (il2p_core.hpp holds the arithmetic) --------------------------------------
+// Stream c: min(counts ? counts[c] : n_cap, n_cap) f32 symbols at syms + c stride, read on the device; nothing at or beyond that
+// count is read.  Its state goes from st_in to st_out (IL2P_ST_N words each, distinct).  Scratch, all sized by the HOST's bound
+// ntiles = ceil(n_cap / IL2P_T): bits holds p_words = IL2P_CARRY_WORDS + 64 ntiles + 1 words of its virtual stream, mw 64 ntiles
+// match words, maps IL2P_MAP_PITCH bytes per tile, entry one byte per tile.  recs is ONE list of rec_cap records and *count ONE
+// counter for all streams (zeroed by the caller); stats: headers, syncs per stream, added to.  Three launches whatever nstreams,
+// the counts and the symbols are; n_cap == 0 launches nothing.
+struct Il2pArgs {
+    const float* syms;
+    long stride, n_cap, nstreams;
+    const unsigned long long* counts;         // may be null: every stream has n_cap
+    int invert;
+    unsigned allowed;                         // allowed_diffs, clamped to 24
+    const unsigned long long* st_in;
+    unsigned long long* st_out;
+    unsigned long long *bits, *mw;
+    long p_words, ntiles;
+    unsigned char *maps, *entry;
+    Il2pRec* recs;
+    long rec_cap;
+    unsigned long long* count;
+    unsigned long long* stats;
+};
+void launch_il2p(const Il2pArgs& a, hipStream_t s);
 
 // ---- kernels_sync.hip: SymbolSync (symbol_sync.rs:115-217) over the next n samples of nstreams independent streams
 //      (symsync_core.hpp holds the arithmetic) -------------------------------------------------------------------------------------------

@@ -1234,6 +1234,71 @@ public:
     }
 };
 
+// ---- BinarySlicer -> [XorConst(1)] -> CorrelateAccessCodeTag(il2p SYNC_WORD) -> Il2pDeframer x nstreams (examples/il2p-1200-rx.rs:118-137)
+// (rr_il2p_receiver_create / _push / _push_dev / _headers / _stats / _consumed / _dims).  push() takes the next symbols of every
+// stream (rows of any lengths) and returns the headers whose 120th bit lay in them, ascending by (stream, pos); push_dev() takes
+// SymbolSync's device windows and counts_dev() as they are.  Every stream's state stays in the block from push to push.
+class Il2pReceiver {
+    detail::Handle h_;
+    size_t nstreams_;
+public:
+    struct Stats { unsigned long long headers, syncs; };
+    Il2pReceiver(size_t nstreams, bool invert = false, size_t allowed_diffs = 0)
+        : h_(rr_il2p_receiver_create(nstreams, invert ? RR_BITS_INVERT : 0, allowed_diffs)), nstreams_(nstreams) {}
+    rr_block* handle() const { return h_.h; }
+    size_t nstreams() const { return nstreams_; }
+    // the headers of the most recent push (waits for it)
+    std::vector<rr_il2p_header> headers() {
+        size_t n = 0;
+        if (rr_il2p_receiver_headers(h_.h, nullptr, 0, &n) != 0) throw Error(rr_last_error());
+        std::vector<rr_il2p_header> rec(n);
+        if (n && rr_il2p_receiver_headers(h_.h, rec.data(), n, &n) != 0) throw Error(rr_last_error());
+        rec.resize(std::min(n, rec.size()));
+        for (auto& r : rec)
+            if (r.stream >= nstreams_) throw Error("Il2pReceiver: no such stream");
+        return rec;
+    }
+    // rows[c] = the next symbols of stream c
+    std::vector<rr_il2p_header> push(const std::vector<std::vector<float>>& rows) {
+        if (rows.size() != nstreams_) throw Error("Il2pReceiver: one row per stream");
+        size_t n_cap = 0;
+        for (auto& r : rows) n_cap = std::max(n_cap, r.size());
+        std::vector<float> in(nstreams_ * n_cap + 1);
+        std::vector<size_t> counts(nstreams_);
+        for (size_t c = 0; c < nstreams_; c++) {
+            std::copy(rows[c].begin(), rows[c].end(), in.begin() + (long)(c * n_cap));
+            counts[c] = rows[c].size();
+        }
+        if (rr_il2p_receiver_push(h_.h, in.data(), n_cap, n_cap, counts.data()) != 0) throw Error(rr_last_error());
+        return headers();
+    }
+    // device windows in the layout SymbolSync::push_dev writes, d_counts = SymbolSync::counts_dev() (or null: n_cap each);
+    // asynchronous on hip_stream, headers() waits
+    void push_dev(const void* d_syms, size_t stride, size_t n_cap, const void* d_counts, void* hip_stream = nullptr) {
+        if (rr_il2p_receiver_push_dev(h_.h, d_syms, stride, n_cap, d_counts, hip_stream) != 0) throw Error(rr_last_error());
+    }
+    std::vector<Stats> stats() {
+        std::vector<unsigned long long> h(nstreams_), s(nstreams_);
+        size_t total = 0;
+        if (rr_il2p_receiver_stats(h_.h, h.data(), s.data(), nstreams_, &total) != 0) throw Error(rr_last_error());
+        std::vector<Stats> out(nstreams_);
+        for (size_t c = 0; c < nstreams_; c++) out[c] = Stats{h[c], s[c]};
+        return out;
+    }
+    std::vector<unsigned long long> consumed() {
+        std::vector<unsigned long long> k(nstreams_);
+        size_t total = 0;
+        if (rr_il2p_receiver_consumed(h_.h, k.data(), k.size(), &total) != 0) throw Error(rr_last_error());
+        return k;
+    }
+    // -> (tile_bits, carry_bits)
+    std::pair<size_t, size_t> dims() const {
+        size_t t = 0, c = 0;
+        if (rr_il2p_receiver_dims(h_.h, &t, &c) != 0) throw Error(rr_last_error());
+        return {t, c};
+    }
+};
+
 // ---- AfskDemod: Hilbert -> QuadratureDemod -> FftFilterFloat -> AddConst (examples/ax25-1200-rx.rs:238-247) x nstreams ------------
 // (rr_afsk_demod_create / rr_afsk_demod_push / rr_afsk_demod_push_dev / rr_afsk_demod_dims).  push() takes the next samples of
 // every stream and returns the soft samples they complete: one fewer than pushed for the push that starts the streams, as many
