@@ -439,7 +439,7 @@ int rr_pdu_records(rr_block *b, rr_pdu_record *rec, size_t cap, size_t *total);
 /* The edges of the most recent push, ascending: pos[j] window-relative, val[j] = cur (1: rising) — the contract of
  * rr_burst_edges, and the same list when fed rr_burst_detector's output and threshold. */
 int rr_pdu_edges(rr_block *b, size_t *pos, unsigned char *val, size_t cap, size_t *total);
-/* The arena of the most recent push (device memory, *n_total f32: max_size + n); valid until the next push.  NULL, *n_total = 0
+/* The arena of the most recent push (device memory, *n_total elements of the handle's type: max_size + n); valid until the next push.  NULL, *n_total = 0
  * before the first push and after a push of no samples. */
 const void *rr_pdu_arena_dev(rr_block *b, size_t *n_total);
 /* The samples of PDU idx of the most recent push, the first min(len, cap) of them, to the host. */
@@ -448,6 +448,53 @@ int rr_pdu_fetch(rr_block *b, size_t idx, float *out, size_t cap);
  * them without RR_PDU_MIDPOINT) and calls rr_wpcr_process_dev on the arena with their `mid` (NULL without RR_PDU_MIDPOINT).
  * d_syms holds the arena's n_total floats.  rr_wpcr_results then has one record per such PDU, in order. */
 int rr_wpcr_process_pdus(rr_block *wpcr, rr_block *pdus, void *d_syms, void *hip_stream);
+/* StreamToPdu<Complex> (the reference block is generic over T: Sample): the same f32 trigger, edges, closed form, records and
+ * carried state as rr_stream_to_pdu_create; the data, the arena and the carried open burst are rr_c32.  No flags: Midpointer is a
+ * block over Vec<Float>.  rr_stream_to_pdu_push_dev, rr_pdu_records, rr_pdu_edges and rr_pdu_arena_dev (*n_total in rr_c32) serve
+ * both kinds of handle; rr_pdu_fetch on a Complex handle, rr_pdu_fetch_c32 and rr_stream_to_pdu_push_c32 on an f32 handle and
+ * rr_wpcr_process_pdus on a Complex handle ("wpcr: the PDUs are not f32") are RR_ERR.  The payload is copied bit for bit.
+ * NULL + rr_last_error: "max_size beyond 512000 samples", before any device is touched. */
+rr_block *rr_stream_to_pdu_c32_create(float threshold, size_t max_size, size_t tail);
+int rr_stream_to_pdu_push_c32(rr_block *b, const rr_c32 *data, const float *trigger, size_t n);
+int rr_pdu_fetch_c32(rr_block *b, size_t idx, rr_c32 *out, size_t cap);
+
+/* Delay::new(src, delay) (src/delay.rs:25-111) for elements of 1, 4 or 8 bytes, a stream block (rr_block_work /
+ * rr_block_work_dev): output position p of the whole stream is T::default() (all zero bytes) for p < delay and input sample
+ * p - delay behind that, bit for bit.  One call emits min(remaining delay, out_cap) zeros, then copies min(in_len, the space left)
+ * samples — the loop of one work() of the reference — in one launch; consumed and produced depend on lengths only and are final
+ * on return.  RR_WAIT_DST when no output space is left (out_cap == 0 included), else RR_WAIT_SRC (nothing left to delay and no
+ * input left); need = 1.  rr_block_eof: src_eof and the delay spent (delay.rs:56-60).  Tags: RR_TAGS_SHIFT, delay.
+ * Deviations: set_delay is not offered (the reference's own test of a mid-stream change is disabled as "TODO: fix"), and the
+ * delay is capped.  NULL + rr_last_error, before any device is touched: "unsupported element size",
+ * "delay: more than 1,024,000 samples". */
+rr_block *rr_delay_create(size_t delay, size_t elem_size);
+
+/* The sample-rate path of examples/burst_saver.rs:111-131 behind one handle: Tee -> [ComplexToMag2 -> SinglePoleIirFilter(alpha)]
+ * and [Delay(delay)] -> BurstTagger(threshold) -> StreamToPdu<Complex>(max_size, tail).  Complex in; PDU records and a Complex
+ * arena out.  A batch block: rr_block_work on the handle is an error.  For pushed windows x_0, x_1, ..:
+ *   the envelope e and cur(i) = e[i] > threshold are those of rr_burst_detector_create(alpha, threshold) fed the same windows
+ *     (the same f64 scan, the same stored f32), so rr_pdu_edges is that handle's rr_burst_edges;
+ *   the data stream is d[p] = x[p - delay] for p >= delay and 0 + 0i in front (Delay<Complex>), bit for bit;
+ *   the PDUs are those of rr_stream_to_pdu_c32_create(threshold, max_size, tail) pushed (d, e) over the same windows: the same
+ *     records (ok = 1, mean = mid = 0), arena geometry (max_size + n elements) and lifetime (until the next push).
+ * stream_pos counts positions of the DELAYED stream (the tags sit on Delay's output): stream_pos - delay is the input position of
+ * the PDU's first sample, and a PDU that begins before position `delay` starts with Delay's zeros.  A NaN input sample makes the
+ * envelope NaN for good (rr_single_pole_iir_create's rule) and a NaN envelope is never above the threshold: no further edges.
+ * rr_pdu_records, rr_pdu_edges, rr_pdu_arena_dev and rr_pdu_fetch_c32 take the handle under their own contracts.
+ * One stream per handle (N channels of a channelizer: N handles fed its rows); no back-pressure: a push takes the whole window.
+ * NULL + rr_last_error, before any device is touched: "alpha out of range", "max_size beyond 512000 samples",
+ * "delay: more than 1,024,000 samples". */
+rr_block *rr_burst_saver_create(float alpha, float threshold, size_t delay, size_t max_size, size_t tail);
+/* One window of n <= 1,024,000 Complex samples (device pointer; longer, or NULL with n > 0: RR_ERR before anything is enqueued).
+ * d_env: NULL, or n f32 that receive the envelope (rr_burst_detector's output).  Enqueued on hip_stream (used as given), returns
+ * without waiting and decides nothing on the host from device data; the launch count depends on n alone
+ * (rr_burst_saver_dims).  n == 0 launches nothing, reports no PDUs and leaves every state alone. */
+int rr_burst_saver_push_dev(rr_block *b, const void *d_in, size_t n, void *d_env, void *hip_stream);
+/* The same with host pointers: copies the window down, runs, waits, and copies the envelope back when env is given. */
+int rr_burst_saver_push(rr_block *b, const rr_c32 *in, size_t n, float *env);
+/* *tile = the samples of one tile of the scan and of the edge kernels (2048); *launches = the kernel launches of a push of n
+ * samples. */
+int rr_burst_saver_dims(const rr_block *b, size_t n, size_t *tile, size_t *launches);
 /* PduToStream (src/pdu_to_stream.rs:57-101) over the most recent process call of `wpcr`: the symbols of every burst with ok
  * and nsyms > 0, in burst order, back to back in d_out (device, out_cap f32), by ONE gather launch on hip_stream (the offsets
  * come from the host's copy of the results; the call waits for them).  *produced = symbols written; pdu_start[j] / pdu_len[j]
@@ -1056,8 +1103,10 @@ const char *rr_block_name(const rr_block *b);
  *                    FirFilter -> FftFilter: 1; Hilbert -> FirFilter(deci): deci.
  *   RR_TAGS_FRAMES   input tags dropped, frame tags added per *param = frame size outputs: FftStream
  *                    (fft_stream.rs:98-111).
+ *   RR_TAGS_SHIFT    re-emitted on output sample a + *param once that output exists: Delay (delay.rs:104-108: the copy
+ *                    keeps a tag's position in the window, and *param = delay outputs precede the first copied one).
  * Returns the rule, or RR_ERR for a NULL handle. */
-enum rr_tag_rule { RR_TAGS_DROP = 0, RR_TAGS_FORWARD = 1, RR_TAGS_FRAMES = 2 };
+enum rr_tag_rule { RR_TAGS_DROP = 0, RR_TAGS_FORWARD = 1, RR_TAGS_FRAMES = 2, RR_TAGS_SHIFT = 3 };
 int rr_block_tag_rule(const rr_block *b, size_t *param);
 size_t      rr_block_in_elem_size(const rr_block *b);
 size_t      rr_block_out_elem_size(const rr_block *b);

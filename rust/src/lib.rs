@@ -80,6 +80,25 @@ unsafe extern "C" {
     //  map) and rr_pdu_fetch too; not written yet)
     #[allow(dead_code)]
     fn rr_stream_to_pdu_create(threshold: f32, max_size: usize, tail: usize, flags: c_int) -> *mut RrBlock;
+    // (declared for completeness: StreamToPdu<Complex>, Delay and the burst saver of examples/burst_saver.rs.  Delay is a stream
+    //  block a GpuFused could carry once TagForwarder knows RR_TAGS_SHIFT (the C++ twin does); the two PDU handles need
+    //  rr_pdu_records like rr_stream_to_pdu_create above; not written yet)
+    #[allow(dead_code)]
+    fn rr_stream_to_pdu_c32_create(threshold: f32, max_size: usize, tail: usize) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_stream_to_pdu_push_c32(b: *mut RrBlock, data: *const Complex, trigger: *const f32, n: usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_pdu_fetch_c32(b: *mut RrBlock, idx: usize, out: *mut Complex, cap: usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_delay_create(delay: usize, elem_size: usize) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_burst_saver_create(alpha: f32, threshold: f32, delay: usize, max_size: usize, tail: usize) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_burst_saver_push_dev(b: *mut RrBlock, d_in: *const c_void, n: usize, d_env: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_burst_saver_push(b: *mut RrBlock, input: *const Complex, n: usize, env: *mut f32) -> c_int;
+    #[allow(dead_code)]
+    fn rr_burst_saver_dims(b: *const RrBlock, n: usize, tile: *mut usize, launches: *mut usize) -> c_int;
     fn rr_nrzi_encode_create() -> *mut RrBlock;
     fn rr_scrambler_g3ruh_create() -> *mut RrBlock;
     // (declared for completeness: FcsAdder -> HdlcFramer -> PduToStream behind one handle takes an NCReadStream<Vec<u8>> and feeds a

@@ -1609,6 +1609,103 @@ class StreamToPdu(Block):
         return lh[0], lh[1]
 
 
+class StreamToPduC32(StreamToPdu):
+    """StreamToPdu<Complex> (rr_stream_to_pdu_c32_create): the f32 trigger, the edges, the records and the carried state of
+    StreamToPdu; the data, the arena and the payloads are complex64.  No Midpointer (a block over Vec<Float>)."""
+
+    def __init__(self, threshold: float, max_size: int, tail: int):
+        Block.__init__(self, lib().rr_stream_to_pdu_c32_create(float(threshold), int(max_size), int(tail)), np.complex64, np.complex64)
+        self.flags = 0
+
+    def push(self, data: np.ndarray, trigger: np.ndarray) -> np.ndarray:
+        """rr_stream_to_pdu_push_c32 on host arrays of one length -> records()"""
+        x = np.ascontiguousarray(data, np.complex64).ravel()
+        t = np.ascontiguousarray(trigger, np.float32).ravel()
+        if x.shape != t.shape:
+            raise ValueError("data and trigger must have one length")
+        if lib().rr_stream_to_pdu_push_c32(self._h, _ptr(x) if len(x) else None, _ptr(t) if len(t) else None, len(x)) != 0:
+            raise RuntimeError(last_error())
+        return self.records()
+
+    def pdu(self, i: int, rec=None) -> np.ndarray:
+        """the samples of PDU i of the most recent push (rr_pdu_fetch_c32)"""
+        r = self.records() if rec is None else rec
+        if not 0 <= i < len(r):
+            raise IndexError("no such PDU in the most recent push")
+        out = np.zeros(max(int(r[i]["len"]), 1), np.complex64)
+        if lib().rr_pdu_fetch_c32(self._h, i, _ptr(out), int(r[i]["len"])) != 0:
+            raise RuntimeError(last_error())
+        return out[:int(r[i]["len"])]
+
+
+TAGS_DROP, TAGS_FORWARD, TAGS_FRAMES, TAGS_SHIFT = 0, 1, 2, 3      # rr_tag_rule
+
+
+class Delay(Block):
+    """Delay::new(src, delay) (rr_delay_create; src/delay.rs): `delay` zero elements, then the input, for a dtype of 1, 4 or 8
+    bytes.  ValueError ("unsupported element size", "delay: more than 1,024,000 samples")."""
+
+    def __init__(self, delay: int, dtype=np.complex64):
+        dt = np.dtype(dtype)
+        super().__init__(lib().rr_delay_create(int(delay), dt.itemsize), dt, dt)
+        self.delay = int(delay)
+
+    def tag_rule(self):
+        """-> (rule, param) of rr_block_tag_rule: (TAGS_SHIFT, delay)"""
+        p = C.c_size_t(0)
+        return lib().rr_block_tag_rule(self._h, C.byref(p)), p.value
+
+
+class BurstSaver(StreamToPduC32):
+    """The sample-rate path of examples/burst_saver.rs behind one handle (rr_burst_saver_create): Tee -> [ComplexToMag2 ->
+    SinglePoleIirFilter(alpha)] and [Delay(delay)] -> BurstTagger(threshold) -> StreamToPdu<Complex>(max_size, tail).  complex64
+    windows in; records(), edges(), arena_dev() and pdu() as StreamToPduC32; save() is PduWriter."""
+
+    def __init__(self, alpha: float, threshold: float, delay: int, max_size: int, tail: int):
+        Block.__init__(self, lib().rr_burst_saver_create(float(alpha), float(threshold), int(delay), int(max_size), int(tail)),
+                       np.complex64, np.complex64)
+        self.flags = 0
+        self.delay = int(delay)
+        self._written = 0
+
+    def push_dev(self, d_in: int, n: int, d_env: int = 0, stream: int = 0) -> None:
+        """rr_burst_saver_push_dev: a raw device pointer to n complex64, and 0 or one to n f32 that receive the envelope;
+        asynchronous on `stream`; records() waits"""
+        if lib().rr_burst_saver_push_dev(self._h, C.c_void_p(d_in), n, C.c_void_p(d_env), C.c_void_p(stream)) != 0:
+            raise RuntimeError(last_error())
+
+    def push(self, x: np.ndarray, env: bool = False):
+        """rr_burst_saver_push on a host window -> records(), or (records(), envelope) with env=True"""
+        x = np.ascontiguousarray(x, np.complex64).ravel()
+        e = np.zeros(max(len(x), 1), np.float32) if env else None
+        if lib().rr_burst_saver_push(self._h, _ptr(x) if len(x) else None, len(x), _ptr(e) if env else None) != 0:
+            raise RuntimeError(last_error())
+        return (self.records(), e[:len(x)]) if env else self.records()
+
+    def dims(self, n: int):
+        """-> (tile, kernel launches of a push of n samples) (rr_burst_saver_dims)"""
+        t, k = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_burst_saver_dims(self._h, int(n), C.byref(t), C.byref(k)) != 0:
+            raise RuntimeError(last_error())
+        return t.value, k.value
+
+    def save(self, directory) -> list:
+        """PduWriter (src/pdu_writer.rs:41-69) over the PDUs of the most recent push: one file each, named
+        <microseconds since the epoch>-<files written so far>, opened create-new, holding the samples as Sample::serialize
+        writes them (interleaved little-endian f32 re, im) -> the paths written"""
+        import os
+        import time
+        paths = []
+        rec = self.records()
+        for i in range(len(rec)):
+            name = os.path.join(os.fspath(directory), f"{time.time_ns() // 1000}-{self._written}")
+            with open(name, "xb") as f:
+                f.write(self.pdu(i, rec).astype("<c8").tobytes())
+            self._written += 1
+            paths.append(name)
+        return paths
+
+
 def FmChainU8(taps, interp: int, deci: int, gain: float = 1.0, mode: int = ATAN2_EXACT) -> Block:
     """RtlSdrDecode -> FmChain fused (examples/rtl_fm.rs:328-419): RTL-SDR bytes in, f32 out; windows,
     consumed and the WAIT_SRC need count bytes."""

@@ -18,6 +18,7 @@
 #include "kiss_core.hpp"
 #include "kiss_host.hpp"
 #include "pdu_host.hpp"
+#include "saver_host.hpp"
 #include "symsync_host.hpp"
 #include "taps.hpp"
 
@@ -334,12 +335,20 @@ int rr_stream_to_pdu_push_dev(rr_block* b, const void* d_data, const void* d_tri
     if (!p) return RR_ERR;
     if (n && (!d_data || !d_trigger)) { rr::set_last_error("rr_stream_to_pdu_push_dev: null argument"); return RR_ERR; }
     return on_device(p, hip_stream, [&](hipStream_t s) {
-        p->push_dev(static_cast<const float*>(d_data), static_cast<const float*>(d_trigger), n, s);
+        if (dynamic_cast<rr::BurstSaver*>(p)) throw rr::Error("rr_stream_to_pdu_push_dev: a burst saver takes rr_burst_saver_push_dev");
+        p->push_dev(d_data, static_cast<const float*>(d_trigger), n, s);
     });
 }
+// what a call on host data of element size `es` says to a handle of the other kind (a burst saver is fed by its own calls)
+static bool pdu_kind_ok(rr::StreamToPdu* p, size_t es, const char* what, const char* msg, bool saver_ok) {
+    if (p->es == es && (saver_ok || !dynamic_cast<rr::BurstSaver*>(p))) return true;
+    rr::set_last_error(std::string(what) + ": " + msg);
+    return false;
+}
+static const char PDU_NOT_F32[] = "the PDUs are not f32", PDU_NOT_C32[] = "the PDUs are not Complex";
 int rr_stream_to_pdu_push(rr_block* b, const float* data, const float* trigger, size_t n) {
     auto* p = as<rr::StreamToPdu>(b, "rr_stream_to_pdu_push", NOT_PDU);
-    if (!p) return RR_ERR;
+    if (!p || !pdu_kind_ok(p, 4, "rr_stream_to_pdu_push", PDU_NOT_F32, false)) return RR_ERR;
     if (n && (!data || !trigger)) { rr::set_last_error("rr_stream_to_pdu_push: null argument"); return RR_ERR; }
     return guarded([&] { p->push_host(data, trigger, n); });
 }
@@ -362,7 +371,7 @@ const void* rr_pdu_arena_dev(rr_block* b, size_t* n_total) {
 }
 int rr_pdu_fetch(rr_block* b, size_t idx, float* out, size_t cap) {
     auto* p = as<rr::StreamToPdu>(b, "rr_pdu_fetch", NOT_PDU);
-    if (!p) return RR_ERR;
+    if (!p || !pdu_kind_ok(p, 4, "rr_pdu_fetch", PDU_NOT_F32, true)) return RR_ERR;
     if (cap && !out) { rr::set_last_error("rr_pdu_fetch: null argument"); return RR_ERR; }
     return on_device(p, [&] { p->fetch_pdu(idx, out, cap); });
 }
@@ -376,6 +385,7 @@ int rr_wpcr_process_pdus(rr_block* wpcr, rr_block* pdus, void* d_syms, void* hip
     auto* w = as<rr::Wpcr>(wpcr, "rr_wpcr_process_pdus", NOT_WPCR);
     auto* p = as<rr::StreamToPdu>(pdus, "rr_wpcr_process_pdus", NOT_PDU);
     if (!w || !p) return RR_ERR;
+    if (p->es != 4) { rr::set_last_error("wpcr: the PDUs are not f32"); return RR_ERR; }
     return on_device(p, [&] {
         if (w->device != p->device) throw rr::Error("rr_wpcr_process_pdus: the two handles live on different devices");
         std::vector<size_t> starts, lens;
@@ -385,9 +395,53 @@ int rr_wpcr_process_pdus(rr_block* wpcr, rr_block* pdus, void* d_syms, void* hip
         if (!starts.empty() && !d_syms) throw rr::Error("rr_wpcr_process_pdus: null argument");
         hipStream_t s = static_cast<hipStream_t>(hip_stream);
         w->last_stream = s;
-        w->process_dev(p->arena_dev(), p->n_total, starts.data(), lens.data(), p->midpoint ? mids.data() : nullptr, starts.size(),
+        w->process_dev(static_cast<const float*>(p->arena_dev()), p->n_total, starts.data(), lens.data(), p->midpoint ? mids.data() : nullptr, starts.size(),
                        static_cast<float*>(d_syms), s);
     });
+}
+rr_block* rr_stream_to_pdu_c32_create(float threshold, size_t max_size, size_t tail) {
+    if (const char* e = rr::pdu_check(max_size, 0)) return refuse_create(e);
+    return make_block([&] { return new rr::StreamToPdu(threshold, max_size, tail, 0, 8); });
+}
+int rr_stream_to_pdu_push_c32(rr_block* b, const rr_c32* data, const float* trigger, size_t n) {
+    auto* p = as<rr::StreamToPdu>(b, "rr_stream_to_pdu_push_c32", NOT_PDU);
+    if (!p || !pdu_kind_ok(p, 8, "rr_stream_to_pdu_push_c32", PDU_NOT_C32, false)) return RR_ERR;
+    if (n && (!data || !trigger)) { rr::set_last_error("rr_stream_to_pdu_push_c32: null argument"); return RR_ERR; }
+    return guarded([&] { p->push_host(data, trigger, n); });
+}
+int rr_pdu_fetch_c32(rr_block* b, size_t idx, rr_c32* out, size_t cap) {
+    auto* p = as<rr::StreamToPdu>(b, "rr_pdu_fetch_c32", NOT_PDU);
+    if (!p || !pdu_kind_ok(p, 8, "rr_pdu_fetch_c32", PDU_NOT_C32, true)) return RR_ERR;
+    if (cap && !out) { rr::set_last_error("rr_pdu_fetch_c32: null argument"); return RR_ERR; }
+    return on_device(p, [&] { p->fetch_pdu(idx, out, cap); });
+}
+rr_block* rr_delay_create(size_t delay, size_t elem_size) {
+    if (const char* e = rr::delay_check(delay, elem_size)) return refuse_create(e);
+    return make_block([&] { return new rr::Delay(delay, elem_size); }, RR_TAGS_SHIFT, delay);
+}
+static const char NOT_SAVER[] = "not a burst saver handle";
+rr_block* rr_burst_saver_create(float alpha, float threshold, size_t delay, size_t max_size, size_t tail) {
+    if (const char* e = rr::saver_check(alpha, delay, max_size)) return refuse_create(e);
+    return make_block([&] { return new rr::BurstSaver(alpha, threshold, delay, max_size, tail); });
+}
+int rr_burst_saver_push_dev(rr_block* b, const void* d_in, size_t n, void* d_env, void* hip_stream) {
+    auto* p = as<rr::BurstSaver>(b, "rr_burst_saver_push_dev", NOT_SAVER);
+    if (!p) return RR_ERR;
+    if (const char* e = rr::saver_push_check(d_in, n)) { rr::set_last_error(std::string("rr_burst_saver_push_dev: ") + e); return RR_ERR; }
+    return on_device(p, hip_stream, [&](hipStream_t s) { p->push_dev(static_cast<const rr::cf*>(d_in), n, static_cast<float*>(d_env), s); });
+}
+int rr_burst_saver_push(rr_block* b, const rr_c32* in, size_t n, float* env) {
+    auto* p = as<rr::BurstSaver>(b, "rr_burst_saver_push", NOT_SAVER);
+    if (!p) return RR_ERR;
+    if (const char* e = rr::saver_push_check(in, n)) { rr::set_last_error(std::string("rr_burst_saver_push: ") + e); return RR_ERR; }
+    return guarded([&] { p->push_host(reinterpret_cast<const rr::cf*>(in), n, env); });
+}
+int rr_burst_saver_dims(const rr_block* b, size_t n, size_t* tile, size_t* launches) {
+    auto* p = as<rr::BurstSaver>(b, "rr_burst_saver_dims", NOT_SAVER);
+    if (!p) return RR_ERR;
+    if (tile) *tile = rr::IIR_T;
+    if (launches) *launches = rr::saver_launches(n, rr::IIR_T);
+    return 0;
 }
 int rr_wpcr_pack_dev(rr_block* wpcr, const void* d_syms, void* d_out, size_t out_cap, size_t* produced, size_t* pdu_start,
                      size_t* pdu_len, size_t cap, size_t* npdus, void* hip_stream) {

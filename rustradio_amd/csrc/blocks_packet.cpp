@@ -1,5 +1,5 @@
 // blocks_packet.cpp — host side of the packet-side blocks (blocks_packet.hpp): the sync blocks, the burst and bit blocks, and the
-// batch handles (Wpcr, StreamToPdu, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver, AfskDemod, FskTx, FskTxMulti, KissDecode, KissEncode).  Citations are to the reference's src, as in blocks.cpp.
+// batch handles (Wpcr, StreamToPdu, Delay, BurstSaver, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver, AfskDemod, FskTx, FskTxMulti, KissDecode, KissEncode).  Citations are to the reference's src, as in blocks.cpp.
 #include "blocks_packet.hpp"
 
 #include <algorithm>
@@ -12,6 +12,7 @@
 #include "hdlcrx_core.hpp"
 #include "kiss_core.hpp"
 #include "pdu_host.hpp"
+#include "saver_host.hpp"
 #include "symsync_host.hpp"
 #include "taps.hpp"
 
@@ -328,12 +329,16 @@ void Wpcr::pack_dev(const float* d_syms, float* d_out, size_t out_cap, size_t* p
 static_assert(sizeof(PduRec) == sizeof(rr_pdu_record) && offsetof(PduRec, nlow) == offsetof(rr_pdu_record, nlow) &&
               offsetof(PduRec, mid) == offsetof(rr_pdu_record, mid) && offsetof(PduRec, stream_pos) == offsetof(rr_pdu_record, stream_pos),
               "PduRec is rr_pdu_record");
-StreamToPdu::StreamToPdu(float threshold, size_t max_sz, size_t tl, int flags)
-    : BatchBlock("BurstTagger>StreamToPdu>Midpointer", 4, 4, "StreamToPdu forms PDUs: rr_stream_to_pdu_push / rr_stream_to_pdu_push_dev"),
+StreamToPdu::StreamToPdu(float threshold, size_t max_sz, size_t tl, int flags, size_t elem)
+    : StreamToPdu("BurstTagger>StreamToPdu>Midpointer", "StreamToPdu forms PDUs: rr_stream_to_pdu_push / rr_stream_to_pdu_push_dev",
+                  threshold, max_sz, tl, flags, elem) {}
+StreamToPdu::StreamToPdu(const char* nm, const char* sentence, float threshold, size_t max_sz, size_t tl, int flags, size_t elem)
+    : BatchBlock(nm, elem, elem, sentence),
       thr(threshold), max_size(max_sz),
       tail(std::min(tl, max_sz + 1)),          // (a tail beyond max_size files nothing, like max_size + 1: no sum below overflows)
-      midpoint((flags & RR_PDU_MIDPOINT) != 0) {
+      midpoint((flags & RR_PDU_MIDPOINT) != 0), es(elem) {
     if (const char* e = pdu_check(max_sz, flags)) throw Error(e);
+    if (es != 4 && (es != 8 || midpoint)) throw Error("StreamToPdu: Float, or Complex without Midpointer");
     PduState init{};
     init.free = 0;                             // Unsync, last_state false (stream_to_pdu.rs:102, burst_tagger.rs:62)
     init.open_r = init.open_f = PDU_NONE;
@@ -343,16 +348,15 @@ StreamToPdu::StreamToPdu(float threshold, size_t max_sz, size_t tl, int flags)
     root.reserve(1);
     RR_HIP(hipStreamSynchronize(stream));
 }
-void StreamToPdu::push_dev(const float* d_data, const float* d_trig, size_t n, hipStream_t s) {
-    if (n > MAX_WINDOW) throw Error("window longer than 1024000 samples");
+bool StreamToPdu::begin_push(size_t n) {
     records.clear();
     edgelist.clear();
     fetched = efetched = true;                 // a push that moves nothing has no PDUs and no edges and leaves every state alone
     last_n = n;
     n_total = 0;
-    if (!n) return;
+    if (!n) return false;
     const size_t ntiles = (n + PDU_T - 1) / PDU_T, nr = n / 2 + 2;
-    arena.reserve_out(max_size + n);
+    arena.reserve_out((max_size + n) * (es / 4));
     tilecnt.reserve(ntiles);
     offs.reserve(ntiles);
     edges.reserve(n);
@@ -361,6 +365,9 @@ void StreamToPdu::push_dev(const float* d_data, const float* d_trig, size_t n, h
     mark.reserve(nr);
     recs.reserve(nr);
     if (midpoint) ranks.reserve(2 * nr);
+    return true;
+}
+PduArgs StreamToPdu::push_args(const void* d_data, const float* d_trig, size_t n) {
     PduArgs g{};
     g.data = d_data; g.trig = d_trig; g.n = (long)n; g.thr = thr;
     g.max_size = max_size; g.tail = tail; g.w0 = w0; g.C = (long)max_size;
@@ -370,10 +377,10 @@ void StreamToPdu::push_dev(const float* d_data, const float* d_trig, size_t n, h
     g.st_in = st.in(); g.st_out = st.out();
     g.tilecnt = tilecnt.p; g.offs = offs.p; g.etotal = etotal.p; g.edges = edges.p;
     g.jmp0 = jmp[0].p; g.jmp1 = jmp[1].p; g.mark = mark.p; g.root = root.p;
-    g.recs = recs.p; g.rec_cap = (long)nr; g.count = count.p; g.ranks = ranks.p; g.midpoint = midpoint;
-    prof_begin(s);
-    launch_pdu(g, s);
-    prof_end(s);
+    g.recs = recs.p; g.rec_cap = (long)(n / 2 + 2); g.count = count.p; g.ranks = ranks.p; g.midpoint = midpoint;
+    return g;
+}
+void StreamToPdu::end_push(size_t n) {
     arena.flip();
     st.flip();
     n_prev = n;
@@ -381,13 +388,22 @@ void StreamToPdu::push_dev(const float* d_data, const float* d_trig, size_t n, h
     w0 += n;
     fetched = efetched = false;
 }
-void StreamToPdu::push_host(const float* data, const float* trig, size_t n) {
+void StreamToPdu::push_dev(const void* d_data, const float* d_trig, size_t n, hipStream_t s) {
+    if (n > MAX_WINDOW) throw Error("window longer than 1024000 samples");
+    if (!begin_push(n)) return;
+    const PduArgs g = push_args(d_data, d_trig, n);
+    prof_begin(s);
+    launch_pdu(g, s, es == 8 ? PDU_C32 : PDU_F32);
+    prof_end(s);
+    end_push(n);
+}
+void StreamToPdu::push_host(const void* data, const float* trig, size_t n) {
     host_call([&] {
         if (n > MAX_WINDOW) throw Error("window longer than 1024000 samples");
         if (n) {
-            h_data.reserve(n);
+            h_data.reserve(n * (es / 4));
             h_trig.reserve(n);
-            hstage().h2d(h_data.p, data, n * sizeof(float), stream);
+            hstage().h2d(h_data.p, data, n * es, stream);
             hstage().h2d(h_trig.p, trig, n * sizeof(float), stream);
         }
         push_dev(h_data.p, h_trig.p, n, stream);
@@ -410,11 +426,11 @@ const std::vector<unsigned>& StreamToPdu::fetch_edges() {
     }
     return edgelist;
 }
-void StreamToPdu::fetch_pdu(size_t idx, float* out, size_t cap) {
+void StreamToPdu::fetch_pdu(size_t idx, void* out, size_t cap) {
     const std::vector<rr_pdu_record>& r = fetch_records();
     if (idx >= r.size()) throw Error("rr_pdu_fetch: no such PDU in the most recent push");
     if (r[idx].start > n_total || r[idx].len > n_total - r[idx].start) throw Error("stream_to_pdu: record outside the arena");
-    if (const size_t k = std::min(cap, r[idx].len)) stage_download_sync(out, arena.in() + r[idx].start, k * sizeof(float), stream);
+    if (const size_t k = std::min(cap, r[idx].len)) stage_download_sync(out, arena.in() + r[idx].start * (es / 4), k * es, stream);
 }
 void StreamToPdu::fetch_ranks(size_t idx, float* low, float* high) {
     const std::vector<rr_pdu_record>& r = fetch_records();
@@ -424,6 +440,66 @@ void StreamToPdu::fetch_ranks(size_t idx, float* low, float* high) {
     stage_download_sync(lh, ranks.p + 2 * slots[idx], sizeof lh, stream);
     *low = lh[0];
     *high = lh[1];
+}
+
+// ---- Delay (delay.rs:62-111) and the burst saver (examples/burst_saver.rs:111-131; kernels_saver.hip) --------------------------------
+Delay::Delay(size_t d, size_t es) : Block("Delay", es, es), delay(d), remaining(d) {
+    if (const char* e = delay_check(d, es)) throw Error(e);
+}
+int Delay::work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed, size_t* produced, size_t* need,
+                    hipStream_t s) {
+    const DelayStep d = delay_step(remaining, in_len, out_cap);
+    if (d.zeros + d.copied) {
+        prof_begin(s);
+        launch_delay(in, out, (long)d.zeros, (long)d.copied, in_es, s);
+        prof_end(s);
+    }
+    *consumed = d.copied;
+    *produced = d.zeros + d.copied;
+    *need = 1;
+    return d.status;
+}
+BurstSaver::BurstSaver(float alpha, float threshold, size_t dl, size_t max_sz, size_t tl)
+    : StreamToPdu("ComplexToMag2>SinglePoleIirFilter|Delay>BurstTagger>StreamToPdu",
+                  "BurstSaver forms PDUs: rr_burst_saver_push / rr_burst_saver_push_dev", threshold, max_sz, tl, 0, 8),
+      iir(alpha, 1, stream), delay(dl) {
+    if (const char* e = saver_check(alpha, dl, max_sz)) throw Error(e);
+    hist.zero(std::max<size_t>(delay, 1), stream);   // Delay fills with T::default() (delay.rs:87)
+    RR_HIP(hipStreamSynchronize(stream));
+}
+void BurstSaver::push_dev(const cf* d_in, size_t n, float* d_env, hipStream_t s) {
+    if (const char* e = saver_push_check(d_in, n)) throw Error(e);
+    if (!begin_push(n)) return;
+    if (!d_env) { env.reserve(n); d_env = env.p; }
+    const PduArgs g = push_args(nullptr, d_env, n);
+    const SaverPlan pl = saver_plan(n, delay);
+    SaverArgs c{};
+    c.x = reinterpret_cast<const unsigned long long*>(d_in);
+    c.n = (long)n; c.delay = (long)delay; c.from_hist = (long)pl.from_hist; c.shifted = (long)pl.shifted;
+    c.hist_in = hist.in(); c.hist_out = hist.out();
+    c.arena = static_cast<unsigned long long*>(g.arena); c.C = g.C;
+    c.prev_arena = static_cast<const unsigned long long*>(g.prev_arena); c.n_prev = g.n_prev;
+    c.st_in = g.st_in; c.w0 = g.w0;
+    prof_begin(s);
+    launch_mag2_iir(d_in, d_env, (long)n, iir.c, iir.y.in(), iir.y.out(), iir.scratch(n), s);
+    launch_saver_copy(c, s);
+    launch_pdu(g, s, PDU_NODATA);
+    prof_end(s);
+    iir.y.flip();
+    hist.flip();
+    end_push(n);
+}
+void BurstSaver::push_host(const cf* in, size_t n, float* out_env) {
+    host_call([&] {
+        if (const char* e = saver_push_check(in, n)) throw Error(e);
+        if (n) {
+            h_in.reserve(n);
+            hstage().h2d(h_in.p, in, n * sizeof(cf), stream);
+            if (out_env) h_env.reserve(n);
+        }
+        push_dev(h_in.p, n, n && out_env ? h_env.p : nullptr, stream);
+        if (n && out_env) stage_download_sync(out_env, h_env.p, n * sizeof(float), stream);
+    });
 }
 
 // ---- Scrambler::g3ruh, NrziEncode and the HDLC framer (descrambler.rs:41-47, nrzi.rs:52-69, hdlc_framer.rs; kernels_frame.hip) ----------

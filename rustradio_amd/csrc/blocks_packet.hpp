@@ -196,17 +196,19 @@ struct Wpcr : BatchBlock {
                   size_t* npdus, hipStream_t s);
 };
 
-// BurstTagger -> StreamToPdu -> [Midpointer] over windows of an f32 data / trigger stream pair (kernels_pdu.hip): no stream
-// protocol (work_dev is an error).  The state between pushes (PduState) stays on the device; the two arenas alternate, and the
-// one of the previous push holds the samples of a burst that is still open, so they are the carry as well.
+// BurstTagger -> StreamToPdu -> [Midpointer] over windows of a data / f32 trigger stream pair (kernels_pdu.hip): no stream
+// protocol (work_dev is an error).  The data is f32 (es 4) or Complex (es 8: no Midpointer, which is a block over Vec<Float>).
+// The state between pushes (PduState) stays on the device; the two arenas alternate, and the one of the previous push holds the
+// samples of a burst that is still open, so they are the carry as well.
 struct StreamToPdu : BatchBlock {
     static constexpr size_t MAX_WINDOW = 1024000;         // the f32 stream capacity in samples (stream.rs:105)
     float thr;
     size_t max_size, tail;
     bool midpoint;
+    size_t es;                                    // bytes of a data sample: 4 or 8
     Carried<PduState> st;
-    Carried<float> arena;                         // in(): the arena of the most recent push that moved samples
-    size_t n_prev = 0, n_total = 0;               // its window; its length (0: no such push yet, or the latest push was empty)
+    Carried<float> arena;                         // in(): the arena of the most recent push that moved samples (es / 4 floats a sample)
+    size_t n_prev = 0, n_total = 0;               // its window; its length in samples (0: no such push yet, or the latest push was empty)
     unsigned long long w0 = 0;                    // samples of the stream so far
     DevBuf<unsigned> tilecnt, edges, jmp[2], mark;
     DevBuf<unsigned long long> offs, etotal, count;
@@ -219,14 +221,46 @@ struct StreamToPdu : BatchBlock {
     std::vector<rr_pdu_record> records;           // ... ascending
     std::vector<size_t> slots;                    // record i's place in the device's (unordered) list
     std::vector<unsigned> edgelist;               // (pos << 1) | cur, ascending
-    StreamToPdu(float threshold, size_t max_size, size_t tail, int flags);
-    void push_dev(const float* d_data, const float* d_trig, size_t n, hipStream_t s);
-    void push_host(const float* data, const float* trig, size_t n);
+    StreamToPdu(float threshold, size_t max_size, size_t tail, int flags, size_t es = 4);
+    void push_dev(const void* d_data, const float* d_trig, size_t n, hipStream_t s);
+    void push_host(const void* data, const float* trig, size_t n);
     const std::vector<rr_pdu_record>& fetch_records();      // waits for the most recent push
     const std::vector<unsigned>& fetch_edges();
-    const float* arena_dev() const { return n_total ? arena.in() : nullptr; }
-    void fetch_pdu(size_t idx, float* out, size_t cap);
+    const void* arena_dev() const { return n_total ? arena.in() : nullptr; }
+    void fetch_pdu(size_t idx, void* out, size_t cap);      // cap in samples
     void fetch_ranks(size_t idx, float* low, float* high);  // the two elements Midpointer's offset of PDU idx was made of
+protected:
+    StreamToPdu(const char* nm, const char* sentence, float threshold, size_t max_size, size_t tail, int flags, size_t es);
+    // the three parts of a push of n <= MAX_WINDOW samples: drop the previous push's results and size the buffers (false: n == 0,
+    // nothing to do); what the kernels get; the flips once everything is enqueued
+    bool begin_push(size_t n);
+    PduArgs push_args(const void* d_data, const float* d_trig, size_t n);
+    void end_push(size_t n);
+};
+
+// Delay<T> (src/delay.rs:62-111) for elements of 1, 4 or 8 bytes: `delay` default elements, then the input.  What is left of the
+// delay is host state; a call moves min(remaining, out_cap) zeros and then min(in_len, the space left) samples in one launch.
+struct Delay : Block {
+    size_t delay, remaining;
+    Delay(size_t delay, size_t es);
+    int work_dev(const void* in, size_t in_len, void* out, size_t out_cap, size_t* consumed, size_t* produced, size_t* need,
+                 hipStream_t s) override;
+    bool eof(bool src_eof) override { return src_eof && remaining == 0; }        // delay.rs:56-60
+};
+
+// examples/burst_saver.rs:111-131 behind one handle: [ComplexToMag2 -> SinglePoleIirFilter] and [Delay] on the two branches of
+// the Tee, BurstTagger -> StreamToPdu<Complex> behind them.  A StreamToPdu whose trigger is made here (the detector's scan) and
+// whose arena is filled by k_saver_copy from the window and the history: the last `delay` input samples, a ping-pong pair.
+struct BurstSaver : StreamToPdu {
+    IirState iir;
+    size_t delay;
+    Carried<unsigned long long> hist;             // in(): the last `delay` input samples (zeros in front of the stream)
+    DevBuf<float> env;                            // the envelope, when the caller does not want it
+    DevBuf<cf> h_in;                              // push(): the host window's device copy
+    DevBuf<float> h_env;
+    BurstSaver(float alpha, float threshold, size_t delay, size_t max_size, size_t tail);
+    void push_dev(const cf* d_in, size_t n, float* d_env, hipStream_t s);
+    void push_host(const cf* in, size_t n, float* env);
 };
 
 // Scrambler::g3ruh (descrambler.rs:41-47, 95-123) and NrziEncode (nrzi.rs:52-69) as one affine system over GF(2)

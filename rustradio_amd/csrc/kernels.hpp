@@ -429,16 +429,17 @@ struct PduRec {                               // rr_pdu_record
     float mean, mid;
     unsigned long long nlow;
 };
+enum { PDU_F32 = 0, PDU_C32 = 1, PDU_NODATA = 2 };   // the element of data / arena / prev_arena; NODATA: the caller fills the arena
 struct PduArgs {
-    const float* data;
+    const void* data;
     const float* trig;
     long n;
     float thr;
     unsigned long long max_size, tail, w0;
     long C;
-    const float* prev_arena;
+    const void* prev_arena;
     long n_prev;
-    float* arena;
+    void* arena;
     const PduState* st_in;
     PduState* st_out;
     unsigned* tilecnt;
@@ -455,7 +456,29 @@ struct PduArgs {
     float* ranks;                             // with midpoint: low and high of record slot k at [2 k], [2 k + 1] (0 when ok == 0)
     bool midpoint;
 };
-void launch_pdu(const PduArgs& a, hipStream_t s);
+void launch_pdu(const PduArgs& a, hipStream_t s, int elem = PDU_F32);
+
+// ---- kernels_saver.hip: Delay, and Delay -> the arena of StreamToPdu<Complex> (examples/burst_saver.rs) ------------------------------
+// out[i] = 0 (all zero bytes) for i < zeros, in[i - zeros] for the `copied` elements behind them; es = 1, 4 or 8 bytes, pointers
+// aligned to es.  One launch; nothing to write launches nothing.
+void launch_delay(const void* in, void* out, long zeros, long copied, size_t es, hipStream_t s);
+// One window of the burst saver's data branch, Complex samples as 64-bit words: arena[C + i] = the delayed window (i < from_hist:
+// hist_in[i], else x[i - delay]), the open burst of the previous arena in front of arena[C) exactly as k_pdu_tiles places it, and
+// hist_out = the last `delay` input samples (j < shifted: hist_in[j + n], else x[j + n - delay]).  from_hist / shifted:
+// saver_host.hpp saver_plan.  hist_in and hist_out are distinct.  One launch; n == 0 launches nothing.
+struct SaverArgs {
+    const unsigned long long* x;
+    long n, delay, from_hist, shifted;
+    const unsigned long long* hist_in;
+    unsigned long long* hist_out;
+    unsigned long long* arena;
+    long C;
+    const unsigned long long* prev_arena;
+    long n_prev;
+    const PduState* st_in;
+    unsigned long long w0;
+};
+void launch_saver_copy(const SaverArgs& a, hipStream_t s);
 // PduToStream over a batch: out[dst[b] + i] = syms[src[b] + i], i < len[b]; desc holds nb (src, dst, len) triples ascending in
 // dst without gaps, total = their lengths' sum.  One launch; total == 0 launches nothing.
 void launch_pdu_pack(const float* syms, const long* desc, long nb, long total, float* out, hipStream_t s);

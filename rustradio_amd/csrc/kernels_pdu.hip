@@ -9,6 +9,7 @@
 // at or behind the `free` that accepting j leaves — and the accepted edges of a window are the chain j0, nxt(j0), nxt(nxt(j0)) ..
 // from the first edge j0 at or behind the carried `free`.  nxt is monotone (nxt(j) > j), so:
 //   k_pdu_tiles<false>  per tile the number of threshold crossings; the window is copied behind the open burst into the arena
+//   k_pdu_count         ... the same for Complex data (StreamToPdu<Complex>), or with no copy (the burst saver, kernels_saver.hip)
 //   (offsets)           the crossings in front of every tile: launch_bits_tag_offsets, one workgroup
 //   k_pdu_tiles<true>   every tile writes its crossings, ascending, at its offset: the edge list, (pos << 1) | cur
 //   k_pdu_next          nxt(j) by binary search in the edge list, one thread per rising edge; the carried burst meets the window's
@@ -45,14 +46,14 @@ template <bool WRITE> __global__ __launch_bounds__(PDU_B) void k_pdu_tiles(PduAr
         clen = pdu_min(clen, a.C);
         for (long k = (long)blockIdx.x * PDU_B + tid; k < clen; k += (long)gridDim.x * PDU_B) {
             const long idx = a.C - clen + k;
-            a.arena[idx] = a.prev_arena[idx + a.n_prev];
+            static_cast<float*>(a.arena)[idx] = static_cast<const float*>(a.prev_arena)[idx + a.n_prev];
         }
     }
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long o0 = tile * PDU_T;
         const int cnt = (int)pdu_min(a.n - o0, PDU_T);
         if (!WRITE)
-            for (int j = tid; j < cnt; j += PDU_B) a.arena[a.C + o0 + j] = a.data[o0 + j];
+            for (int j = tid; j < cnt; j += PDU_B) static_cast<float*>(a.arena)[a.C + o0 + j] = static_cast<const float*>(a.data)[o0 + j];
         const long i0 = o0 + (long)tid * PDU_PER;
         bool prev = i0 == 0 ? last_in : (i0 - 1 < a.n ? a.trig[i0 - 1] > a.thr : false);
         unsigned em = 0, cm = 0;
@@ -91,6 +92,56 @@ template <bool WRITE> __global__ __launch_bounds__(PDU_B) void k_pdu_tiles(PduAr
                     if (slot < (u64)a.n) a.edges[slot] = ((unsigned)(i0 + i) << 1) | (cm >> i & 1u);
                     ++slot;
                 }
+        }
+        __syncthreads();                      // the next tile overwrites s_w
+    }
+}
+
+// k_pdu_tiles<false> for the handles whose data is not f32: the same tile counts and the same `last`, with the two copies made
+// in Complex samples (COPY: a StreamToPdu<Complex> handle) or not at all (the burst saver has filled the arena itself).  A kernel
+// of its own so that the f32 handle's code object stays what it was.
+template <bool COPY> __global__ __launch_bounds__(PDU_B) void k_pdu_count(PduArgs a) {
+    __shared__ unsigned s_w[PDU_B / 64];
+    const long ntiles = (a.n + PDU_T - 1) / PDU_T;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const bool last_in = a.st_in->last != 0;
+    cf* const arena = static_cast<cf*>(a.arena);
+    if (COPY) {
+        const cf* const prev = static_cast<const cf*>(a.prev_arena);
+        const u64 orr = a.st_in->open_r;
+        long clen = (orr == PDU_NONE || !prev) ? 0 : (long)(a.w0 - orr);
+        clen = pdu_min(clen, a.C);
+        for (long k = (long)blockIdx.x * PDU_B + tid; k < clen; k += (long)gridDim.x * PDU_B) {
+            const long idx = a.C - clen + k;
+            arena[idx] = prev[idx + a.n_prev];
+        }
+    }
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long o0 = tile * PDU_T;
+        const int cnt = (int)pdu_min(a.n - o0, PDU_T);
+        if (COPY)
+            for (int j = tid; j < cnt; j += PDU_B) arena[a.C + o0 + j] = static_cast<const cf*>(a.data)[o0 + j];
+        const long i0 = o0 + (long)tid * PDU_PER;
+        bool prev = i0 == 0 ? last_in : (i0 - 1 < a.n ? a.trig[i0 - 1] > a.thr : false);
+        unsigned mine = 0;
+#pragma unroll
+        for (int i = 0; i < PDU_PER; ++i) {
+            if (i0 + i < a.n) {
+                const bool cur = a.trig[i0 + i] > a.thr;              // (NaN: not above)
+                if (cur != prev) ++mine;
+                prev = cur;
+                if (i0 + i == a.n - 1) a.st_out->last = cur ? 1 : 0;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+        if (lane == 0) s_w[w] = mine;
+        __syncthreads();
+        if (tid == 0) {
+            unsigned total = 0;
+#pragma unroll
+            for (int q = 0; q < PDU_B / 64; ++q) total += s_w[q];
+            a.tilecnt[tile] = total;
         }
         __syncthreads();                      // the next tile overwrites s_w
     }
@@ -366,12 +417,15 @@ __global__ __launch_bounds__(PDU_MB) void k_pdu_midpoint(const float* __restrict
     }
 }
 
-void launch_pdu(const PduArgs& a, hipStream_t s) {
+void launch_pdu(const PduArgs& a, hipStream_t s, int elem) {
     if (a.n <= 0) return;
+    if (elem != PDU_F32 && a.midpoint) throw Error("Midpointer is a block over f32");
     const long ntiles = (a.n + PDU_T - 1) / PDU_T;
     const unsigned gt = tiles_grid(ntiles);
     RR_HIP(hipMemsetAsync(a.count, 0, sizeof(u64), s));
-    hipLaunchKernelGGL((k_pdu_tiles<false>), dim3(gt), dim3(PDU_B), 0, s, a);
+    if (elem == PDU_F32) hipLaunchKernelGGL((k_pdu_tiles<false>), dim3(gt), dim3(PDU_B), 0, s, a);
+    else if (elem == PDU_C32) hipLaunchKernelGGL((k_pdu_count<true>), dim3(gt), dim3(PDU_B), 0, s, a);
+    else hipLaunchKernelGGL((k_pdu_count<false>), dim3(gt), dim3(PDU_B), 0, s, a);
     launch_bits_tag_offsets(a.tilecnt, ntiles, a.offs, a.etotal, s);
     hipLaunchKernelGGL((k_pdu_tiles<true>), dim3(gt), dim3(PDU_B), 0, s, a);
     const long maxr = a.n / 2 + 1;            // rising edges a window of n samples can hold

@@ -448,7 +448,7 @@ public:
         size_t p = 1;
         rule_ = rr_block_tag_rule(h, &p);
         if (rule_ == RR_ERR) throw Error(rr_last_error());
-        param_ = p ? p : 1;
+        param_ = p || rule_ == RR_TAGS_SHIFT ? p : 1;
     }
     bool drops() const { return rule_ == RR_TAGS_DROP; }
     std::vector<Tag> step(const std::vector<Tag>& tags, size_t consumed, size_t produced) {
@@ -456,6 +456,15 @@ public:
         if (rule_ == RR_TAGS_FORWARD) {
             for (auto& t : tags)
                 if (t.pos() < consumed) pending_.emplace_back((in_abs_ + t.pos()) / param_, t);
+            std::vector<std::pair<uint64_t, Tag>> keep;
+            for (auto& pt : pending_) {
+                if (pt.first < out_abs_ + produced) emit.emplace_back((size_t)(pt.first - out_abs_), pt.second.key(), pt.second.val());
+                else keep.push_back(std::move(pt));
+            }
+            pending_.swap(keep);
+        } else if (rule_ == RR_TAGS_SHIFT) {              // delay.rs:104-108: *param outputs precede the first copied sample
+            for (auto& t : tags)
+                if (t.pos() < consumed) pending_.emplace_back(in_abs_ + t.pos() + param_, t);
             std::vector<std::pair<uint64_t, Tag>> keep;
             for (auto& pt : pending_) {
                 if (pt.first < out_abs_ + produced) emit.emplace_back((size_t)(pt.first - out_abs_), pt.second.key(), pt.second.val());
@@ -888,6 +897,41 @@ public:
         if (n && rr_pdu_edges(h_.h, pos.data(), val.data(), n, &n) != 0) throw Error(rr_last_error());
         std::vector<std::pair<size_t, bool>> out(n);
         for (size_t i = 0; i < n; i++) out[i] = {pos[i], val[i] != 0};
+        return out;
+    }
+};
+
+// ---- The sample-rate path of examples/burst_saver.rs:111-131 (rr_burst_saver_create / rr_burst_saver_push / rr_pdu_records /
+// rr_pdu_fetch_c32): Tee -> [ComplexToMag2 -> SinglePoleIirFilter(alpha)] and [Delay(delay)] -> BurstTagger(threshold) ->
+// StreamToPdu<Complex>(max_size, tail).  push() takes one window of the Complex stream and returns what StreamToPdu's output
+// would receive for it; stream_pos counts positions of the delayed stream.  The block keeps the envelope's state, Delay's
+// history and the open burst.
+class BurstSaver {
+    detail::Handle h_;
+public:
+    struct Pdu {
+        unsigned long long stream_pos;
+        std::vector<Complex> samples;
+    };
+    BurstSaver(Float alpha, Float threshold, size_t delay, size_t max_size, size_t tail)
+        : h_(rr_burst_saver_create(alpha, threshold, delay, max_size, tail)) {}
+    rr_block* handle() const { return h_.h; }
+    // envelope: when given, receives the filtered power of the window (what the trigger branch carries)
+    std::vector<Pdu> push(const std::vector<Complex>& window, std::vector<Float>* envelope = nullptr) {
+        if (envelope) envelope->assign(window.size(), 0.0f);
+        if (rr_burst_saver_push(h_.h, reinterpret_cast<const rr_c32*>(window.data()), window.size(),
+                                envelope && !window.empty() ? envelope->data() : nullptr) != 0)
+            throw Error(rr_last_error());
+        size_t n = 0;
+        if (rr_pdu_records(h_.h, nullptr, 0, &n) != 0) throw Error(rr_last_error());
+        std::vector<rr_pdu_record> rec(n + 1);
+        if (n && rr_pdu_records(h_.h, rec.data(), n, &n) != 0) throw Error(rr_last_error());
+        std::vector<Pdu> out(n);
+        for (size_t i = 0; i < n; i++) {
+            out[i].stream_pos = rec[i].stream_pos;
+            out[i].samples.resize(rec[i].len);
+            if (rr_pdu_fetch_c32(h_.h, i, reinterpret_cast<rr_c32*>(out[i].samples.data()), rec[i].len) != 0) throw Error(rr_last_error());
+        }
         return out;
     }
 };
@@ -1739,6 +1783,14 @@ inline auto AudioChain(ReadStream<Float> src, const std::vector<Float>& taps, si
 struct FmTx {
     static auto new_(ReadStream<Float> src, size_t interp, size_t deci, double k) {
         return Fused<Float, Complex>::make(std::move(src), [&] { return rr_fm_tx_create(interp, deci, detail::f64_bits(k)); });
+    }
+};
+
+// Delay::new(src, delay) (src/delay.rs): `delay` default elements, then the input; tags move `delay` outputs on (RR_TAGS_SHIFT).
+// T of 1, 4 or 8 bytes.  set_delay is not offered.
+template <class T> struct Delay {
+    static auto new_(ReadStream<T> src, size_t delay) {
+        return Fused<T, T>::make(std::move(src), [&] { return rr_delay_create(delay, sizeof(T)); });
     }
 };
 
