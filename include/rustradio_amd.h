@@ -201,6 +201,11 @@ rr_block *rr_vco_create(unsigned long long k_bits);
 /* ComplexToMag2::new(src) (src/complex_to_mag2.rs:8-21): Complex in, f32 out, re*re + im*im with the reference's three
  * f32 roundings (num-complex norm_sqr, no FMA).  #[rustradio(sync)].  Bit-exact.  Tags: RR_TAGS_FORWARD, 1. */
 rr_block *rr_complex_to_mag2_create(void);
+/* The first Map of examples/airspy_am_decode.rs ("AirSPY to Complex"): input elements are 4 bytes, a little-endian u32 with I in
+ * the low 16 bits and Q in the high 16, each an i16; out = Complex(f32(i) / 1000.0, f32(q) / 1000.0), two true IEEE f32 divisions
+ * (num-complex divides each component; no reciprocal).  #[rustradio(sync)], the protocol of rr_complex_to_mag2; input windows
+ * count u32 elements.  Bit-exact.  Tags: RR_TAGS_FORWARD, 1. */
+rr_block *rr_airspy_decode_create(void);
 
 /* SinglePoleIirFilter::<Float|Complex>::new(src, alpha) (src/single_pole_iir_filter.rs:11-93): elem_size 4 or 8 (Complex:
  * re and im are two independent recurrences).  y = x*alpha + y_prev*(1 - alpha), y_prev = 0 at the start, carried across calls
@@ -883,6 +888,48 @@ int rr_afsk_demod_push_dev(rr_block *b, const void *d_in, size_t in_stride, size
 int rr_afsk_demod_push(rr_block *b, const float *in, size_t in_stride, size_t n, float *out, size_t out_stride, size_t *produced);
 /* *tile_samples = outputs of one workgroup (2048), *carry_samples = samples of a stream a handle carries (L + H) */
 int rr_afsk_demod_dims(const rr_block *b, size_t *tile_samples, size_t *carry_samples);
+
+/* The audio path of examples/airspy_am_decode.rs behind the RF filter,
+ *   Map(|v| v.norm()) -> FftFilterFloat::new(_, taps) -> RationalResampler::new(_, interp, deci) -> MultiplyConst::new(_, scale)
+ * x nstreams behind one handle, behind the Complex windows of rr_channelizer_create (or rr_fftfilter), with the samples and every
+ * stream's state staying on the device.  A batch block like rr_afsk_demod: rr_block_work on the handle is an error.
+ * DEFINITION, per stream (x = every Complex sample pushed so far, L = ntaps, I:D = interp:deci after gcd reduction):
+ *   m[k]   = fl32( sqrt( f64(x[k].re)^2 + f64(x[k].im)^2 ) )      m[k < 0] = 0   (FftFilterFloat starts from zero history)
+ *   y[i]   = sum_j taps[j] m[i - j]                               j = 0 .. L-1, f32
+ *   out[o] = scale * y[ floor(o D / I) ]                          one f32 multiply, last
+ * After N samples in all a stream has delivered exactly ceil(N I / D) outputs (src/rational_resampler.rs:183-198).  The squares
+ * of f32 values are exact in f64, so m is one f64 add, one correctly rounded f64 sqrt and one narrowing: the bits of glibc's
+ * hypotf, which Complex::norm() calls, for every finite input.  The bits of out do not depend on how the stream was cut into
+ * pushes, on which tile or lane computed them or on what the other streams hold: every output is one fixed sequence of f32
+ * operations that L alone determines (am_core.hpp: 64 strided partial sums of fmaf, a six-level tree of adds, the multiply), and
+ * stream c of an N-stream handle equals a 1-stream handle fed row c.
+ * BOUND: against the float64 form of the definition (exact m, exact sums) each output is within
+ *   B[o] = 1.01 (L + 2) 2^-24 |scale| sum_j |taps[j]| m64[p(o) - j],  p(o) = floor(o D / I)
+ * (outputs that are not subnormal).
+ * ONE launch per push whatever nstreams, n, L and the ratio are.  The filter is a direct, decimate-first sum: only the y the
+ * resampler picks are computed (L multiply-adds per OUTPUT), not the reference's overlap-save transform at the input rate.  A
+ * handle carries the latest L - 1 magnitudes of every stream on the device (rr_am_demod_dims); the counts live on the host.
+ * DEVIATIONS: the reference's FftFilterFloat withholds a partial block and never flushes it; this delivers every output whose
+ * inputs exist (same values, a later tail).  A NaN at x[k] makes NaN exactly the outputs o with p(o) - L + 1 <= k <= p(o) and
+ * touches no other bit (the reference poisons whole transform blocks, a superset); after +-Inf the set is not pinned
+ * (hypot(Inf, NaN) is Inf in libm and NaN by the definition).
+ * NULL + rr_last_error, said before any device is touched: "nstreams out of range" (0 or above 4096), "AmDemod needs 1 to 16384
+ * finite taps" (refused beyond, never clamped), "RationalResampler created using deci 0", "RationalResampler created using
+ * interp 0" (the reference's sentences), "am demod: reduced ratio part above 2^31", "scale must be finite". */
+rr_block *rr_am_demod_create(size_t nstreams, const float *taps, size_t ntaps, size_t interp, size_t deci, float scale);
+/* stream c: its next n samples at d_in + c*in_stride (rr_c32 elements: the out_cap windows rr_channelizer_create writes), its
+ * *produced outputs at d_out + c*out_stride (f32 elements).  A push of n samples behind N0 earlier ones writes outputs
+ * [O(N0), O(N0 + n)), O(N) = ceil(N I / D).  *produced (may be NULL) depends on lengths only, is the same for every stream and is
+ * written before the call returns.  Nothing at or beyond a stream's count is written.  RR_ERR, nothing launched and nothing
+ * changed: in_stride below n, out_stride below produced, nstreams * n or nstreams * produced above 2^30, a null buffer with work
+ * to do.  n == 0 launches nothing and leaves every state alone.  Asynchronous on hip_stream. */
+int rr_am_demod_push_dev(rr_block *b, const void *d_in, size_t in_stride, size_t n,
+                         void *d_out, size_t out_stride, size_t *produced, void *hip_stream);
+/* The same with host pointers: copies the samples down, runs, waits and copies each stream's outputs back. */
+int rr_am_demod_push(rr_block *b, const rr_c32 *in, size_t in_stride, size_t n, float *out, size_t out_stride, size_t *produced);
+/* *tile_outputs = outputs of one workgroup (32 .. 192, chosen at create from (I, D, L)), *carry_samples = magnitudes of a stream
+ * a handle carries (L - 1) */
+int rr_am_demod_dims(const rr_block *b, size_t *tile_outputs, size_t *carry_samples);
 
 /* The modulators of the reference's two packet transmitters, line bits in, baseband out, in PDU form (rr_block_work on the handle
  * is an error).  Bits are u8 as rr_hdlc_framer_push_dev writes them without RR_FRAME_SYMBOLS; a byte is 1 when it is nonzero (the

@@ -56,6 +56,7 @@ unsafe extern "C" {
     fn rr_vco_create(k_bits: u64) -> *mut RrBlock;
     fn rr_fm_tx_create(interp: usize, deci: usize, k_bits: u64) -> *mut RrBlock;
     fn rr_complex_to_mag2_create() -> *mut RrBlock;
+    fn rr_airspy_decode_create() -> *mut RrBlock;
     fn rr_single_pole_iir_create(alpha: f32, elem_size: usize) -> *mut RrBlock;
     // (declared for completeness: the detector's block needs rr_burst_edges too and is not written yet)
     #[allow(dead_code)]
@@ -228,6 +229,18 @@ unsafe extern "C" {
                           produced: *mut usize) -> c_int;
     #[allow(dead_code)]
     fn rr_afsk_demod_dims(b: *const RrBlock, tile_samples: *mut usize, carry_samples: *mut usize) -> c_int;
+    // (declared for completeness: the audio path of examples/airspy_am_decode.rs for N stations is a batch block behind the
+    //  N-channel blocks; its typed block is not written yet)
+    #[allow(dead_code)]
+    fn rr_am_demod_create(nstreams: usize, taps: *const f32, ntaps: usize, interp: usize, deci: usize, scale: f32) -> *mut RrBlock;
+    #[allow(dead_code)]
+    fn rr_am_demod_push_dev(b: *mut RrBlock, d_in: *const c_void, in_stride: usize, n: usize, d_out: *mut c_void, out_stride: usize,
+                            produced: *mut usize, hip_stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn rr_am_demod_push(b: *mut RrBlock, input: *const Complex, in_stride: usize, n: usize, out: *mut f32, out_stride: usize,
+                        produced: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn rr_am_demod_dims(b: *const RrBlock, tile_outputs: *mut usize, carry_samples: *mut usize) -> c_int;
     // (declared for completeness: the PDU-form modulator of examples/bell202.rs:166-183 and g3ruh.rs:256-272 takes pushes of line
     //  bits, not a stream; its typed block is not written yet)
     #[allow(dead_code)]
@@ -586,6 +599,13 @@ impl GpuMap<u8, Complex> {
     /// `RtlSdrDecode::new(src)` (src/rtlsdr_decode.rs:9-47)
     pub fn rtlsdr_decode(src: ReadStream<u8>) -> Result<(Self, ReadStream<Complex>)> {
         Self::wrap(unsafe { rr_rtlsdr_decode_create() }, "GpuRtlSdrDecode", false, src)
+    }
+}
+impl GpuMap<u32, Complex> {
+    /// The `Map` "AirSPY to Complex" of examples/airspy_am_decode.rs: i16 I in the low half of the word, i16 Q in the high half,
+    /// each divided by 1000.0; a sync block: tags pass through position for position
+    pub fn airspy_decode(src: ReadStream<u32>) -> Result<(Self, ReadStream<Complex>)> {
+        Self::wrap(unsafe { rr_airspy_decode_create() }, "GpuAirspyDecode", true, src)
     }
 }
 impl GpuMap<u8, u8> {

@@ -18,6 +18,8 @@ what the reference would pass to `consume()`/`produce()`.
     SymbolSync           src/symbol_sync.rs:46-217, src/iir_filter.rs:104-125   (N streams per handle, a window of each per call)
     AddConst             src/add_const.rs:51-68
     AfskDemod            Hilbert -> QuadratureDemod -> FftFilterFloat -> AddConst, examples/ax25-1200-rx.rs:238-247 (N streams per handle)
+    AmDemod              norm -> FftFilterFloat -> RationalResampler -> MultiplyConst, examples/airspy_am_decode.rs (N streams per handle)
+    AirspyDecode         examples/airspy_am_decode.rs, the Map "AirSPY to Complex"
     FskTx                line bits -> AFSK / FSK baseband, examples/bell202.rs:166-183, examples/g3ruh.rs:256-272 (a push of bits per call)
     low_pass / low_pass_complex / hilbert_taps / make_window   src/fir.rs:594-680, src/window.rs
 
@@ -30,6 +32,7 @@ import ctypes as C
 import numpy as np
 
 import contextlib
+import math
 import struct
 import threading
 
@@ -583,6 +586,12 @@ def FmTx(interp: int, deci: int, k: float) -> Block:
     """RationalResampler(interp, deci) -> Vco(k) fused into one block (rr_fm_tx_create; the modulator of
     examples/fm_tx.rs:84-91); f32 in, Complex out."""
     return Block(lib().rr_fm_tx_create(interp, deci, _f64_bits(k)), np.float32, np.complex64)
+
+
+def AirspyDecode() -> Block:
+    """The first Map of examples/airspy_am_decode.rs: AirSPY u32 words (i16 I low, i16 Q high) in, Complex(i / 1000, q / 1000)
+    out, bit-exact; windows count u32 elements."""
+    return Block(lib().rr_airspy_decode_create(), np.uint32, np.complex64)
 
 
 def ComplexToMag2() -> Block:
@@ -1313,6 +1322,59 @@ class AfskDemod(Block):
         k = C.c_size_t(0)
         if lib().rr_afsk_demod_push(self._h, _ptr(a) if n else None, n, n, _ptr(out) if n else None, n, C.byref(k)) != 0:
             raise ValueError(last_error())
+        return out[:, :k.value].copy()
+
+
+class AmDemod(Block):
+    """norm -> FftFilterFloat(taps) -> RationalResampler(interp, deci) -> MultiplyConst(scale) x nstreams behind one handle
+    (rr_am_demod_create; examples/airspy_am_decode.rs; not a stream block: work() raises): the next n Complex samples of each
+    stream in, the audio samples they complete out — ceil(N interp / deci) of each after N samples in all.  Only the filter outputs
+    the resampler picks are computed.  The bits do not depend on how a stream is cut into pushes.  Every stream's latest
+    magnitudes stay on the device.  See include/rustradio_amd.h."""
+
+    def __init__(self, nstreams: int, taps, interp: int = 1, deci: int = 1, scale: float = 1.0):
+        t = np.ascontiguousarray(taps, np.float32).ravel()
+        super().__init__(lib().rr_am_demod_create(int(nstreams), _ptr(t) if len(t) else None, len(t), int(interp), int(deci),
+                                                  float(scale)), np.complex64, np.float32)
+        g = math.gcd(int(interp), int(deci))
+        self.nstreams, self.ntaps, self.interp, self.deci = int(nstreams), len(t), int(interp) // g, int(deci) // g
+        self.total = 0                         # samples every stream has taken
+
+    def dims(self):
+        """-> (tile_outputs, carry_samples) (rr_am_demod_dims)"""
+        t, c = C.c_size_t(0), C.c_size_t(0)
+        if lib().rr_am_demod_dims(self._h, C.byref(t), C.byref(c)) != 0:
+            raise RuntimeError(last_error())
+        return t.value, c.value
+
+    def count(self, n: int) -> int:
+        """outputs of each stream a push of n samples would deliver now"""
+        up = lambda N: (N * self.interp + self.deci - 1) // self.deci
+        return up(self.total + int(n)) - up(self.total)
+
+    def push_dev(self, d_in: int, in_stride: int, n: int, d_out: int, out_stride: int, stream: int = 0) -> int:
+        """rr_am_demod_push_dev: stream c's next n samples at d_in + c * in_stride (raw device pointers, Complex elements), its
+        outputs to d_out + c * out_stride (f32 elements); asynchronous on `stream` -> produced"""
+        k = C.c_size_t(0)
+        if lib().rr_am_demod_push_dev(self._h, C.c_void_p(d_in), int(in_stride), int(n), C.c_void_p(d_out), int(out_stride),
+                                      C.byref(k), C.c_void_p(stream)) != 0:
+            raise ValueError(last_error())
+        self.total += int(n)
+        return k.value
+
+    def push(self, x) -> np.ndarray:
+        """rr_am_demod_push on a host array of shape (nstreams, n) (or (n,) for one stream) -> float32 (nstreams, produced)"""
+        a = np.ascontiguousarray(x, np.complex64)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        if a.ndim != 2 or a.shape[0] != self.nstreams:
+            raise ValueError("AmDemod.push: one row per stream")
+        n = a.shape[1]
+        cap = self.count(n)
+        out = np.zeros((self.nstreams, max(cap, 1)), np.float32)
+        k = C.c_size_t(0)
+        if lib().rr_am_demod_push(self._h, _ptr(a) if n else None, n, n, _ptr(out) if cap else None, cap, C.byref(k)) != 0:
+            raise ValueError(last_error())
+        self.total += n
         return out[:, :k.value].copy()
 
 

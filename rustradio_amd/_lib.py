@@ -19,7 +19,7 @@ SYMBOLS = [
     "rr_max_attenuation", "rr_make_window", "rr_compute_ntaps", "rr_low_pass", "rr_low_pass_complex",
     "rr_hilbert_taps", "rr_multiband",
     "rr_fir_c32_create", "rr_fir_f32_create", "rr_fftfilter_create", "rr_fftfilter_float_create",
-    "rr_resampler_create", "rr_quaddemod_create", "rr_rtlsdr_decode_create", "rr_fftstream_create", "rr_fft_process", "rr_multiply_const_f32_create", "rr_multiply_const_c32_create", "rr_add_const_f32_create", "rr_add_const_c32_create", "rr_fastfm_create", "rr_hilbert_create", "rr_fm_chain_create", "rr_fm_chain_u8_create", "rr_fir_fftfilter_create", "rr_fir_fm_chain_create", "rr_audio_chain_create", "rr_vco_create", "rr_fm_tx_create", "rr_complex_to_mag2_create", "rr_single_pole_iir_create", "rr_burst_detector_create", "rr_burst_edges", "rr_binary_slicer_create", "rr_nrzi_decode_create", "rr_descrambler_create", "rr_correlate_access_code_tag_create", "rr_bit_decoder_create", "rr_bit_tags", "rr_wpcr_create", "rr_wpcr_process_dev", "rr_wpcr_process", "rr_wpcr_results", "rr_debug_wpcr_spectrum", "rr_stream_to_pdu_create", "rr_stream_to_pdu_push_dev", "rr_stream_to_pdu_push", "rr_pdu_records", "rr_pdu_edges", "rr_pdu_arena_dev", "rr_pdu_fetch", "rr_debug_pdu_ranks", "rr_wpcr_process_pdus", "rr_stream_to_pdu_c32_create", "rr_stream_to_pdu_push_c32", "rr_pdu_fetch_c32", "rr_delay_create", "rr_burst_saver_create", "rr_burst_saver_push_dev", "rr_burst_saver_push", "rr_burst_saver_dims", "rr_wpcr_pack_dev", "rr_nrzi_encode_create", "rr_scrambler_g3ruh_create", "rr_hdlc_framer_create", "rr_hdlc_framer_bound", "rr_hdlc_framer_push_dev", "rr_hdlc_framer_push", "rr_hdlc_framer_records", "rr_hdlc_framer_dims", "rr_hdlc_framer_produced_dev", "rr_hdlc_deframer_create", "rr_hdlc_deframer_push_dev", "rr_hdlc_deframer_push", "rr_hdlc_frames", "rr_hdlc_frame_bytes", "rr_hdlc_bytes_dev", "rr_hdlc_stats", "rr_hdlc_deframer_dims", "rr_kiss_decode_create", "rr_kiss_decode_push_dev", "rr_kiss_decode_push", "rr_kiss_packets", "rr_kiss_packet_bytes", "rr_kiss_packet_bytes_dev", "rr_kiss_decode_stats", "rr_kiss_decode_dims", "rr_kiss_encode_create", "rr_kiss_encode_bound", "rr_kiss_encode_push_dev", "rr_kiss_encode_push", "rr_kiss_encode_records", "rr_kiss_encode_dims", "rr_kiss_encode_frames", "rr_hdlc_framer_push_kiss", "rr_symbol_sync_create", "rr_symbol_sync_push_dev", "rr_symbol_sync_push", "rr_symbol_sync_produced", "rr_symbol_sync_counts_dev", "rr_symbol_sync_dims", "rr_debug_symbol_sync_state", "rr_afsk_demod_create", "rr_afsk_demod_push_dev", "rr_afsk_demod_push", "rr_afsk_demod_dims", "rr_fsk_tx_create", "rr_fsk_tx_count", "rr_fsk_tx_push_dev", "rr_fsk_tx_push", "rr_fsk_tx_dims", "rr_fsk_tx_multi_create", "rr_fsk_tx_multi_bound", "rr_fsk_tx_multi_push_dev", "rr_fsk_tx_multi_push", "rr_fsk_tx_multi_counts", "rr_fsk_tx_multi_counts_dev", "rr_fsk_tx_multi_positions", "rr_fsk_tx_multi_dims", "rr_hdlc_receiver_create", "rr_hdlc_receiver_push_dev", "rr_hdlc_receiver_push", "rr_hdlc_receiver_frames", "rr_hdlc_receiver_frame_bytes", "rr_hdlc_receiver_bytes_dev", "rr_hdlc_receiver_stats", "rr_hdlc_receiver_consumed", "rr_hdlc_receiver_dims", "rr_il2p_receiver_create", "rr_il2p_receiver_push_dev", "rr_il2p_receiver_push", "rr_il2p_receiver_headers", "rr_il2p_receiver_stats", "rr_il2p_receiver_consumed", "rr_il2p_receiver_dims", "rr_pwm_decoder_create", "rr_pwm_decoder_push_dev", "rr_pwm_decoder_push", "rr_pwm_decoder_flush", "rr_pwm_frames", "rr_pwm_frame_bits", "rr_pwm_bits_dev", "rr_pwm_decoder_dims", "rr_hilbert_fir_create", "rr_fm_multi_create", "rr_fm_multi_u8_create", "rr_channelizer_create", "rr_channelizer_u8_create", "rr_fm_receiver_create", "rr_fm_receiver_u8_create", "rr_block_out_windows", "rr_block_destroy",
+    "rr_resampler_create", "rr_quaddemod_create", "rr_rtlsdr_decode_create", "rr_fftstream_create", "rr_fft_process", "rr_multiply_const_f32_create", "rr_multiply_const_c32_create", "rr_add_const_f32_create", "rr_add_const_c32_create", "rr_fastfm_create", "rr_hilbert_create", "rr_fm_chain_create", "rr_fm_chain_u8_create", "rr_fir_fftfilter_create", "rr_fir_fm_chain_create", "rr_audio_chain_create", "rr_vco_create", "rr_fm_tx_create", "rr_complex_to_mag2_create", "rr_airspy_decode_create", "rr_am_demod_create", "rr_am_demod_push_dev", "rr_am_demod_push", "rr_am_demod_dims", "rr_single_pole_iir_create", "rr_burst_detector_create", "rr_burst_edges", "rr_binary_slicer_create", "rr_nrzi_decode_create", "rr_descrambler_create", "rr_correlate_access_code_tag_create", "rr_bit_decoder_create", "rr_bit_tags", "rr_wpcr_create", "rr_wpcr_process_dev", "rr_wpcr_process", "rr_wpcr_results", "rr_debug_wpcr_spectrum", "rr_stream_to_pdu_create", "rr_stream_to_pdu_push_dev", "rr_stream_to_pdu_push", "rr_pdu_records", "rr_pdu_edges", "rr_pdu_arena_dev", "rr_pdu_fetch", "rr_debug_pdu_ranks", "rr_wpcr_process_pdus", "rr_stream_to_pdu_c32_create", "rr_stream_to_pdu_push_c32", "rr_pdu_fetch_c32", "rr_delay_create", "rr_burst_saver_create", "rr_burst_saver_push_dev", "rr_burst_saver_push", "rr_burst_saver_dims", "rr_wpcr_pack_dev", "rr_nrzi_encode_create", "rr_scrambler_g3ruh_create", "rr_hdlc_framer_create", "rr_hdlc_framer_bound", "rr_hdlc_framer_push_dev", "rr_hdlc_framer_push", "rr_hdlc_framer_records", "rr_hdlc_framer_dims", "rr_hdlc_framer_produced_dev", "rr_hdlc_deframer_create", "rr_hdlc_deframer_push_dev", "rr_hdlc_deframer_push", "rr_hdlc_frames", "rr_hdlc_frame_bytes", "rr_hdlc_bytes_dev", "rr_hdlc_stats", "rr_hdlc_deframer_dims", "rr_kiss_decode_create", "rr_kiss_decode_push_dev", "rr_kiss_decode_push", "rr_kiss_packets", "rr_kiss_packet_bytes", "rr_kiss_packet_bytes_dev", "rr_kiss_decode_stats", "rr_kiss_decode_dims", "rr_kiss_encode_create", "rr_kiss_encode_bound", "rr_kiss_encode_push_dev", "rr_kiss_encode_push", "rr_kiss_encode_records", "rr_kiss_encode_dims", "rr_kiss_encode_frames", "rr_hdlc_framer_push_kiss", "rr_symbol_sync_create", "rr_symbol_sync_push_dev", "rr_symbol_sync_push", "rr_symbol_sync_produced", "rr_symbol_sync_counts_dev", "rr_symbol_sync_dims", "rr_debug_symbol_sync_state", "rr_afsk_demod_create", "rr_afsk_demod_push_dev", "rr_afsk_demod_push", "rr_afsk_demod_dims", "rr_fsk_tx_create", "rr_fsk_tx_count", "rr_fsk_tx_push_dev", "rr_fsk_tx_push", "rr_fsk_tx_dims", "rr_fsk_tx_multi_create", "rr_fsk_tx_multi_bound", "rr_fsk_tx_multi_push_dev", "rr_fsk_tx_multi_push", "rr_fsk_tx_multi_counts", "rr_fsk_tx_multi_counts_dev", "rr_fsk_tx_multi_positions", "rr_fsk_tx_multi_dims", "rr_hdlc_receiver_create", "rr_hdlc_receiver_push_dev", "rr_hdlc_receiver_push", "rr_hdlc_receiver_frames", "rr_hdlc_receiver_frame_bytes", "rr_hdlc_receiver_bytes_dev", "rr_hdlc_receiver_stats", "rr_hdlc_receiver_consumed", "rr_hdlc_receiver_dims", "rr_il2p_receiver_create", "rr_il2p_receiver_push_dev", "rr_il2p_receiver_push", "rr_il2p_receiver_headers", "rr_il2p_receiver_stats", "rr_il2p_receiver_consumed", "rr_il2p_receiver_dims", "rr_pwm_decoder_create", "rr_pwm_decoder_push_dev", "rr_pwm_decoder_push", "rr_pwm_decoder_flush", "rr_pwm_frames", "rr_pwm_frame_bits", "rr_pwm_bits_dev", "rr_pwm_decoder_dims", "rr_hilbert_fir_create", "rr_fm_multi_create", "rr_fm_multi_u8_create", "rr_channelizer_create", "rr_channelizer_u8_create", "rr_fm_receiver_create", "rr_fm_receiver_u8_create", "rr_block_out_windows", "rr_block_destroy",
     "rr_block_work", "rr_block_work_dev", "rr_block_eof", "rr_block_name", "rr_block_tag_rule", "rr_block_in_elem_size",
     "rr_block_out_elem_size", "rr_block_sync", "rr_fftfilter_dims", "rr_fir_fft_tile", "rr_fir_set_rotator_mode",
     "rr_block_set_profiling", "rr_block_profile", "rr_debug_fft_stamps", "rr_debug_kernel_launches",
@@ -87,6 +87,7 @@ def lib():
     L.rr_vco_create.argtypes = [C.c_ulonglong]; L.rr_vco_create.restype = vp
     L.rr_fm_tx_create.argtypes = [sz, sz, C.c_ulonglong]; L.rr_fm_tx_create.restype = vp
     L.rr_complex_to_mag2_create.argtypes = []; L.rr_complex_to_mag2_create.restype = vp
+    L.rr_airspy_decode_create.argtypes = []; L.rr_airspy_decode_create.restype = vp
     L.rr_single_pole_iir_create.argtypes = [f32, sz]; L.rr_single_pole_iir_create.restype = vp
     L.rr_burst_detector_create.argtypes = [f32, f32]; L.rr_burst_detector_create.restype = vp
     L.rr_burst_edges.argtypes = [vp, vp, vp, sz, psz]; L.rr_burst_edges.restype = i32
@@ -191,6 +192,10 @@ def lib():
     L.rr_afsk_demod_push_dev.argtypes = [vp, vp, sz, sz, vp, sz, psz, vp]; L.rr_afsk_demod_push_dev.restype = i32
     L.rr_afsk_demod_push.argtypes = [vp, vp, sz, sz, vp, sz, psz]; L.rr_afsk_demod_push.restype = i32
     L.rr_afsk_demod_dims.argtypes = [vp, psz, psz]; L.rr_afsk_demod_dims.restype = i32
+    L.rr_am_demod_create.argtypes = [sz, vp, sz, sz, sz, f32]; L.rr_am_demod_create.restype = vp
+    L.rr_am_demod_push_dev.argtypes = [vp, vp, sz, sz, vp, sz, psz, vp]; L.rr_am_demod_push_dev.restype = i32
+    L.rr_am_demod_push.argtypes = [vp, vp, sz, sz, vp, sz, psz]; L.rr_am_demod_push.restype = i32
+    L.rr_am_demod_dims.argtypes = [vp, psz, psz]; L.rr_am_demod_dims.restype = i32
     L.rr_fsk_tx_create.argtypes = [i32, sz, sz, f32, f32, u64, f32, sz, sz, u64]; L.rr_fsk_tx_create.restype = vp
     L.rr_fsk_tx_count.argtypes = [vp, sz, psz, psz]; L.rr_fsk_tx_count.restype = i32
     L.rr_fsk_tx_push_dev.argtypes = [vp, vp, sz, vp, sz, vp, sz, psz, psz, vp]; L.rr_fsk_tx_push_dev.restype = i32

@@ -87,6 +87,7 @@ template <class T> static T* as(const rr_block* b, const char* what, const char*
 }
 static const char NOT_WPCR[] = "not a wpcr handle", NOT_PDU[] = "not a stream_to_pdu handle", NOT_FRAMER[] = "not an hdlc framer handle";
 static const char NOT_DEFRAMER[] = "not an hdlc deframer handle", NOT_SYNC[] = "not a symbol sync handle", NOT_AFSK[] = "not an afsk demod handle";
+static const char NOT_AM[] = "not an am demod handle";
 static const char NOT_RECEIVER[] = "not an hdlc receiver handle", NOT_PWM[] = "not a pwm decoder handle";
 static const char NOT_IL2P[] = "not an il2p receiver handle";
 static const char NOT_FSK[] = "not an fsk tx handle", NOT_FSKM[] = "not an fsk tx multi handle";
@@ -954,6 +955,38 @@ int rr_afsk_demod_dims(const rr_block* b, size_t* tile_samples, size_t* carry_sa
     *carry_samples = (size_t)y->g.C;
     return 0;
 }
+rr_block* rr_am_demod_create(size_t nstreams, const float* taps, size_t ntaps, size_t interp, size_t deci, float scale) {
+    if (const char* e = rr::am_check(nstreams, taps, ntaps, interp, deci, scale)) return refuse_create(e);
+    return make_block([&] { return new rr::AmDemod(nstreams, taps, ntaps, interp, deci, scale); });
+}
+int rr_am_demod_push_dev(rr_block* b, const void* d_in, size_t in_stride, size_t n, void* d_out, size_t out_stride, size_t* produced,
+                         void* hip_stream) {
+    auto* y = as<rr::AmDemod>(b, "rr_am_demod_push_dev", NOT_AM);
+    if (!y) return RR_ERR;
+    size_t k = 0;
+    const char* e = rr::am_check_push(y->nstreams, y->g, y->e, d_in, in_stride, n, d_out, out_stride, &k);
+    if (produced) *produced = k;
+    if (e) { rr::set_last_error(e); return RR_ERR; }
+    return on_device(y, hip_stream, [&](hipStream_t s) {
+        y->push_dev(static_cast<const rr::cf*>(d_in), in_stride, n, static_cast<float*>(d_out), out_stride, s);
+    });
+}
+int rr_am_demod_push(rr_block* b, const rr_c32* in, size_t in_stride, size_t n, float* out, size_t out_stride, size_t* produced) {
+    auto* y = as<rr::AmDemod>(b, "rr_am_demod_push", NOT_AM);
+    if (!y) return RR_ERR;
+    size_t k = 0;
+    const char* e = rr::am_check_push(y->nstreams, y->g, y->e, in, in_stride, n, out, out_stride, &k);
+    if (produced) *produced = k;
+    if (e) { rr::set_last_error(e); return RR_ERR; }
+    return guarded([&] { y->push_host(reinterpret_cast<const rr::cf*>(in), in_stride, n, out, out_stride); });
+}
+int rr_am_demod_dims(const rr_block* b, size_t* tile_outputs, size_t* carry_samples) {
+    auto* y = as<rr::AmDemod>(b, "rr_am_demod_dims", NOT_AM);
+    if (!y || !tile_outputs || !carry_samples) { if (y) rr::set_last_error("rr_am_demod_dims: null argument"); return RR_ERR; }
+    *tile_outputs = (size_t)y->g.T;
+    *carry_samples = (size_t)y->g.C;
+    return 0;
+}
 rr_block* rr_fsk_tx_create(int mode, size_t interp1, size_t deci1, float lo, float hi, unsigned long long k1_bits, float gain,
                            size_t interp2, size_t deci2, unsigned long long k2_bits) {
     const double k1 = f64_from_bits(k1_bits), k2 = f64_from_bits(k2_bits);
@@ -1095,6 +1128,9 @@ int rr_fsk_tx_multi_dims(const rr_block* b, size_t* audio_tile, size_t* out_tile
     *out_tile = (size_t)rr::FSK_OT;
     *scan_chunk_tiles = (size_t)rr::FSK_SCAN_CHUNK;
     return 0;
+}
+rr_block* rr_airspy_decode_create(void) {
+    return make_block([&] { return new rr::AirspyDecode(); }, RR_TAGS_FORWARD, 1);
 }
 rr_block* rr_rtlsdr_decode_create(void) {
     return make_block([&] { return new rr::RtlSdrDecode(); });

@@ -1,5 +1,5 @@
 // blocks_packet.cpp — host side of the packet-side blocks (blocks_packet.hpp): the sync blocks, the burst and bit blocks, and the
-// batch handles (Wpcr, StreamToPdu, Delay, BurstSaver, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver, AfskDemod, FskTx, FskTxMulti, KissDecode, KissEncode).  Citations are to the reference's src, as in blocks.cpp.
+// batch handles (Wpcr, StreamToPdu, Delay, BurstSaver, HdlcFramer, HdlcDeframer, PwmDecoder, SymbolSync, HdlcReceiver, AfskDemod, AmDemod, FskTx, FskTxMulti, KissDecode, KissEncode).  Citations are to the reference's src, as in blocks.cpp.
 #include "blocks_packet.hpp"
 
 #include <algorithm>
@@ -91,6 +91,10 @@ void FmTx::emit(const void* in, void* out, int64_t r, int64_t n_gather, int64_t 
 ComplexToMag2::ComplexToMag2() : SyncBlock("ComplexToMag2", 8, 4) {}
 void ComplexToMag2::run(const void* in, void* out, size_t n, hipStream_t s) {
     launch_mag2(static_cast<const cf*>(in), static_cast<float*>(out), (long)n, s);
+}
+AirspyDecode::AirspyDecode() : SyncBlock("AirspyDecode", 4, 8) {}
+void AirspyDecode::run(const void* in, void* out, size_t n, hipStream_t s) {
+    launch_airspy_decode(static_cast<const unsigned*>(in), static_cast<cf*>(out), (long)n, s);
 }
 IirState::IirState(float alpha, int nrows, hipStream_t s) : rows(nrows) {
     if (!(alpha >= 0.0f && alpha <= 1.0f)) throw Error("alpha out of range");          // single_pole_iir_filter.rs:38-41 (None)
@@ -1310,6 +1314,58 @@ size_t AfskDemod::push_host(const float* in, size_t in_stride, size_t n, float* 
         produced = push_dev(h_in.p, in_stride, n, h_out.p, n, stream);
         for (size_t c = 0; c < nstreams && produced; c++)
             hstage().d2h(out + c * out_stride, h_out.p + c * n, produced * sizeof(float), stream);
+    });
+    return produced;
+}
+
+// ---- AmDemod (examples/airspy_am_decode.rs; fft_filter.rs:365-491, rational_resampler.rs:183-198, multiply_const.rs:20-22; kernels_am.hip) ----
+AmDemod::AmDemod(size_t ns, const float* taps, size_t ntaps, size_t interp, size_t deci, float sc)
+    : BatchBlock("Norm>FftFilterFloat>RationalResampler>MultiplyConst", 8, 4,
+                 "AmDemod runs nstreams streams: rr_am_demod_push / rr_am_demod_push_dev"),
+      nstreams(ns), scale(sc) {
+    if (const char* err = am_check(ns, taps, ntaps, interp, deci, sc)) throw Error(err);
+    g = am_geom_of(ntaps, interp, deci);
+    int dev = 0, granted = 0;                        // what a workgroup may take of the LDS: asked, not assumed
+    RR_HIP(hipGetDevice(&dev));
+    RR_HIP(hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    if ((size_t)granted < am_lds_bytes()) throw Error("am demod: the device grants a workgroup less LDS than a tile needs");
+    d_taps.upload(taps, ntaps, stream);
+    carry.zero(ns * (size_t)g.C + 1, stream);
+    RR_HIP(hipStreamSynchronize(stream));
+}
+size_t AmDemod::push_dev(const cf* d_in, size_t in_stride, size_t n, float* d_out, size_t out_stride, hipStream_t s) {
+    size_t produced = 0;
+    if (const char* err = am_check_push(nstreams, g, e, d_in, in_stride, n, d_out, out_stride, &produced)) throw Error(err);
+    if (!n) return 0;                          // a push of no samples launches nothing and leaves every state alone
+    AmArgs a{};
+    a.g = g;
+    a.in = reinterpret_cast<const float*>(d_in); a.in_stride = (long)in_stride; a.n = (long)n;
+    a.out = d_out; a.out_stride = (long)out_stride; a.produced = (long)produced;
+    a.carry_in = carry.in(); a.carry_out = carry.out();
+    a.taps = d_taps.p;
+    a.scale = scale;
+    a.e = e;
+    prof_begin(s);
+    launch_am(a, (long)nstreams, s);
+    prof_end(s);
+    carry.flip();
+    e = am_next_e(e, (long)n, a.produced, g.I, g.D);
+    total += n;
+    return produced;
+}
+size_t AmDemod::push_host(const cf* in, size_t in_stride, size_t n, float* out, size_t out_stride) {
+    size_t produced = 0;
+    host_call([&] {
+        size_t k = 0;
+        if (const char* err = am_check_push(nstreams, g, e, in, in_stride, n, out, out_stride, &k)) throw Error(err);
+        if (!n) return;
+        const size_t span = am_span_elems(nstreams, in_stride, n);
+        h_in.reserve(span);
+        h_out.reserve(nstreams * k + 1);
+        hstage().h2d(h_in.p, in, span * sizeof(cf), stream);
+        produced = push_dev(h_in.p, in_stride, n, h_out.p, k, stream);
+        for (size_t c = 0; c < nstreams && produced; c++)
+            hstage().d2h(out + c * out_stride, h_out.p + c * k, produced * sizeof(float), stream);
     });
     return produced;
 }

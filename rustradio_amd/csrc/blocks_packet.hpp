@@ -5,6 +5,7 @@
 #include "il2p_host.hpp"
 #include "pwm_host.hpp"
 #include "afsk_host.hpp"
+#include "am_host.hpp"
 #include "fsk_host.hpp"
 #include "kiss_host.hpp"
 
@@ -89,6 +90,12 @@ protected:
 // ComplexToMag2 (complex_to_mag2.rs:8-21): Complex -> re * re + im * im, a sync block.  Bit-exact.
 struct ComplexToMag2 : SyncBlock {
     ComplexToMag2();
+    void run(const void* in, void* out, size_t n, hipStream_t s) override;
+};
+// The first Map of examples/airspy_am_decode.rs ("AirSPY to Complex"): u32 (i16 I low, i16 Q high) -> Complex(i / 1000, q / 1000),
+// a sync block.  Bit-exact.
+struct AirspyDecode : SyncBlock {
+    AirspyDecode();
     void run(const void* in, void* out, size_t n, hipStream_t s) override;
 };
 // SinglePoleIirFilter (single_pole_iir_filter.rs:11-93): y = alpha x + fl32(1 - alpha) y_prev as a tiled f64 scan
@@ -523,6 +530,25 @@ struct AfskDemod : BatchBlock {
               float offset);
     size_t push_dev(const float* d_in, size_t in_stride, size_t n, float* d_out, size_t out_stride, hipStream_t s);   // -> produced
     size_t push_host(const float* in, size_t in_stride, size_t n, float* out, size_t out_stride);
+};
+
+// norm -> FftFilterFloat -> RationalResampler -> MultiplyConst x nstreams over windows of nstreams Complex streams (kernels_am.hip,
+// am_core.hpp): no stream protocol (work_dev is an error).  Each stream's latest L - 1 magnitudes stay on the device between
+// pushes; the host keeps only where the resampler stands (e) and how many samples the streams have taken, which is all a push's
+// counts depend on.
+struct AmDemod : BatchBlock {
+    size_t nstreams;
+    AmGeom g{};
+    float scale;
+    DevBuf<float> d_taps;
+    Carried<float> carry;                         // in(): nstreams x (L - 1), the streams' latest magnitudes (zeros before their start)
+    long e = 0;                                   // output k of the next push sits over its sample (e + k D) / I
+    unsigned long long total = 0;                 // samples every stream has taken
+    DevBuf<float> h_out;                          // push_host(): the host buffers' device copies
+    DevBuf<cf> h_in;
+    AmDemod(size_t nstreams, const float* taps, size_t ntaps, size_t interp, size_t deci, float scale);
+    size_t push_dev(const cf* d_in, size_t in_stride, size_t n, float* d_out, size_t out_stride, hipStream_t s);   // -> produced
+    size_t push_host(const cf* in, size_t in_stride, size_t n, float* out, size_t out_stride);
 };
 
 // The modulators of the two packet transmitters over pushes of u8 line bits (kernels_tx.hip, fsk_core.hpp): no stream protocol

@@ -7,6 +7,7 @@
 #include "pwm_core.hpp"
 #include "symsync_core.hpp"
 #include "afsk_core.hpp"
+#include "am_core.hpp"
 #include "fsk_core.hpp"
 
 namespace rr {
@@ -721,6 +722,15 @@ void launch_sync(const SyncArgs& a, int which, hipStream_t s);
 //      and n are (none for n == 0): grid (tiles of AFSK_TILE outputs, at least one; nstreams).  a.carry_in and a.carry_out are
 //      distinct; a.taps and a.hr are device pointers.
 void launch_afsk(const AfskArgs& a, long nstreams, hipStream_t s);
+
+// ---- kernels_am.hip: norm -> FftFilterFloat (direct form, only the outputs the resampler picks) -> RationalResampler ->
+//      MultiplyConst over the next a.n Complex samples of nstreams independent streams (am_core.hpp holds AmArgs, the arithmetic
+//      and the indexing).  ONE launch whatever nstreams, n, the taps and the ratio are (none for n == 0): grid (tiles of a.g.T
+//      outputs, at least one; nstreams), am_lds_bytes() of LDS.  a.carry_in and a.carry_out are distinct; a.taps is a device pointer.
+size_t am_lds_bytes();
+void launch_am(const AmArgs& a, long nstreams, hipStream_t s);
+// AirSPY u32 samples (i16 I low, i16 Q high) -> Complex(i / 1000, q / 1000), true f32 divisions
+void launch_airspy_decode(const unsigned* in, cf* out, long n, hipStream_t s);
 
 // ---- kernels_pwm.hip: [ComplexToMag2 ->] PwmDecoder (pwm_decoder.rs:385-513) over the next n samples of a stream (pwm_core.hpp
 //      holds the arithmetic) -----------------------------------------------------------------------------------------------------------

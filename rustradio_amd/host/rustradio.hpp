@@ -1384,6 +1384,57 @@ public:
     size_t carry_samples() const { size_t t = 0, c = 0; if (rr_afsk_demod_dims(h_.h, &t, &c) != 0) throw Error(rr_last_error()); return c; }
 };
 
+// ---- AmDemod: Map(norm) -> FftFilterFloat -> RationalResampler -> MultiplyConst (examples/airspy_am_decode.rs) x nstreams ----------
+// (rr_am_demod_create / rr_am_demod_push / rr_am_demod_push_dev / rr_am_demod_dims).  push() takes the next Complex samples of
+// every stream and returns the audio samples they complete: ceil(N interp / deci) per stream after N samples in all.  Each
+// stream's latest magnitudes stay in the block from push to push.
+class AmDemod {
+    detail::Handle h_;
+    size_t nstreams_, interp_, deci_;
+    unsigned long long total_ = 0;
+    static size_t gcd_(size_t a, size_t b) { while (b) { const size_t t = a % b; a = b; b = t; } return a; }
+public:
+    AmDemod(size_t nstreams, const std::vector<float>& taps, size_t interp, size_t deci, float scale)
+        : h_(rr_am_demod_create(nstreams, taps.data(), taps.size(), interp, deci, scale)), nstreams_(nstreams) {
+        const size_t g = gcd_(interp, deci);
+        interp_ = interp / g; deci_ = deci / g;
+    }
+    rr_block* handle() const { return h_.h; }
+    size_t nstreams() const { return nstreams_; }
+    // outputs of each stream a push of n samples would deliver now
+    size_t count(size_t n) const {
+        auto up = [&](unsigned long long N) { return (N * interp_ + deci_ - 1) / deci_; };
+        return (size_t)(up(total_ + n) - up(total_));
+    }
+    // rows[c] = the next samples of stream c, all of one length -> the outputs of stream c, all of one length
+    std::vector<std::vector<float>> push(const std::vector<std::vector<Complex>>& rows) {
+        if (rows.size() != nstreams_) throw Error("AmDemod: one row per stream");
+        const size_t n = rows.empty() ? 0 : rows[0].size(), cap = count(n);
+        std::vector<Complex> in(nstreams_ * n + 1);
+        std::vector<float> out(nstreams_ * cap + 1);
+        for (size_t c = 0; c < nstreams_; c++) {
+            if (rows[c].size() != n) throw Error("AmDemod: rows of one length");
+            std::copy(rows[c].begin(), rows[c].end(), in.begin() + (long)(c * n));
+        }
+        size_t produced = 0;
+        if (rr_am_demod_push(h_.h, reinterpret_cast<const rr_c32*>(in.data()), n, n, out.data(), cap, &produced) != 0) throw Error(rr_last_error());
+        total_ += n;
+        produced = std::min(produced, cap);
+        std::vector<std::vector<float>> res(nstreams_);
+        for (size_t c = 0; c < nstreams_; c++) res[c].assign(out.begin() + (long)(c * cap), out.begin() + (long)(c * cap + produced));
+        return res;
+    }
+    // device windows in the layout of rr_channelizer_create's output; asynchronous on hip_stream -> produced
+    size_t push_dev(const void* d_in, size_t in_stride, size_t n, void* d_out, size_t out_stride, void* hip_stream = nullptr) {
+        size_t produced = 0;
+        if (rr_am_demod_push_dev(h_.h, d_in, in_stride, n, d_out, out_stride, &produced, hip_stream) != 0) throw Error(rr_last_error());
+        total_ += n;
+        return produced;
+    }
+    size_t tile_outputs() const { size_t t = 0, c = 0; if (rr_am_demod_dims(h_.h, &t, &c) != 0) throw Error(rr_last_error()); return t; }
+    size_t carry_samples() const { size_t t = 0, c = 0; if (rr_am_demod_dims(h_.h, &t, &c) != 0) throw Error(rr_last_error()); return c; }
+};
+
 // ---- #[rustradio(sync)] blocks: MultiplyConst (src/multiply_const.rs), FastFM (src/quadrature_demod.rs:144-165) ----------
 // work() per rustradio_macros_code/src/lib.rs:458-515; a tag at position pos < n passes through at pos.
 template <class In, class Out> class SyncBlock : public Block {
@@ -1594,6 +1645,15 @@ public:
     static std::pair<std::unique_ptr<ComplexToMag2>, ReadStream<Float>> new_(ReadStream<Complex> src) {
         auto [w, r] = new_stream<Float>();
         return {std::make_unique<ComplexToMag2>(rr_complex_to_mag2_create(), std::move(src), std::move(w)), std::move(r)};
+    }
+};
+// The first Map of examples/airspy_am_decode.rs ("AirSPY to Complex"): u32 words (i16 I low, i16 Q high) -> Complex(i / 1000, q / 1000)
+class AirspyDecode : public SyncBlock<uint32_t, Complex> {
+public:
+    using SyncBlock<uint32_t, Complex>::SyncBlock;
+    static std::pair<std::unique_ptr<AirspyDecode>, ReadStream<Complex>> new_(ReadStream<uint32_t> src) {
+        auto [w, r] = new_stream<Complex>();
+        return {std::make_unique<AirspyDecode>(rr_airspy_decode_create(), std::move(src), std::move(w)), std::move(r)};
     }
 };
 template <class T> class SinglePoleIirFilter : public SyncBlock<T, T> {
